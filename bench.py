@@ -11,13 +11,15 @@ on): one Trainer_prototype_full iteration with B=16 source + 16 target images pe
 (Trainer_prototype_full.py:261-517).  ``--workload source_only`` (configs[1]): zero_grad -> generator
 forward -> BCE+MSE seg loss -> backward -> Adam (Trainer_baseline.py:198-243).  Data parallel: one process per GPU, per-rank batch fixed (weak
 scaling), one flat RCCL all-reduce of the generator gradients per step; BN statistics stay per rank
-as in the reference.  Rank 0 prints ONE JSON line with the metric, the roofline of the dominant
-kernel (the wide-tile multi-tap implicit GEMM of the 3x3 / 2x2 convolutions, timed live with HIP events on the
-launch stream) and the CPU baseline (the oracle restatement on the host cores, bounded sample).
+as in the reference.  Rank 0 prints ONE JSON line with the metric.  A plain run does only what that line needs: set-up,
+warm-up, the timed steps (``--steps``; ``ms_per_step`` is one of them) and, with ``--dump-outputs DIR``, what the last timed step
+computed.  ``--full`` adds the other measurements: the roofline of the dominant kernel (the wide-tile multi-tap implicit GEMM of
+the 3x3 / 2x2 convolutions, timed live with HIP events on the launch stream inside the timed steps), the PCIe-inclusive rate
+(``host_input``), a short run of the other matrix mode (``other_mfma``) and the CPU baseline (the oracle restatement on the host
+cores, bounded sample), all but the roofline outside the timed region.
 
-``--mfma`` selects the matrix instructions of that kernel: ``bf16x3`` (default) = fp32 emulated on the bf16 pipe by exact
-3-way operand splitting (fp32-level results), ``f32`` = v_mfma_f32_32x32x2_f32.  The line of the default run
-also carries a short measurement of the other mode (``other_mfma``), outside the timed region.
+``--mfma`` selects the matrix instructions of the wide conv tiles: ``bf16x3`` (default) = fp32 emulated on the bf16 pipe by exact
+3-way operand splitting (fp32-level results), ``f32`` = v_mfma_f32_32x32x2_f32.
 """
 import argparse
 import json
@@ -25,6 +27,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -258,6 +261,33 @@ def cpu_baseline(workload, B, S, backbone="mobilenet"):
                          {k: round(v, 2) for k, v in probes.items()})}
 
 
+DUMP_BYTES = 64 * 10 ** 6 - 2 ** 16      # --dump-outputs: at most 64 MB in all, .npy headers included
+
+
+def step_outputs(last, models):
+    """What a caller of the timed step holds after its last call: the step's return values (the logged losses) and the state
+    the step trained (each network's floating-point state_dict entries - parameters and BatchNorm statistics - flattened in
+    state_dict order)."""
+    losses = last if isinstance(last, list) else [last.item()]
+    arrays = {"losses": np.asarray(losses, dtype=np.float64)}
+    for name, m in models.items():
+        ts = [v.detach().reshape(-1).float() for v in m.state_dict().values() if v.is_floating_point()]
+        arrays[name] = torch.cat(ts).cpu().numpy()
+    return arrays
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array.  A set larger than DUMP_BYTES keeps its small arrays whole and a fixed, seeded sample of
+    each large one (sorted positions, the same from run to run for the same arguments)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    rng = np.random.default_rng(1337)
+    for name, a in arrays.items():
+        if total > DUMP_BYTES and a.size > 4096:
+            a = a[np.sort(rng.choice(a.size, a.size * DUMP_BYTES // total, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` with no launcher environment: become the launcher.  Starts
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <argv>` as a CHILD
@@ -347,11 +377,16 @@ def main():
                     help="resnet = the ResNet-101 variant of BASELINE.json configs[4] (quoted at --batch 8)")
     ap.add_argument("--use-tn", action="store_true",
                     help="the --use_TN model of train_use_fix_initial.py:98-100,180-181 (TransNorm layers; not a BASELINE.json config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--mfma", choices=("bf16x3", "f32"), default=None,
                     help="matrix instructions of the wide conv tiles (default: UDA_CLR_MFMA or bf16x3)")
-    ap.add_argument("--no-other-mfma", action="store_true", help="skip the short measurement of the other matrix mode")
-    ap.add_argument("--no-host-input", action="store_true", help="skip the PCIe-inclusive measurement (batches handed over from pinned host memory)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, trained network state) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the dominant kernel's roofline, the PCIe-inclusive rate, the other matrix mode and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-mfma", action="store_true", help="with --full: skip the short measurement of the other matrix mode")
+    ap.add_argument("--no-host-input", action="store_true",
+                    help="with --full: skip the PCIe-inclusive measurement (batches handed over from pinned host memory)")
     ap.add_argument("--stub-step", action="store_true", help=argparse.SUPPRESS)   # launcher / timing-protocol rehearsal on CPU + gloo (tests)
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -416,6 +451,7 @@ def main():
             opt.step()
             return loss
         per_step = args.batch
+        trained = {"generator": model}
     else:
         d1, d2 = BoundaryDiscriminator().to(dev).train(), UncertaintyDiscriminator().to(dev).train()
         od = torch.optim.SGD(d1.parameters(), lr=2.5e-5, momentum=0.99, weight_decay=5e-4)
@@ -430,11 +466,12 @@ def main():
         def step():
             return tr.train_step(sampleS, sampleT)
         per_step = 2 * args.batch          # source + target images (the metric counts both)
+        trained = {"generator": model, "boundary_discriminator": d1, "uncertainty_discriminator": d2}
 
     for _ in range(args.warmup):
         step()
     from uda_clr_amd.kernels import HipKernels
-    timer = ConvTimer(HipKernels)
+    timer = ConvTimer(HipKernels) if args.full else None
 
     def sync():
         if dist is not None:
@@ -442,26 +479,31 @@ def main():
         torch.cuda.synchronize()
 
     sync()
-    timer.enabled = True
+    if timer is not None:
+        timer.enabled = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
         last = step()
     sync()
     dt = time.perf_counter() - t0
-    timer.enabled = False
+    if timer is not None:
+        timer.enabled = False
     peak_gib = torch.cuda.max_memory_allocated(dev) / 2.0 ** 30
     if dist is not None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     losses = [round(float(v), 5) for v in (last if isinstance(last, list) else [last.item()])]
+    if args.dump_outputs and rank == 0:           # before --full's extra steps train the networks further
+        dump_outputs(args.dump_outputs, step_outputs(last, trained))
     # the other matrix mode, outside the timed region: same step, 2 warm-up + 5 timed steps (all ranks take part)
     other = None
-    timer.restore()
     host = None
-    if args.workload == "prototype_full" and not args.no_host_input:
+    if timer is not None:
+        timer.restore()
+    if args.full and args.workload == "prototype_full" and not args.no_host_input:
         host = host_input_leg(tr, args, per_step, world, sync, dist, dev, img, tmap, tbd, imgT)
-    if not args.no_other_mfma:
+    if args.full and not args.no_other_mfma:
         om = "f32" if mode == "bf16x3" else "bf16x3"
         insts = [o for o in __import__("gc").get_objects() if isinstance(o, HipKernels)]
         for o in insts:
@@ -505,9 +547,10 @@ def main():
                                 "bf16 matrix pipe with every fp32 operand split exactly into three bf16 pieces (six piece products, "
                                 "fp32 accumulate) - fp32-level results, error against float64 measured equal to the fp32-MFMA "
                                 "kernel's (DESIGN.md 3d, tests/bench_x3.py); the exact fp32-MFMA path is `--mfma f32`, measured "
-                                "in `other_mfma`") if mode == "bf16x3" else "f32: v_mfma_f32_32x32x2_f32 (exact fp32 fma chain)"},
-            "roofline": timer.summary(mode, measured_traffic(args, mode)),
+                                "in `other_mfma` of a --full run") if mode == "bf16x3" else "f32: v_mfma_f32_32x32x2_f32 (exact fp32 fma chain)"},
         }
+        if timer is not None:
+            line["roofline"] = timer.summary(mode, measured_traffic(args, mode))
         # step-level figures of SURVEY.md 8(d): algorithmic GFLOP / GB per counted image (reference algorithm,
         # i.e. the 4 MC passes counted as full forwards although the fast path recomputes only their stochastic tail)
         gflop = {("mobilenet", "source_only"): 158.2, ("mobilenet", "prototype_full"): 478.0,
@@ -539,11 +582,13 @@ def main():
                 gbs = line["value"] / world * gb_img
                 line["step_roofline"].update(algorithmic_gb_per_image=gb_img, achieved_gb_s_per_gpu=round(gbs, 1),
                                              hbm_frac=round(gbs / 8000.0, 4))
-        if world == 1 and not args.no_cpu_baseline and not args.use_tn:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.use_tn:
             line["cpu_baseline"] = cpu_baseline(args.workload, 2, args.size, args.backbone)
-        line["other_mfma"] = other
+        if args.full:
+            line["other_mfma"] = other
         line["peak_hbm_gib"] = round(peak_gib, 2)          # torch allocator peak of this rank up to the end of the timed region (of 288)
-        line["host_input"] = host
+        if args.full:
+            line["host_input"] = host
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

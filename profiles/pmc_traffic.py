@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """HBM traffic per launch of the dominant kernel from two rocprofv3 PMC passes (MI355X_MICROARCH.md, HBM):
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out/f -o f -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d out/w -o w -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out/f -o f -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d out/w -o w -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
     python profiles/pmc_traffic.py out/f/..._counter_collection.csv out/w/..._counter_collection.csv --match 'igemm_conv_ws_kernel<3'
 (--match takes comma-separated substrings; --calls N divides the total by the number of conv calls instead of kernel launches)
 

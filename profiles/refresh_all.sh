@@ -15,11 +15,11 @@ echo "so rn tn done"
 # ResNet-101 (BASELINE.json configs[4] shape on one GPU): PMC traffic of its dominant kernel (the bf16x3 multi-tap conv)
 EXTRA="--backbone resnet --workload source_only --batch 8" bash profiles/run_profiles.sh $OUT/rn pmc > $OUT/rn_pmc.log 2>&1 || { echo "resnet pmc failed"; exit 1; }
 echo "resnet pmc done"
-python3 bench.py --backbone resnet --workload source_only --batch 8 --steps 10 > $OUT/bench_rn_b8.log 2>&1 || { echo "bench rn failed"; exit 1; }
+python3 bench.py --full --backbone resnet --workload source_only --batch 8 --steps 10 > $OUT/bench_rn_b8.log 2>&1 || { echo "bench rn failed"; exit 1; }
 grep '^{' $OUT/bench_rn_b8.log | tail -1 > $OUT/bench_rn_b8.json
-python3 bench.py > $OUT/bench_b16.log 2>&1 || { echo "bench b16 failed"; exit 1; }
+python3 bench.py --full > $OUT/bench_b16.log 2>&1 || { echo "bench b16 failed"; exit 1; }
 grep '^{' $OUT/bench_b16.log | tail -1 > $OUT/bench_b16.json
-python3 bench.py --batch 32 --steps 5 > $OUT/bench_b32.log 2>&1 || { echo "bench b32 failed"; exit 1; }
+python3 bench.py --full --batch 32 --steps 5 > $OUT/bench_b32.log 2>&1 || { echo "bench b32 failed"; exit 1; }
 grep '^{' $OUT/bench_b32.log | tail -1 > $OUT/bench_b32.json
 echo "bench lines done"
 python3 tests/bench_x3.py > $OUT/bench_x3.txt 2>&1 || { echo "bench_x3 failed"; exit 1; }

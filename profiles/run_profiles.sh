@@ -7,7 +7,7 @@ set -o pipefail
 # (default: the bf16x3 dominant kernel; 'igemm_conv_ws_kernel<3' with EXTRA="--mfma f32").
 OUT=${1:-gpurun_out/prof}; shift
 WHAT=${@:-pf so rn pmc}
-EXTRA="${EXTRA:-} --no-other-mfma --no-host-input"
+EXTRA="${EXTRA:-} --full --no-other-mfma --no-host-input"
 PMC_MATCH=${PMC_MATCH:-igemm_conv_x3_kernel<3,x3_tail_reduce_kernel}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
