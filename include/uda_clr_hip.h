@@ -127,7 +127,8 @@ uint64_t uda_conv_wgrad_workspace_bytes(int64_t P, int Cout, int Cin, int ksize)
 int uda_conv_wgrad_uses_x3(const uda_wgrad_args_t* a);
 int uda_conv_wgrad(const uda_wgrad_args_t* a, void* stream);
 
-/* ---- depthwise 3x3 (mobilenet.py:39,53): stride 1|2, dilation 1|2, "pad 0 on a padded input".
+/* ---- depthwise 3x3 (mobilenet.py:39,53): stride 1|2, dilation 1|2|4, "pad 0 on a padded input"; C <= 1024 on these
+ * kernels, C <= 2048 routed to the channel-blocked ones below.
  * border_mode 0: out-of-image taps read 0; 1: they read act(shift[c]) (quirk Q1). */
 uint64_t uda_dwconv_workspace_bytes(int64_t Pout, int C);
 int uda_dwconv_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
@@ -137,6 +138,17 @@ int uda_dwconv_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int
 int uda_dwconv_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
                      int border_mode, float* dw /* [C][9] */, float* workspace,
                      uint64_t workspace_bytes, void* stream);
+
+/* ---- channel-blocked depthwise 3x3 (Aligned Xception, networks/backbone/xception.py:17-31: 728 ... 2048 channels, stride
+ * 1|2, dilation 1|2|4, zero border after the activation - fixed_padding, :8-14).  Same arguments and layouts as the three
+ * entries above, C any multiple of 4 up to 2048; those entries route C > 1024 (and dilation 4 at C >= 1024) here.  Workspace: uda_dwconv_workspace_bytes. */
+int uda_dwconv_cb_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
+                      float* y, int64_t ldy, double* stats /* [SLOTS][2][C] or NULL */, void* stream);
+int uda_dwconv_cb_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
+                        int N, int H, int W, float* dx, int64_t lddx, void* stream);
+int uda_dwconv_cb_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
+                        int border_mode, float* dw /* [C][9] */, float* workspace,
+                        uint64_t workspace_bytes, void* stream);
 
 /* ---- stem conv 3x3 stride 2 pad 1, 3 -> 32, NCHW image in, NHWC out (mobilenet.py:10) */
 uint64_t uda_stem_workspace_bytes(int64_t Pout);

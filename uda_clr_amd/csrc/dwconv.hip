@@ -429,9 +429,255 @@ __global__ void dw_wgrad_store_kernel(const double* __restrict__ sums, int C, fl
     if (e < 9 * C) dw[(e % C) * 9 + e / C] = (float)sums[e];
 }
 
-static int dw_check(const uda_src_t* s, const char* who) {
+// ------------------------------------------------------------------------------------------
+// Channel-blocked strip kernels (Aligned Xception: 728 ... 2048 channels, dilation 1 / 2 / 4).  The kernels above map
+// ALL C/4 float4 groups of a pixel into one workgroup (flat: C <= 1024, LDS sized for it) or tile 32 channels x a 2-D
+// halo (dilation <= 2).  Here a workgroup owns a channel block of CG float4 groups (CG = the power of two >= C/4, at
+// most 64: 256 channels) x a strip of consecutive output pixels, PL = 256 / CG pixel lanes wide, ITER pixels per lane:
+// a wave reads 64 / CG pixel rows of CG * 16 contiguous bytes, every lane busy whatever the width (1536 = 6 blocks of
+// 64 groups; 728 = 3 blocks, 10 of 192 groups idle).  The nine taps of a pixel are loaded back to back from clamped
+// positions (zeroed / replaced by the border value afterwards), the producer's BN affine + activation applied on load,
+// and the 9x re-read of each input row is served by L1 / L2 (the strip walks the image row-major).  Statistics / weight
+// gradients: fp32 per thread and through one LDS reduction per workgroup, fp64 atomics across workgroups into
+// UDA_STAT_SLOTS replicas.
+#define DWB_ITER_FWD 8
+#define DWB_ITER_RED 32
+#define DWB_CMAX 2048
+
+static inline int dwb_lg_groups(int C) {          // log2(CG)
+    int lg = 0;
+    while ((1 << lg) < C / 4 && lg < 6) ++lg;
+    return lg;
+}
+
+__device__ __forceinline__ void dwb_pixel(int64_t po, int Wo, int Ho, int& n, int& oh, int& ow) {
+    ow = (int)(po % Wo);
+    const int64_t r = po / Wo;
+    oh = (int)(r % Ho);
+    n = (int)(r / Ho);
+}
+
+// the nine (transformed) taps of output pixel (n, oh, ow) for the channels at xc (= src.x + c0)
+__device__ __forceinline__ void dwb_taps(float4 (&u)[9], const float* xc, int64_t ldx, int H, int W, int n, int oh, int ow,
+                                         int stride, int dil, const Xf4& xf, bool has_xf, int act, float4 bval) {
+    float4 v[9];
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+        const int ih = min(max(oh * stride + (kh - 1) * dil, 0), H - 1);
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+            const int iw = min(max(ow * stride + (kw - 1) * dil, 0), W - 1);
+            v[kh * 3 + kw] = uda_ld4(xc + (((int64_t)n * H + ih) * W + iw) * ldx);
+        }
+    }
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+        const int ih = oh * stride + (kh - 1) * dil;
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+            const int iw = ow * stride + (kw - 1) * dil;
+            const bool in = ih >= 0 && ih < H && iw >= 0 && iw < W;
+            u[kh * 3 + kw] = in ? dw_transform(v[kh * 3 + kw], xf, has_xf, act) : bval;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void dwconv_cb_fwd_kernel(DwArgs a, int lg) {
+    __shared__ __attribute__((aligned(16))) float red[2 * 256 * 4];      // [2][PL][CG*4]
+    const int CG = 1 << lg, PL = 256 >> lg;
+    const int C = a.src.C, G = C >> 2, H = a.src.H, W = a.src.W;
+    const int tid = threadIdx.x, cl = tid & (CG - 1), pl = tid >> lg;
+    const int cg = blockIdx.y * CG + cl;
+    const bool cok = cg < G;
+    const int c0 = (cok ? cg : G - 1) * 4;               // idle lanes of the last block read a valid group and store nothing
+    const int64_t Pout = (int64_t)a.src.N * a.Ho * a.Wo;
+    const bool has_xf = a.src.scale != nullptr;
+    const int act = a.src.act;
+    Xf4 xf;
+    uda_load_xf4(xf, a.src.scale, a.src.shift, c0, C);
+    float4 bval = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.border_mode == 1)
+        bval = make_float4(uda_act(xf.sh[0], act), uda_act(xf.sh[1], act), uda_act(xf.sh[2], act), uda_act(xf.sh[3], act));
+    float4 w[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) w[t] = uda_ld4(a.w9c + t * C + c0);
+    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+    const float* xc = a.src.x + c0;
+    const int64_t base = (int64_t)blockIdx.x * PL * DWB_ITER_FWD;
+    for (int it = 0; it < DWB_ITER_FWD; ++it) {
+        const int64_t po = base + (int64_t)it * PL + pl;
+        if (po >= Pout) break;
+        int n, oh, ow;
+        dwb_pixel(po, a.Wo, a.Ho, n, oh, ow);
+        float4 u[9];
+        dwb_taps(u, xc, a.src.ldx, H, W, n, oh, ow, a.stride, a.dil, xf, has_xf, act, bval);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            acc.x += w[t].x * u[t].x; acc.y += w[t].y * u[t].y; acc.z += w[t].z * u[t].z; acc.w += w[t].w * u[t].w;
+        }
+        if (cok) {
+            uda_st4(a.y + po * a.ldy + c0, acc);
+            s1.x += acc.x; s1.y += acc.y; s1.z += acc.z; s1.w += acc.w;
+            s2.x += acc.x * acc.x; s2.y += acc.y * acc.y; s2.z += acc.z * acc.z; s2.w += acc.w * acc.w;
+        }
+    }
+    if (a.stats == nullptr) return;
+    uda_st4(&red[((0 * PL + pl) * CG + cl) * 4], s1);
+    uda_st4(&red[((1 * PL + pl) * CG + cl) * 4], s2);
+    __syncthreads();
+    double* dst = a.stats + (int64_t)(blockIdx.x % UDA_STAT_SLOTS) * 2 * C;
+    for (int e = tid; e < 2 * CG * 4; e += 256) {
+        const int q = e / (CG * 4), cc = e - q * (CG * 4);
+        const int c = blockIdx.y * CG * 4 + cc;
+        if (c >= C) continue;
+        float t = 0.f;
+        for (int p = 0; p < PL; ++p) t += red[(q * PL + p) * CG * 4 + cc];
+        atomicAdd(&dst[q * C + c], (double)t);
+    }
+}
+
+__global__ __launch_bounds__(256) void dwconv_cb_wgrad_kernel(DwArgs a, int lg, double* sums) {
+    __shared__ __attribute__((aligned(16))) float red[9 * 256 * 4];      // [PL][9][CG*4]
+    const int CG = 1 << lg, PL = 256 >> lg;
+    const int C = a.src.C, G = C >> 2, H = a.src.H, W = a.src.W;
+    const int tid = threadIdx.x, cl = tid & (CG - 1), pl = tid >> lg;
+    const int cg = blockIdx.y * CG + cl;
+    const bool cok = cg < G;
+    const int c0 = (cok ? cg : G - 1) * 4;
+    const int64_t Pout = (int64_t)a.src.N * a.Ho * a.Wo;
+    const bool has_xf = a.src.scale != nullptr;
+    const int act = a.src.act;
+    Xf4 xf;
+    uda_load_xf4(xf, a.src.scale, a.src.shift, c0, C);
+    float4 bval = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.border_mode == 1)
+        bval = make_float4(uda_act(xf.sh[0], act), uda_act(xf.sh[1], act), uda_act(xf.sh[2], act), uda_act(xf.sh[3], act));
+    float4 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float* xc = a.src.x + c0;
+    const int64_t base = (int64_t)blockIdx.x * PL * DWB_ITER_RED;
+    for (int it = 0; it < DWB_ITER_RED; ++it) {
+        const int64_t po = base + (int64_t)it * PL + pl;
+        if (po >= Pout) break;
+        int n, oh, ow;
+        dwb_pixel(po, a.Wo, a.Ho, n, oh, ow);
+        const float4 g = uda_ld4(a.dy + po * a.lddy + c0);
+        float4 u[9];
+        dwb_taps(u, xc, a.src.ldx, H, W, n, oh, ow, a.stride, a.dil, xf, has_xf, act, bval);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            acc[t].x += g.x * u[t].x; acc[t].y += g.y * u[t].y; acc[t].z += g.z * u[t].z; acc[t].w += g.w * u[t].w;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) uda_st4(&red[((pl * 9 + t) * CG + cl) * 4], acc[t]);
+    __syncthreads();
+    double* dst = sums + (int64_t)(blockIdx.x % UDA_STAT_SLOTS) * 9 * C;
+    for (int e = tid; e < 9 * CG * 4; e += 256) {
+        const int t = e / (CG * 4), cc = e - t * (CG * 4);
+        const int c = blockIdx.y * CG * 4 + cc;
+        if (c >= C) continue;
+        float v = 0.f;
+        for (int p = 0; p < PL; ++p) v += red[(p * 9 + t) * CG * 4 + cc];
+        atomicAdd(&dst[t * C + c], (double)v);
+    }
+}
+
+// input gradient (interior H x W positions of the padded input): every (tap, output) pair that reads input pixel p, the
+// nine candidates loaded back to back from clamped positions and weighted 0 where they do not exist; same tap order as
+// dwconv_dgrad_kernel's general loop
+__global__ __launch_bounds__(256) void dwconv_cb_dgrad_kernel(const float* __restrict__ dy, int64_t lddy,
+                                                               const float* __restrict__ w9c, int C, int stride, int dil,
+                                                               int N, int H, int W, int Ho, int Wo,
+                                                               float* __restrict__ dx, int64_t lddx, int lg) {
+    const int CG = 1 << lg, PL = 256 >> lg, G = C >> 2;
+    const int tid = threadIdx.x, cl = tid & (CG - 1), pl = tid >> lg;
+    const int cg = blockIdx.y * CG + cl;
+    const bool cok = cg < G;
+    const int c0 = (cok ? cg : G - 1) * 4;
+    const int64_t P = (int64_t)N * H * W;
+    float4 w[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) w[t] = uda_ld4(w9c + t * C + c0);
+    const int64_t base = (int64_t)blockIdx.x * PL * DWB_ITER_FWD;
+    for (int it = 0; it < DWB_ITER_FWD; ++it) {
+        const int64_t p = base + (int64_t)it * PL + pl;
+        if (p >= P) break;
+        int n, ih, iw;
+        dwb_pixel(p, W, H, n, ih, iw);
+        int oh[3], ow[3];
+        bool vh[3], vw[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int nh = ih - (k - 1) * dil, nw = iw - (k - 1) * dil;
+            vh[k] = nh >= 0 && nh % stride == 0 && nh / stride < Ho;
+            vw[k] = nw >= 0 && nw % stride == 0 && nw / stride < Wo;
+            oh[k] = vh[k] ? nh / stride : 0;
+            ow[k] = vw[k] ? nw / stride : 0;
+        }
+        const float* base_n = dy + (int64_t)n * Ho * Wo * lddy + c0;
+        float4 g[9];
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) g[kh * 3 + kw] = uda_ld4(base_n + ((int64_t)oh[kh] * Wo + ow[kw]) * lddy);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                if (!(vh[kh] && vw[kw])) continue;
+                const float4 ww = w[kh * 3 + kw], gg = g[kh * 3 + kw];
+                acc.x += ww.x * gg.x; acc.y += ww.y * gg.y; acc.z += ww.z * gg.z; acc.w += ww.w * gg.w;
+            }
+        if (cok) uda_st4(dx + p * lddx + c0, acc);
+    }
+}
+
+static int dwb_fwd(DwArgs& a, hipStream_t st) {
+    const int lg = dwb_lg_groups(a.src.C);
+    const int64_t Pout = (int64_t)a.src.N * a.Ho * a.Wo;
+    const dim3 grid(uda_cdiv(Pout, (int64_t)(256 >> lg) * DWB_ITER_FWD), uda_cdiv(a.src.C / 4, 1 << lg));
+    hipLaunchKernelGGL(dwconv_cb_fwd_kernel, grid, dim3(256), 0, st, a, lg);
+    UDA_LAUNCH_CHECK("dwconv_cb_fwd");
+    return 0;
+}
+
+static int dwb_wgrad(DwArgs& a, double* sums, float* dw, hipStream_t st) {
+    const int C = a.src.C, lg = dwb_lg_groups(C);
+    const int64_t Pout = (int64_t)a.src.N * a.Ho * a.Wo;
+    (void)hipMemsetAsync(sums, 0, (size_t)UDA_STAT_SLOTS * 9 * C * sizeof(double), st);
+    const dim3 grid(uda_cdiv(Pout, (int64_t)(256 >> lg) * DWB_ITER_RED), uda_cdiv(C / 4, 1 << lg));
+    hipLaunchKernelGGL(dwconv_cb_wgrad_kernel, grid, dim3(256), 0, st, a, lg, sums);
+    UDA_LAUNCH_CHECK("dwconv_cb_wgrad");
+    hipLaunchKernelGGL(dw_wgrad_store_slots_kernel, dim3(uda_cdiv(9 * C, 256)), dim3(256), 0, st, sums, C, dw);
+    UDA_LAUNCH_CHECK("dw_wgrad_store");
+    return 0;
+}
+
+static int dwb_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil, int N, int H, int W,
+                     float* dx, int64_t lddx, hipStream_t st) {
+    const int lg = dwb_lg_groups(C);
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const int64_t P = (int64_t)N * H * W;
+    const dim3 grid(uda_cdiv(P, (int64_t)(256 >> lg) * DWB_ITER_FWD), uda_cdiv(C / 4, 1 << lg));
+    hipLaunchKernelGGL(dwconv_cb_dgrad_kernel, grid, dim3(256), 0, st, dy, lddy, w9c, C, stride, dil, N, H, W, Ho, Wo, dx, lddx, lg);
+    UDA_LAUNCH_CHECK("dwconv_cb_dgrad");
+    return 0;
+}
+
+// Shape rule of the C entries (measured on MI355X at Xception's 512^2, B = 16 shapes, profiles/xception_dw_kernels.md): the
+// channel-blocked kernels take the widths the other families reject (C > 1024) and the dilation-4 convs of 1024 channels
+// (fwd 343 -> 235 us, wgrad 346 -> 258 us against the flat kernel).  At 728 / 1024 channels with dilation <= 2 the LDS-tiled
+// kernels stay (fwd 25 / 31 us against 44 / 52 us).  Every MobileNetV2 launch (C <= 960) keeps its kernel; ResNet-101 has
+// no depthwise conv.
+static inline bool dw_use_cb(int C, int dil) { return C > 1024 || (dil > 2 && C >= 1024); }
+
+static int dw_check(const uda_src_t* s, const char* who, int cmax = 1024) {
     UDA_REQUIRE(s && s->x && uda_aligned16(s->x) && s->ldx % 4 == 0 && s->ldx >= s->C, "%s: bad src", who);
-    UDA_REQUIRE(s->C % 4 == 0 && s->C >= 4 && s->C <= 1024, "%s: C=%d must be a multiple of 4 in [4,1024]", who, s->C);
+    UDA_REQUIRE(s->C % 4 == 0 && s->C >= 4 && s->C <= cmax, "%s: C=%d must be a multiple of 4 in [4,%d]", who, s->C, cmax);
     UDA_REQUIRE((s->scale == nullptr) == (s->shift == nullptr), "%s: scale/shift must come together", who);
     UDA_REQUIRE(s->mask == nullptr, "%s: dropout masks are not supported on depthwise inputs", who);
     return 0;
@@ -441,15 +687,16 @@ static inline int dw_pixels_per_wg(int C, int iter) { return (256 / (C / 4)) * i
 
 extern "C" uint64_t uda_dwconv_workspace_bytes(int64_t Pout, int C) {
     if (C < 4) return 0;
+    const uint64_t tiled = (uint64_t)UDA_STAT_SLOTS * 9 * C * sizeof(double);     // (the channel-blocked kernels' too)
+    if (C > 1024) return tiled;
     const uint64_t flat = (uint64_t)uda_cdiv(Pout, dw_pixels_per_wg(C, DW_ITER_RED)) * 9 * C * sizeof(float) + 9 * C * sizeof(double);
-    const uint64_t tiled = (uint64_t)UDA_STAT_SLOTS * 9 * C * sizeof(double);
     return flat > tiled ? flat : tiled;
 }
 
-extern "C" int uda_dwconv_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
-                              float* y, int64_t ldy, double* stats, void* stream) {
+static int dw_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
+                  float* y, int64_t ldy, double* stats, void* stream, bool cb) {
     hipStream_t st = (hipStream_t)stream;
-    if (int e = dw_check(src, "uda_dwconv_fwd")) return e;
+    if (int e = dw_check(src, "uda_dwconv_fwd", cb ? DWB_CMAX : 1024)) return e;
     UDA_REQUIRE(w9c && uda_aligned16(w9c) && y && uda_aligned16(y) && ldy % 4 == 0 && ldy >= src->C, "uda_dwconv_fwd: bad pointers");
     UDA_REQUIRE((stride == 1 || stride == 2) && dil >= 1, "uda_dwconv_fwd: stride must be 1 or 2");
     UDA_REQUIRE(border_mode == 0 || (border_mode == 1 && src->shift), "uda_dwconv_fwd: border_mode 1 needs shift");
@@ -460,10 +707,11 @@ extern "C" int uda_dwconv_fwd(const uda_src_t* src, const float* w9c, int stride
     a.Ho = (src->H - 1) / stride + 1;
     a.Wo = (src->W - 1) / stride + 1;
     a.y = y; a.ldy = ldy; a.dy = nullptr; a.lddy = 0;
-    const int64_t Pout = (int64_t)src->N * a.Ho * a.Wo;
-    const int nwg = uda_cdiv(Pout, dw_pixels_per_wg(src->C, DW_ITER_FWD));
     a.part = nullptr;
     a.stats = stats;
+    if (cb) return dwb_fwd(a, st);
+    const int64_t Pout = (int64_t)src->N * a.Ho * a.Wo;
+    const int nwg = uda_cdiv(Pout, dw_pixels_per_wg(src->C, DW_ITER_FWD));     // (C <= 1024 here: at least one pixel per workgroup)
     static const bool flat = getenv("UDA_DW_FLAT") != nullptr;      // diagnostics: the untiled kernel
     if (!flat && dil <= 2) return stride == 1 ? launch_dw_tiled<1, 8, 16>(a, st) : launch_dw_tiled<2, 8, 8>(a, st);
     hipLaunchKernelGGL(dwconv_fwd_kernel, dim3(nwg), dim3(256), 0, st, a);
@@ -471,11 +719,25 @@ extern "C" int uda_dwconv_fwd(const uda_src_t* src, const float* w9c, int stride
     return 0;
 }
 
-extern "C" int uda_dwconv_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
-                                int N, int H, int W, float* dx, int64_t lddx, void* stream) {
+extern "C" int uda_dwconv_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
+                              float* y, int64_t ldy, double* stats, void* stream) {
+    return dw_fwd(src, w9c, stride, dil, border_mode, y, ldy, stats, stream, src && dw_use_cb(src->C, dil));
+}
+
+extern "C" int uda_dwconv_cb_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
+                                 float* y, int64_t ldy, double* stats, void* stream) {
+    return dw_fwd(src, w9c, stride, dil, border_mode, y, ldy, stats, stream, true);
+}
+
+static int dw_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
+                    int N, int H, int W, float* dx, int64_t lddx, void* stream, bool cb) {
     UDA_REQUIRE(dy && w9c && dx && uda_aligned16(dy) && uda_aligned16(dx) && uda_aligned16(w9c), "uda_dwconv_dgrad: pointers must be 16-byte aligned");
     UDA_REQUIRE(C % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && lddy >= C && lddx >= C, "uda_dwconv_dgrad: C and lds must be multiples of 4");
     UDA_REQUIRE((stride == 1 || stride == 2) && dil >= 1 && N > 0 && H > 0 && W > 0, "uda_dwconv_dgrad: bad geometry");
+    if (cb) {
+        UDA_REQUIRE(C >= 4 && C <= DWB_CMAX, "uda_dwconv_dgrad: C=%d must be in [4,%d]", C, DWB_CMAX);
+        return dwb_dgrad(dy, lddy, w9c, C, stride, dil, N, H, W, dx, lddx, (hipStream_t)stream);
+    }
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const int64_t total = (int64_t)N * H * W * (C / 4);
     int grid = uda_cdiv(total, 256);
@@ -486,10 +748,20 @@ extern "C" int uda_dwconv_dgrad(const float* dy, int64_t lddy, const float* w9c,
     return 0;
 }
 
-extern "C" int uda_dwconv_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
-                                int border_mode, float* dw, float* workspace, uint64_t workspace_bytes, void* stream) {
+extern "C" int uda_dwconv_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
+                                int N, int H, int W, float* dx, int64_t lddx, void* stream) {
+    return dw_dgrad(dy, lddy, w9c, C, stride, dil, N, H, W, dx, lddx, stream, dw_use_cb(C, dil));
+}
+
+extern "C" int uda_dwconv_cb_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
+                                   int N, int H, int W, float* dx, int64_t lddx, void* stream) {
+    return dw_dgrad(dy, lddy, w9c, C, stride, dil, N, H, W, dx, lddx, stream, true);
+}
+
+static int dw_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
+                    int border_mode, float* dw, float* workspace, uint64_t workspace_bytes, void* stream, bool cb) {
     hipStream_t st = (hipStream_t)stream;
-    if (int e = dw_check(src, "uda_dwconv_wgrad")) return e;
+    if (int e = dw_check(src, "uda_dwconv_wgrad", cb ? DWB_CMAX : 1024)) return e;
     UDA_REQUIRE(dy && uda_aligned16(dy) && lddy % 4 == 0 && lddy >= src->C && dw, "uda_dwconv_wgrad: bad pointers");
     UDA_REQUIRE((stride == 1 || stride == 2) && dil >= 1, "uda_dwconv_wgrad: stride must be 1 or 2");
     UDA_REQUIRE(border_mode == 0 || (border_mode == 1 && src->shift), "uda_dwconv_wgrad: border_mode 1 needs shift");
@@ -502,8 +774,9 @@ extern "C" int uda_dwconv_wgrad(const uda_src_t* src, const float* dy, int64_t l
     a.y = nullptr; a.ldy = 0; a.dy = dy; a.lddy = lddy; a.stats = nullptr;
     const int C = src->C;
     const int64_t Pout = (int64_t)src->N * a.Ho * a.Wo;
-    const int nwg = uda_cdiv(Pout, dw_pixels_per_wg(C, DW_ITER_RED));
     UDA_REQUIRE(workspace && workspace_bytes >= uda_dwconv_workspace_bytes(Pout, C), "uda_dwconv_wgrad: workspace too small");
+    if (cb) return dwb_wgrad(a, reinterpret_cast<double*>(workspace), dw, st);
+    const int nwg = uda_cdiv(Pout, dw_pixels_per_wg(C, DW_ITER_RED));
     static const bool flat = getenv("UDA_DW_FLAT") != nullptr;
     if (!flat && dil <= 2) {
         double* slot_sums = reinterpret_cast<double*>(workspace);
@@ -518,6 +791,16 @@ extern "C" int uda_dwconv_wgrad(const uda_src_t* src, const float* dy, int64_t l
     hipLaunchKernelGGL(dw_wgrad_store_kernel, dim3(uda_cdiv(9 * C, 256)), dim3(256), 0, st, sums, C, dw);
     UDA_LAUNCH_CHECK("dw_wgrad_store");
     return 0;
+}
+
+extern "C" int uda_dwconv_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
+                                int border_mode, float* dw, float* workspace, uint64_t workspace_bytes, void* stream) {
+    return dw_wgrad(src, dy, lddy, stride, dil, border_mode, dw, workspace, workspace_bytes, stream, src && dw_use_cb(src->C, dil));
+}
+
+extern "C" int uda_dwconv_cb_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
+                                   int border_mode, float* dw, float* workspace, uint64_t workspace_bytes, void* stream) {
+    return dw_wgrad(src, dy, lddy, stride, dil, border_mode, dw, workspace, workspace_bytes, stream, true);
 }
 
 // ==========================================================================================

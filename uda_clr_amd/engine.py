@@ -1,4 +1,4 @@
-"""Execution plan of the DeepLabV3+ generator (MobileNetV2 or ResNet-101 backbone) on the HIP kernels.
+"""Execution plan of the DeepLabV3+ generator (MobileNetV2, ResNet-101 or Aligned Xception backbone) on the HIP kernels.
 
 The whole generator is ONE autograd node (``networks.deeplabv3._GeneratorFn``): this module runs
 its forward as a fixed sequence of kernel launches on NHWC buffers and its backward as the
@@ -159,6 +159,14 @@ class GeneratorEngine:
             n = 64
             for pre, inp, planes, stride, dil, has_ds in self.rblocks:
                 n += 2 * planes + 4 * planes * (2 if has_ds else 1)
+        elif backbone == "xception":
+            from .networks.backbone.xception import exit_plan, xception_plan
+            self.xblocks, self.xexit = xception_plan(output_stride), exit_plan(output_stride)
+            self.c_high, self.c_low = 2048, 128
+            n = 32 + 64
+            for name, inp, planes, stride, has_skip, seps in self.xblocks:
+                n += sum(ci + co for _, ci, co, _, _ in seps) + (planes if has_skip else 0)
+            n += sum(ci + co for _, _, ci, co, _ in self.xexit)
         else:
             raise NotImplementedError("backbone %r" % (backbone,))
         self.bn_channels = n + 5 * 256 + 256 + 48 + 256 + 256 + 305
@@ -566,6 +574,154 @@ class GeneratorEngine:
         K.stem_wgrad(x, dy0, dw0)
         G["backbone.features.0.0.weight"] = dw0
 
+    # ------------------------------------------------------------------ Aligned Xception backbone
+    def _sep_forward(self, ctx, v, pre, bn_key, cout, stride, dil, training, act):
+        """SeparableConv2d + its outer BatchNorm (xception.py:26-31, 47-73) on the rectified input ``v``: depthwise 3x3 with
+        a zero border (the reference pads AFTER the activation, ``fixed_padding`` = dil on every side), its own BN pending in
+        the pointwise conv's prologue, the outer BN pending with ``act`` in the consumer's."""
+        K, N = self.K, ctx.N
+        Ho, Wo = (v.H - 1) // stride + 1, (v.W - 1) // stride + 1
+        Po, cin = N * Ho * Wo, v.C
+        yd = self._buf(v.x, Po, cin)
+        st = self._stats(ctx, cin, training)
+        K.dwconv_fwd(v, self._w(ctx, pre + ".conv1.weight", "dw"), stride, dil, 0, yd, st)
+        d = self._bn_act(ctx, pre + ".bn", yd, N, Ho, Wo, st, Po, training, ACT_NONE)
+        yp = self._buf(v.x, Po, cout)
+        st = self._stats(ctx, cout, training)
+        K.conv(d, self._w(ctx, pre + ".pointwise.weight", "ohwi"), 1, 1, yp, stats=st)
+        p = self._bn_act(ctx, bn_key, yp, N, Ho, Wo, st, Po, training, act)
+        return dict(pre=pre, v=v, d=d, p=p, stride=stride, dil=dil)
+
+    def _xception_forward(self, ctx, x, training):
+        """xception.py:179-231.  Every block output is only ever read rectified (the shared in-place ReLU of ``rep[0]``
+        rectifies the block input before the identity skip reads it, :44-49,80-90; blocks 1-2 get a rectified input, the
+        output of block 20 is rectified before conv3), so each block materialises relu(bn(rep) + skip) once (bn_add_relu)
+        and its successor reads that matrix for both its separable convs and its skip."""
+        K, S, params = self.K, ctx.S, ctx.params
+        N, _, Hin, Win = x.shape
+        H, W = (Hin - 1) // 2 + 1, (Win - 1) // 2 + 1
+        y1 = self._buf(x, N * H * W, 32)
+        st = self._stats(ctx, 32, training)
+        K.stem_fwd(x, params["backbone.conv1.weight"], y1, st)
+        a1 = self._bn_act(ctx, "backbone.bn1", y1, N, H, W, st, N * H * W, training, ACT_RELU)
+        y2 = self._buf(x, N * H * W, 64)
+        st = self._stats(ctx, 64, training)
+        K.conv(a1, self._w(ctx, "backbone.conv2.weight", "ohwi"), 3, 1, y2, stats=st)
+        a = self._bn_act(ctx, "backbone.bn2", y2, N, H, W, st, N * H * W, training, ACT_RELU)
+        S["xstem"] = dict(a1=a1, a2=a)
+        recs, low = [], None
+        for name, inp, planes, stride, has_skip, seps in self.xblocks:
+            pre = "backbone." + name
+            u = a                                   # the rectified block input (block1: bn2 + ReLU still pending)
+            seprecs, v = [], u
+            for j, (idx, ci, co, s, d) in enumerate(seps):
+                last = j == len(seps) - 1
+                r = self._sep_forward(ctx, v, "%s.rep.%d" % (pre, idx), "%s.rep.%d" % (pre, idx + 1), co, s, d, training,
+                                      ACT_NONE if last else ACT_RELU)
+                seprecs.append(r)
+                v = r["p"]
+            Ho, Wo = v.H, v.W
+            Po = N * Ho * Wo
+            us = ad = None
+            if has_skip:
+                us = u
+                if stride != 1:
+                    usb = self._buf(x, Po, inp)
+                    K.rows_stride(u.x, N, u.H, u.W, stride, usb)
+                    us = Act(usb, N, Ho, Wo, u.scale, u.shift, u.act, bn=u.bn)     # the pending transform is per channel
+                yk = self._buf(x, Po, planes)
+                st = self._stats(ctx, planes, training)
+                K.conv(us, self._w(ctx, pre + ".skip.weight", "ohwi"), 1, 1, yk, stats=st)
+                ad = self._bn_act(ctx, pre + ".skipbn", yk, N, Ho, Wo, st, Po, training, ACT_NONE)
+            zo = self._buf(x, Po, planes)
+            K.bn_add_relu(v, ad if has_skip else u, zo)
+            a = Act(zo, N, Ho, Wo)
+            recs.append(dict(pre=pre, stride=stride, u=u, us=us, ad=ad, seps=seprecs, zo=a))
+            if name == "block1":
+                low = a                             # low_level_feat = relu(block1 output) (xception.py:193-194)
+        exits = []
+        for sep, bn, ci, co, d in self.xexit:
+            r = self._sep_forward(ctx, a, "backbone." + sep, "backbone." + bn, co, 1, d, training, ACT_RELU)
+            exits.append(r)
+            a = r["p"]
+        out = self._buf(x, a.P, a.C)                # the ASPP's pooling branch reads the activated matrix
+        K.bn_apply(a, out, None)
+        S["xblocks"], S["xexit"] = recs, exits
+        return Act(out, N, a.H, a.W), low
+
+    def _sep_backward(self, ctx, G, r, dP):
+        """Reverse of ``_sep_forward``: dP is the gradient w.r.t. the activated outer-BN output.  Returns the gradient
+        w.r.t. the rectified input ``v`` (a fresh [P, Cin] matrix)."""
+        K, x, N = self.K, ctx.x, ctx.N
+        pre, v, d, p, stride, dil = r["pre"], r["v"], r["d"], r["p"], r["stride"], r["dil"]
+        dyp = self._buf(x, p.P, p.C)
+        self._bn_backward(ctx, G, p, dP, out=dyp)
+        self._wgrad(ctx, G, pre + ".pointwise.weight", d, dyp, 1, 1)
+        dUd = self._buf(x, d.P, d.C)
+        self._dgrad(ctx, pre + ".pointwise.weight", dyp, N, d.H, d.W, 1, 1, dUd)
+        del dyp
+        dyd = self._bn_backward(ctx, G, d, dUd)
+        key = pre + ".conv1.weight"
+        dwg = torch.empty_like(ctx.params[key])
+        K.dwconv_wgrad(v, dyd, stride, dil, 0, dwg)
+        G[key] = dwg
+        dV = self._buf(x, v.P, v.C)
+        if stride == 1:          # a stride-1 depthwise conv's input gradient is the depthwise conv of dy with the taps reversed
+            K.dwconv_fwd(Act(dyd, N, v.H, v.W), self._w(ctx, key, "dwflip"), 1, dil, 0, dV, None)
+        else:
+            K.dwconv_dgrad(dyd, self._w(ctx, key, "dw"), stride, dil, N, v.H, v.W, dV)
+        return dV
+
+    def _xception_backward(self, ctx, G, d_a, d_low):
+        """d_a: gradient w.r.t. the activated [P16, 2048] backbone output, d_low: w.r.t. relu(block1 output)."""
+        K, S, x = self.K, ctx.S, ctx.x
+        N = ctx.N
+        dP = d_a
+        for r in reversed(S["xexit"]):
+            dP = self._sep_backward(ctx, G, r, dP)
+        d_z = dP                                    # gradient w.r.t. relu(block20 output)
+        for r in reversed(S["xblocks"]):
+            pre, stride, u, us, ad, zo = r["pre"], r["stride"], r["u"], r["us"], r["ad"], r["zo"]
+            if pre.endswith(".block1"):
+                d_z.add_(d_low)
+            g = self._buf(x, zo.P, zo.C)            # gradient w.r.t. bn(rep) + skip
+            K.relu_gate(d_z, zo.x, g)
+            del d_z
+            seps = r["seps"]
+            dP = g
+            for j in range(len(seps) - 1, -1, -1):
+                # the last separable conv's outer BN reads g (not in place: the skip's BN backward needs it afterwards)
+                dP = self._sep_backward(ctx, G, seps[j], dP)
+            d_u = dP                                # gradient w.r.t. the rectified block input, from the separable convs
+            if ad is not None:
+                dyk = self._bn_backward(ctx, G, ad, g)
+                self._wgrad(ctx, G, pre + ".skip.weight", us, dyk, 1, 1)
+                if stride == 1:
+                    self._dgrad(ctx, pre + ".skip.weight", dyk, N, u.H, u.W, 1, 1, d_u, addend=d_u)
+                else:
+                    d_us = self._buf(x, us.P, us.C)
+                    self._dgrad(ctx, pre + ".skip.weight", dyk, N, us.H, us.W, 1, 1, d_us)
+                    full = self._buf(x, u.P, u.C)
+                    K.rows_stride(d_us, N, u.H, u.W, stride, full, scatter=True)
+                    d_u.add_(full)
+                    del d_us, full
+                del dyk
+            else:
+                d_u.add_(g)
+            del g
+            d_z = d_u
+        st = S["xstem"]
+        a1, a2 = st["a1"], st["a2"]
+        dy2 = self._bn_backward(ctx, G, a2, d_z)
+        self._wgrad(ctx, G, "backbone.conv2.weight", a1, dy2, 3, 1)
+        dU1 = self._buf(x, a1.P, a1.C)
+        self._dgrad(ctx, "backbone.conv2.weight", dy2, N, a1.H, a1.W, 3, 1, dU1)
+        del dy2
+        dy1 = self._bn_backward(ctx, G, a1, dU1)
+        dw1 = torch.empty_like(ctx.params["backbone.conv1.weight"])
+        K.stem_wgrad(x, dy1, dw1)
+        G["backbone.conv1.weight"] = dw1
+
     # ------------------------------------------------------------------ forward
     def forward(self, params: Dict[str, torch.Tensor], x: torch.Tensor, training: bool,
                 need_grad: bool, masks=None, repeat_prefix: bool = False, bn_training: Optional[bool] = None,
@@ -595,6 +751,8 @@ class GeneratorEngine:
             raise ValueError("repeat_prefix describes a training-mode (batch statistics) forward")
         if self.backbone == "mobilenet":
             a, low = self._mobilenet_forward(ctx, x, training)
+        elif self.backbone == "xception":
+            a, low = self._xception_forward(ctx, x, training)
         else:
             a, low = self._resnet_forward(ctx, x, training)
         # ---- ASPP (aspp.py:65-78): branches write channel windows of one [P, 1280] buffer
@@ -995,6 +1153,8 @@ class GeneratorEngine:
         del dUc, dyc
         if self.backbone == "mobilenet":
             self._mobilenet_backward(ctx, G, d_a, d_low)
+        elif self.backbone == "xception":
+            self._xception_backward(ctx, G, d_a, d_low)
         else:
             self._resnet_backward(ctx, G, d_a, d_low)
         self._check_arena(ctx)

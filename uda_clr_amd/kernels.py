@@ -62,6 +62,9 @@ SYMBOLS = {
     "uda_dwconv_fwd": (_I, [C.POINTER(UdaSrc), _P, _I, _I, _I, _P, _L, _P, _P]),
     "uda_dwconv_dgrad": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     "uda_dwconv_wgrad": (_I, [C.POINTER(UdaSrc), _P, _L, _I, _I, _I, _P, _P, _U, _P]),
+    "uda_dwconv_cb_fwd": (_I, [C.POINTER(UdaSrc), _P, _I, _I, _I, _P, _L, _P, _P]),
+    "uda_dwconv_cb_dgrad": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "uda_dwconv_cb_wgrad": (_I, [C.POINTER(UdaSrc), _P, _L, _I, _I, _I, _P, _P, _U, _P]),
     "uda_stem_workspace_bytes": (_U, [_L]),
     "uda_stem_fwd": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
     "uda_stem_wgrad": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _U, _P]),
@@ -152,6 +155,13 @@ def load_library(path: Optional[str] = None):
 
 class UdaError(RuntimeError):
     pass
+
+
+def _family(family: str) -> str:
+    """Depthwise kernel family of a binding call: "" (the library routes by shape) or "cb" (channel-blocked, uda_dwconv_cb_*)."""
+    if family not in ("", "cb"):
+        raise ValueError("depthwise kernel family %r" % (family,))
+    return family + "_" if family else ""
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -385,32 +395,35 @@ class HipKernels:
         self._ck(self.lib.uda_conv_wgrad(C.byref(a), self._stream()))
 
     # ------------------------------------------------------------------ depthwise
-    def dwconv_fwd(self, src: Act, w9c, stride, dil, border_mode, out, stats=None):
+    def dwconv_fwd(self, src: Act, w9c, stride, dil, border_mode, out, stats=None, family=""):
+        """``family``: "" routes by shape inside the library (uda_dwconv_*), "cb" calls the channel-blocked kernels directly
+        (uda_dwconv_cb_*: kernel tests and measurements; the engine always routes)."""
         s = self._src(src)
         Ho, Wo = (src.H - 1) // stride + 1, (src.W - 1) // stride + 1
         assert out.shape == (src.N * Ho * Wo, src.C) and w9c.is_contiguous() and tuple(w9c.shape) == (9, src.C)
         y, ldy = _mat(out, "out")
         if stats is not None:
             assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, src.C)
-        self._ck(self.lib.uda_dwconv_fwd(C.byref(s), w9c.data_ptr(), stride, dil, border_mode, y, ldy, _ptr(stats),
-                                         self._stream()))
+        self._ck(getattr(self.lib, "uda_dwconv_%sfwd" % _family(family))(C.byref(s), w9c.data_ptr(), stride, dil, border_mode, y, ldy,
+                                                                        _ptr(stats), self._stream()))
 
-    def dwconv_dgrad(self, dy, w9c, stride, dil, N, H, W, out):
+    def dwconv_dgrad(self, dy, w9c, stride, dil, N, H, W, out, family=""):
         Cc = dy.shape[1]
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         assert dy.shape[0] == N * Ho * Wo and out.shape == (N * H * W, Cc)
         g, ldg = _mat(dy, "dy")
         o, ldo = _mat(out, "out")
-        self._ck(self.lib.uda_dwconv_dgrad(g, ldg, w9c.data_ptr(), Cc, stride, dil, N, H, W, o, ldo, self._stream()))
+        self._ck(getattr(self.lib, "uda_dwconv_%sdgrad" % _family(family))(g, ldg, w9c.data_ptr(), Cc, stride, dil, N, H, W, o, ldo,
+                                                                          self._stream()))
 
-    def dwconv_wgrad(self, src: Act, dy, stride, dil, border_mode, dw):
+    def dwconv_wgrad(self, src: Act, dy, stride, dil, border_mode, dw, family=""):
         s = self._src(src)
         Ho, Wo = (src.H - 1) // stride + 1, (src.W - 1) // stride + 1
         assert dy.shape == (src.N * Ho * Wo, src.C) and dw.is_contiguous() and dw.numel() == 9 * src.C
         g, ldg = _mat(dy, "dy")
         ws = self._ws(dy, self.lib.uda_dwconv_workspace_bytes(dy.shape[0], src.C))
-        self._ck(self.lib.uda_dwconv_wgrad(C.byref(s), g, ldg, stride, dil, border_mode, dw.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), self._stream()))
+        self._ck(getattr(self.lib, "uda_dwconv_%swgrad" % _family(family))(C.byref(s), g, ldg, stride, dil, border_mode, dw.data_ptr(),
+                                                                          ws.data_ptr(), ws.numel(), self._stream()))
 
     # ------------------------------------------------------------------ stem
     def stem_fwd(self, x, w, out, stats=None):

@@ -1,4 +1,4 @@
-from . import mobilenet, resnet
+from . import mobilenet, resnet, xception
 
 
 def build_backbone(backbone, output_stride, BatchNorm):
@@ -6,4 +6,6 @@ def build_backbone(backbone, output_stride, BatchNorm):
         return mobilenet.MobileNetV2(output_stride, BatchNorm)
     if backbone == 'resnet':
         return resnet.ResNet101(output_stride, BatchNorm)
-    raise NotImplementedError("backbone %r is not built (mobilenet and resnet are)" % (backbone,))
+    if backbone == 'xception':
+        return xception.AlignedXception(output_stride, BatchNorm)
+    raise NotImplementedError("backbone %r is not built (mobilenet, resnet and xception are)" % (backbone,))
