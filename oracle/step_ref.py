@@ -98,7 +98,8 @@ class PrototypeFullStep:
                 with torch.no_grad():
                     preds[2 * stride * i:2 * stride * (i + 1)] = self.g(rep)[0]
             if self.retrify:
-                cur = proto_ref.gen_prototype_retrify(oT_before, xt_feature, preds, T, stride)[:4]
+                res = proto_ref.gen_prototype_retrify(oT_before, xt_feature, preds, T, stride)
+                cur, self.retrify_maps = res[:4], res[4:]                    # (std_map, mask_0, mask_1) for the tests
             else:
                 cur = proto_ref.gen_prototype(torch.sigmoid(oT_before), xt_feature)
             tgt = self.bank.update("tgt", cur)

@@ -335,3 +335,45 @@ def test_fused_grad_accumulation_equals_autograd_accumulation():
     m._engine_override.rng_offset = 0
     got = torch.autograd.grad(loss(), params, allow_unused=True)
     assert all(a is not None for a in got)
+
+
+@pytest.mark.parametrize("passes", [3, 4, 5])
+def test_fused_grad_accumulation_with_several_passes_equals_autograd(passes):
+    """``fused_grad_accumulation()`` around a backward that runs 3, 4 or 5 generator passes' nodes: every later node adds into the
+    tensors the FIRST node handed to autograd (one multi-tensor launch per later node), and the sums are plain autograd's, bit for
+    bit.  (A stash that the second node dropped made the third node a new "first"; autograd then folded the third node's tensors
+    into its input buffer in place and the fourth node added into the orphaned ones: its gradient was lost.)"""
+    m = _model()
+    m.train()
+    g = torch.Generator().manual_seed(4)
+    xs = [torch.randn(2, 3, 32, 32, generator=g) for _ in range(passes)]
+    masks = [deeplab_ref.draw_masks(2, 32, 32, g) for _ in range(passes)]
+    params = [p for p in m.parameters() if p.requires_grad]
+
+    def loss():
+        total = 0.0
+        for i, x in enumerate(xs):
+            m.set_dropout_masks(masks[i])
+            o = m(x)
+            total = total + (i + 1) * o[0].square().mean() + o[4].mean() + o[1].sum() * 1e-3
+        return total
+
+    loss().backward(inputs=params)
+    ref = [p.grad.clone() for p in params]
+    for p in params:
+        p.grad = None
+    calls, orig = [], torch._foreach_add_
+
+    def spy(a, b, *args, **kw):
+        calls.append(len(a))
+        return orig(a, b, *args, **kw)
+    torch._foreach_add_ = spy
+    try:
+        with m.fused_grad_accumulation():
+            loss().backward(inputs=params)
+    finally:
+        torch._foreach_add_ = orig
+    assert not m._fuse_accum and m._accum_stash is None
+    bad = [i for i, (p, r) in enumerate(zip(params, ref)) if not torch.equal(p.grad, r)]
+    assert not bad, "%d of %d gradients differ from autograd's sums (first: %s)" % (len(bad), len(params), bad[:3])
+    assert calls.count(len(params)) == passes - 1, calls          # (the engine's own backward adds shorter lists)

@@ -52,20 +52,23 @@ class _GeneratorFn(torch.autograd.Function):
             # inside fused_grad_accumulation(): autograd would sum the gradients the generator passes of ONE backward run send to the
             # same parameter in its input buffers, one add launch per parameter (~190).  Instead the first node of a run remembers
             # the tensors it hands over and every later node adds its gradients INTO them with one multi-tensor launch and hands
-            # over None (an absent contribution).  The references are dropped right away so that AccumulateGrad still holds the last
-            # one and keeps the tensor instead of cloning it; an engine callback clears them at the end of the run in any case.
+            # over None (an absent contribution), for any number of nodes: the stash lives until an engine callback clears it at the
+            # end of the run.  Since the later nodes contribute None, autograd's input buffer keeps holding exactly the tensors of
+            # the stash.  The stash keeps detached aliases, not the handed-over tensors themselves, so that AccumulateGrad still holds
+            # the only reference and keeps the tensor instead of cloning it.
             module = ctx.module
             stash = module._accum_stash
             if stash is None:
-                module._accum_stash = {k: g for k, g in zip(ctx.keys, out) if g is not None}
+                stash = module._accum_stash = {}
                 torch.autograd.Variable._execution_engine.queue_callback(lambda: setattr(module, "_accum_stash", None))
-            else:
-                idx = [i for i, k in enumerate(ctx.keys) if out[i] is not None and k in stash]
-                if idx:
-                    torch._foreach_add_([stash[ctx.keys[i]] for i in idx], [out[i] for i in idx])
-                    for i in idx:
-                        out[i] = None
-                module._accum_stash = None
+            idx = [i for i, k in enumerate(ctx.keys) if out[i] is not None and k in stash]
+            if idx:
+                torch._foreach_add_([stash[ctx.keys[i]] for i in idx], [out[i] for i in idx])
+                for i in idx:
+                    out[i] = None
+            for k, g in zip(ctx.keys, out):
+                if g is not None:          # first contribution of the run to this parameter: handed over, later ones add into it
+                    stash[k] = g.detach()
         return (None, None, None, None) + tuple(out)
 
 
@@ -158,8 +161,9 @@ class DeepLab(Holder):
 
     def fused_grad_accumulation(self):
         """Context manager around a ``backward()`` that runs SEVERAL generator passes' backward nodes (source + target of one
-        step): the later node adds its parameter gradients into the tensors the first one handed to autograd, with one multi-tensor
-        launch, and hands over ``None`` (same sums as autograd's per-parameter input-buffer adds, bit for bit).  Only around
+        step, or any number of passes): every later node adds its parameter gradients into the tensors the first one handed to
+        autograd, with one multi-tensor launch, and hands over ``None`` (same sums as autograd's per-parameter input-buffer adds, bit
+        for bit).  Only around
         ``backward()`` / ``autograd.grad`` calls that want the SUM over the passes; ``Trainer_prototype_full`` holds it around
         ``loss_all.backward``."""
         import contextlib
