@@ -179,6 +179,26 @@ int uda_bn_add_relu(const uda_src_t* a, const uda_src_t* b, float* out, int64_t 
 int uda_relu_gate(const float* dz, int64_t lddz, const float* z, int64_t ldz, int64_t P, int C, float* out,
                   int64_t ldo, void* stream);
 
+/* ---- DRN-D-54 head (networks/backbone/drn.py): the layers no other backbone has
+ * layer0: conv 7x7 stride 1 pad 3, 3 -> 16, NCHW image in, NHWC out (drn.py:124-129, 214).  w_hwio: the weight as
+ * [7][7][3][16] (taps, input channel, output channels fastest; 16-byte aligned).  The weight gradient comes out OIHW. */
+uint64_t uda_stem7s1_workspace_bytes(int64_t P);
+int uda_stem7s1_fwd(const float* x, int N, int H, int W, const float* w_hwio, float* y, int64_t ldy,
+                    double* stats /* [SLOTS][2][16] or NULL */, void* stream);
+int uda_stem7s1_wgrad(const float* x, int N, int H, int W, const float* dy, int64_t lddy, float* dw,
+                      float* workspace, uint64_t workspace_bytes, void* stream);
+/* narrow dense 3x3 convolution, pad 1, dilation 1: C and Cout each 16, 32 or 64, stride 1 or 2 (anything else is an error) -
+ * layer1 16 -> 16, layer2 16 -> 32 stride 2 (drn.py:131-134, 196-206, 216-217), layer3.0.conv2 64 -> 64 stride 2 (drn.py:69-71, 86).
+ *   y[(n,oh,ow), co] = sum_{kh,kw,ci} u(n, s*oh + kh - 1, s*ow + kw - 1, ci) * w_hwio[kh][kw][ci][co]
+ * u = the pending transform of src (no dropout mask), 0 outside the image; y and stats live on the grid
+ * ((H-1)/s+1) x ((W-1)/s+1).  With w_hwio[kh][kw][co][ci] = w[co][ci][2-kh][2-kw] the stride-1 form is the input gradient.
+ * uda_conv3n_wgrad: dw[co][ci][kh][kw] (OIHW) = sum_p dy[p,co] * u(...), dy on the strided grid. */
+int uda_conv3n_fwd(const uda_src_t* src, const float* w_hwio, int Cout, int stride, float* y, int64_t ldy,
+                   double* stats /* [SLOTS][2][Cout] or NULL */, void* stream);
+uint64_t uda_conv3n_workspace_bytes(int Cin, int Cout);
+int uda_conv3n_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int Cout, int stride, float* dw,
+                     float* workspace, uint64_t workspace_bytes, void* stream);
+
 /* ---- patch discriminators (networks/GAN.py:86-148): Conv2d(4, stride 2, pad 2) = ksize-2
  * uda_conv_fwd on the space-to-depth image z[n,i,j,(a,b,c)] = x[n, 2i+a-2, 2j+b-2, c] (zero outside the valid
  * region valid_h x valid_w of the [N,Hs,Ws,C] source grid; Hz = (valid_h+5)/2).  uda_s2d_fwd also applies the

@@ -1,0 +1,246 @@
+"""DeepLab(backbone='drn') without a GPU: the parameter tree against the reference's manifest, the pretrained-weights loader,
+and the engine's DRN orchestration (driven with the tests' torch statement of the kernels, tests/kernel_spec.py +
+tests/drn_spec.py) against the functional oracle of tests/drn_ref.py and against the fixtures the reference itself wrote
+(tests/golden/make_golden_drn.py)."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import drn_ref
+import model_cases
+from drn_spec import DrnSpecKernels
+from oracle import deeplab_ref, step_ref
+from uda_clr_amd.engine import GeneratorEngine
+from uda_clr_amd.networks.deeplabv3 import DeepLab
+
+GOLDEN = model_cases.GOLDEN
+NAMES = model_cases.NAMES
+
+
+def _engine():
+    return GeneratorEngine(DrnSpecKernels(), 8, backbone="drn")
+
+
+def _model(perturb=True):
+    m = model_cases.seeded_model(perturb=perturb, backbone="drn", output_stride=8)
+    m._engine_override = _engine()
+    return m
+
+
+def test_manifest_matches_reference():
+    """405 state-dict keys in the reference's order, their shapes, and the seeded-initialisation sums (drn.py:159-169 after the
+    constructors' own draws), then the ASPP / decoder as for the other backbones."""
+    with open(os.path.join(GOLDEN, "manifest_drn.json")) as f:
+        man = json.load(f)
+    torch.manual_seed(1337)
+    m = DeepLab(num_classes=2, backbone="drn", output_stride=16, method="prototype_full")
+    sd = m.state_dict()
+    assert man["n_state_keys"] == len(sd) == 405
+    assert [e["key"] for e in man["entries"]] == list(sd.keys())
+    for e in man["entries"]:
+        v = sd[e["key"]]
+        assert list(v.shape) == e["shape"], e["key"]
+        assert abs(float(v.double().sum()) - e["sum"]) <= 1e-9 * max(1.0, abs(e["sum"])), e["key"]
+    params = list(m.parameters())
+    assert len(params) == man["n_param_tensors"] == 204
+    assert sum(p.numel() for p in params) == man["n_params"] == 40733143
+    n1 = sum(p.numel() for p in m.get_1x_lr_params())
+    n10 = sum(p.numel() for p in m.get_10x_lr_params())
+    assert n1 == sum(p.numel() for p in m.backbone.parameters()) == 35296176
+    assert n1 + n10 == man["n_params"]
+
+
+def test_output_stride_is_forced_to_8():
+    """deeplabv3.py:14-15: whatever output_stride is passed, the DRN model is the output-stride-8 one (ASPP rates 12 / 24 / 36)."""
+    m = DeepLab(num_classes=2, backbone="drn", output_stride=16, method="prototype_full")
+    assert m.output_stride == 8
+    assert m.aspp.aspp2.atrous_conv.dilation == (12, 12) and m.aspp.aspp1.atrous_conv.in_channels == 512
+    assert m.decoder.conv1.in_channels == 256
+    m._engine_override = _engine()
+    m.eval()
+    with torch.no_grad():
+        out = m(torch.randn(1, 3, 64, 64, generator=torch.Generator().manual_seed(0)))
+    assert tuple(out[2].shape) == (1, 256, 8, 8) and tuple(out[3].shape) == (1, 304, 16, 16)
+
+
+def test_pretrained_loader(monkeypatch, tmp_path):
+    """Nothing is ever fetched.  Without UDA_CLR_DRN_D_54_PTH pretrained=True leaves the seeded initialisation; with it the
+    weights are those of the file, loaded the reference's way (fc.weight / fc.bias dropped, then a strict load, drn.py:380-383)."""
+    import torch.utils.model_zoo as model_zoo
+    import urllib.request
+
+    def refuse(*a, **k):
+        raise AssertionError("pretrained=True must not fetch")
+    monkeypatch.setattr(model_zoo, "load_url", refuse)
+    monkeypatch.setattr(urllib.request, "urlopen", refuse)
+    monkeypatch.delenv("UDA_CLR_DRN_D_54_PTH", raising=False)
+    from uda_clr_amd.networks.backbone.drn import drn_d_54
+    torch.manual_seed(0)
+    a = drn_d_54(torch.nn.BatchNorm2d, pretrained=True)
+    torch.manual_seed(0)
+    b = drn_d_54(torch.nn.BatchNorm2d, pretrained=False)
+    for (ka, va), (kb, vb) in zip(a.state_dict().items(), b.state_dict().items()):
+        assert ka == kb and torch.equal(va, vb), ka
+    g = torch.Generator().manual_seed(9)
+    saved = {k: (torch.randn(v.shape, generator=g) if v.is_floating_point() else v + 3) for k, v in a.state_dict().items()}
+    saved["fc.weight"], saved["fc.bias"] = torch.randn(1000, 512, 1, 1, generator=g), torch.randn(1000, generator=g)
+    path = str(tmp_path / "drn_d_54.pth")
+    torch.save(saved, path)
+    monkeypatch.setenv("UDA_CLR_DRN_D_54_PTH", path)
+    c = drn_d_54(torch.nn.BatchNorm2d, pretrained=True)
+    for k, v in c.state_dict().items():
+        assert torch.equal(v, saved[k]), k
+    torch.manual_seed(0)
+    d = drn_d_54(torch.nn.BatchNorm2d, pretrained=False)           # pretrained=False ignores the variable
+    assert torch.equal(d.state_dict()["layer0.0.weight"], b.state_dict()["layer0.0.weight"])
+    del saved["layer8.0.weight"]                                   # the load is strict, as the reference's
+    torch.save(saved, path)
+    with pytest.raises(RuntimeError, match="layer8.0.weight"):
+        drn_d_54(torch.nn.BatchNorm2d, pretrained=True)
+
+
+def test_transnorm_raises():
+    with pytest.raises(NotImplementedError, match="TransNorm"):
+        DeepLab(num_classes=2, backbone="drn", sync_bn=False)
+
+
+@pytest.mark.parametrize("size", [64, 96])
+def test_eval_forward_matches_oracle(size):
+    m = _model().eval()
+    x = torch.randn(2, 3, size, size, generator=torch.Generator().manual_seed(0))
+    with torch.no_grad():
+        mine = m(x)
+        ref = drn_ref.deeplab_forward(deeplab_ref.canonical_state(m.state_dict()), x, training=False)
+    for n, a, b in zip(NAMES, mine, ref):
+        assert a.shape == b.shape, n
+        assert model_cases.rel(a, b) < 2e-4, (n, model_cases.rel(a, b))
+
+
+@pytest.mark.parametrize("narrow", ["", "0", "1"], ids=["routed", "implicit-gemm", "narrow"])
+def test_train_forward_backward_matches_oracle(narrow, monkeypatch):
+    """Training forward + backward at 64^2 (injected dropout masks) against the fp64 oracle, with the bounds of the other
+    backbones' CPU cases: outputs within 3x the fp32 oracle's own fp64 distance, gradients by model_cases.grads_ok with no
+    parameter left out (every DRN BatchNorm is followed by a ReLU or by the residual add + ReLU: no gradient is analytically
+    zero).  Runs on the routes the engine picks, with every head conv on the implicit-GEMM route (stride 2 = stride 1 +
+    subsampling / zero stuffing) and with every head conv on the narrow kernels."""
+    from uda_clr_amd import engine
+    monkeypatch.setattr(engine, "_DRN_NARROW_ENV", narrow)
+    with drn_ref.as_deeplab_oracle():
+        fwd, grads, stats, fwd64 = model_cases.train_parity(torch.device("cpu"), backbone="drn", output_stride=8, engine=_engine())
+    for n, (mine, floor) in fwd64.items():
+        assert mine < 3.0 * floor + 2e-4, (n, mine, floor)
+    assert len(grads) == 204
+    assert all(v[0] < float("inf") for v in grads.values()), [k for k, v in grads.items() if v[0] == float("inf")]
+    bad, gmean = model_cases.grads_ok(grads)
+    assert not bad, list(bad.items())[:10]
+    assert gmean < 1.5, gmean
+    assert stats < 1e-3, stats
+
+
+def test_frozen_batchnorm_training_matches_oracle():
+    """freeze_bn() while training: eval-mode BatchNorm (running statistics, no batch terms in the backward), live dropout."""
+    with drn_ref.as_deeplab_oracle():
+        fwd, grads, stats, _ = model_cases.train_parity(torch.device("cpu"), backbone="drn", output_stride=8, frozen_bn=True,
+                                                        engine=_engine(), seed=11)
+    assert stats == 0.0
+    model_cases.frozen_grads_ok(grads)
+
+
+def test_mc_fast_path_equals_plain_stochastic_forwards():
+    """GeneratorEngine.mc_forward (the DRN backbone's activations reused) vs plain stochastic forwards on identical masks."""
+    B, S, passes = 2, 64, 2
+    gen = torch.Generator().manual_seed(8)
+    x = torch.randn(B, 3, S, S, generator=gen)
+
+    def masks(n):
+        mk = deeplab_ref.draw_masks(n, S, S, gen)
+        mk["aspp.dropout"] = (torch.rand(n, 256, S // 8, S // 8, generator=gen) >= 0.5).to(torch.uint8)
+        return mk
+    m0 = masks(B)
+    mc_masks = [masks(2 * B) for _ in range(passes)]
+    res = []
+    for fast in (False, True):
+        m = _model().train()
+        m.set_dropout_masks(m0)
+        m(x)
+        if not fast:
+            m._recent = []
+        preds = m.mc_dropout_logits(x, passes=passes, reps=2, masks=mc_masks)
+        res.append((preds, {k: v.clone() for k, v in m.state_dict().items()}))
+    (p0, s0), (p1, s1) = res
+    assert model_cases.rel(p1, p0) < 1e-4
+    for k in s0:
+        if k.endswith("num_batches_tracked"):
+            assert int(s0[k]) == int(s1[k]) == 1 + passes
+        elif k.endswith("running_mean") or k.endswith("running_var"):
+            assert model_cases.rel(s1[k], s0[k]) < 1e-4, k
+
+
+def golden_errors(dev, tag, engine=None):
+    """The DRN model (``engine``: CPU tests' kernel statement) against forward_<tag>.npz, as model_cases.golden_parity does for
+    the other backbones."""
+    z = np.load(os.path.join(GOLDEN, "forward_%s.npz" % tag))
+    B, S = int(z["B"]), int(z["S"])
+    assert int(z["output_stride"]) == 8
+    m = model_cases.seeded_model(backbone="drn", output_stride=8)
+    if engine is not None:
+        m._engine_override = engine
+    torch.manual_seed(int(z["input_seed"]))
+    x = torch.randn(B, 3, S, S)
+    errs = {}
+    m.to(dev).eval()
+    with torch.no_grad():
+        out = m(x.to(dev))
+    for n, t in zip(NAMES, out):
+        f = t.double().cpu().reshape(-1)
+        idx = torch.linspace(0, f.numel() - 1, 97).long()
+        ref = torch.from_numpy(z["eval.%s.smp" % n])
+        errs["eval." + n + ".smp"] = (f[idx] - ref).abs().max().item() / max(ref.abs().max().item(), 1e-30)
+        errs["eval." + n + ".abs"] = abs(f.abs().sum().item() - float(z["eval.%s.abs" % n])) / float(z["eval.%s.abs" % n])
+    from make_golden_inputs import synth_targets
+    tmap, tbd = synth_targets(B, S, S, int(z["target_seed"]))
+    m.train()
+    sd0 = deeplab_ref.canonical_state({k: v.cpu() for k, v in m.state_dict().items()})
+    rec = {}
+    torch.manual_seed(int(z["dropout_seed"]))
+    with torch.no_grad():
+        drn_ref.deeplab_forward(sd0, x, training=True, record=rec)
+    for k, v in rec.items():
+        assert int(v.sum()) == int(z["mask.%s.sum" % k]), "dropout stream differs from the reference's draw"
+    m.set_dropout_masks(rec)
+    out = m(x.to(dev))
+    assert all(bool(torch.isfinite(t).all()) for t in out)
+    loss = step_ref.seg_loss(out[0], out[1], tmap.to(dev), tbd.to(dev))
+    loss.backward()
+    errs["train.loss"] = abs(loss.item() - float(z["train.loss"])) / abs(float(z["train.loss"]))
+    for n, t in zip(NAMES, out):
+        d = t.detach().double().cpu()
+        errs["train." + n + ".abs"] = abs(d.abs().sum().item() - float(z["train.%s.abs" % n])) / float(z["train.%s.abs" % n])
+    live = m._flat_state()
+    keys = [str(k) for k in z["train.grad_keys"]]
+    assert len(keys) == 204
+    gn = np.array([live[k].grad.double().norm().item() for k in keys])
+    rel_gn = np.abs(gn - z["train.grad_norm"]) / np.maximum(z["train.grad_norm"], 1e-12)
+    conv = np.array([live[k].dim() == 4 for k in keys])
+    errs["train.grad_norm.conv"] = float(rel_gn[conv].max())
+    errs["train.grad_norm.median"] = float(np.median(rel_gn))
+    bs = np.array([live[k].double().sum().item() for k in z["train.bn_keys"]])
+    errs["train.bn_sum"] = float(np.max(np.abs(bs - z["train.bn_sum"]) / np.maximum(np.abs(z["train.bn_sum"]), 1e-2)))
+    return errs
+
+
+GOLDEN_BOUNDS = {"train.grad_norm.conv": 5e-2, "train.grad_norm.median": 2e-2, "train.bn_sum": 5e-3}      # test_xception_cpu.py's
+
+
+def check_golden(errs):
+    for k, v in errs.items():
+        bound = GOLDEN_BOUNDS.get(k, 1e-3 if k.startswith(("eval.", "train.loss")) else 5e-3)
+        assert v < bound, (k, v, bound)
+
+
+@pytest.mark.parametrize("tag", ["drn_128", "drn_256"])
+def test_engine_matches_reference_fixture(tag):
+    check_golden(golden_errors(torch.device("cpu"), tag, _engine()))

@@ -1,0 +1,156 @@
+"""-m gpu: the DRN head kernels (uda_clr_amd/csrc/drn_head.hip) against fp64 torch on small odd shapes: the 7x7 stride-1 stem
+(3 -> 16, NCHW in) and the narrow dense 3x3 family (16 / 32 / 64 channels on either side, stride 1 | 2) at the channel pairs
+the model uses and at the family's extremes.  Inputs and outputs are [P, C] views with ld > C whose padding columns hold
+NaN / Inf (kernel_cases.padded): nothing may leak.  The kernels are fp32 VALU code: UDA_CLR_MFMA does not reach them, so there
+is one matrix mode to test."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from kernel_cases import act_to, gen, hip, make_src, padded, to_dev
+from uda_clr_amd.acts import ACT_NONE, ACT_RELU, Act
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+# fp32 sums of at most 9 * 64 products (y, dx) and of N * Ho * Wo <= 3,000 products (dw, statistics; fp32 within a workgroup's
+# tile, fp64 across tiles): the bound test_xception_kernels_gpu.py uses for sums of this length
+BOUND = 2e-5
+
+
+def _rel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    if not torch.isfinite(a).all():
+        return float("inf")
+    return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-30)
+
+
+def _nchw(rows, N, H, W):
+    return rows.reshape(N, H, W, -1).permute(0, 3, 1, 2)
+
+
+def _rows(t):
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+
+
+# (N, H, W): one tile, several 16 x 64 tiles with ragged edges, three images
+STEM_SHAPES = [(1, 9, 13), (1, 19, 71), (3, 21, 37), (1, 33, 80)]
+
+
+@pytest.mark.parametrize("N,H,W", STEM_SHAPES, ids=["n%d_%dx%d" % s for s in STEM_SHAPES])
+def test_stem7s1_matches_fp64(N, H, W):
+    assert N * H * W <= 3000
+    g = gen(40 + H)
+    x = torch.randn(N, 3, H, W, generator=g)
+    w = torch.randn(16, 3, 7, 7, generator=g) / 7.0
+    P = N * H * W
+    y = F.conv2d(x.double(), w.double(), None, 1, 3)
+    dy = padded(P, 16, g)
+    dwr = torch.nn.grad.conv2d_weight(x.double(), w.shape, _nchw(dy.double(), N, H, W), 1, 3)
+    yr = _rows(y)
+
+    K = hip()
+    yh = to_dev(padded(P, 16, g), DEV)
+    st = torch.zeros(16, 2, 16, dtype=torch.float64, device=DEV)
+    K.stem7s1_fwd(x.to(DEV), K.relayout_hwio(w.to(DEV)), yh, st)
+    yh2 = to_dev(padded(P, 16, g), DEV)
+    K.stem7s1_fwd(x.to(DEV), K.relayout_hwio(w.to(DEV)), yh2, None)           # without the statistics epilogue
+    dwh = torch.empty(16, 3, 7, 7, device=DEV)
+    K.stem7s1_wgrad(x.to(DEV), to_dev(dy, DEV), dwh)
+    torch.cuda.synchronize()
+    errs = {"y": _rel(yh, yr), "y_nostats": _rel(yh2, yr), "sum": _rel(st.sum(0)[0], yr.sum(0)),
+            "sumsq": _rel(st.sum(0)[1], (yr * yr).sum(0)), "dw": _rel(dwh, dwr)}
+    print(errs)
+    assert max(errs.values()) < BOUND, errs
+
+
+# (N, H, W, Cin, Cout, stride, BN + ReLU prologue): the model's pairs (16 -> 16; 16 -> 32 stride 2; 64 -> 64 stride 2, and
+# 32 -> 16 / 64 -> 64 at stride 1, the input-gradient forms), then the family's extremes; stride 2 on odd and even extents
+CONV_SHAPES = [(1, 13, 37, 16, 16, 1, True), (3, 9, 35, 16, 16, 1, False),
+               (1, 21, 67, 16, 32, 2, True), (3, 18, 40, 16, 32, 2, False), (1, 8, 6, 16, 32, 2, True),
+               (1, 19, 69, 64, 64, 2, True), (3, 12, 34, 64, 64, 2, False),
+               (1, 11, 35, 32, 16, 1, False), (1, 10, 33, 64, 64, 1, True),
+               (1, 9, 34, 16, 64, 1, True), (3, 7, 11, 64, 16, 2, True), (1, 17, 36, 64, 16, 1, False),
+               (1, 15, 33, 32, 32, 2, True), (1, 14, 66, 16, 64, 2, False), (3, 5, 9, 32, 64, 1, True)]
+
+
+@pytest.mark.parametrize("N,H,W,Cin,Cout,stride,lazy", CONV_SHAPES,
+                         ids=["n%d_%dx%d_%dto%d_s%d_%s" % (s[:6] + ("bn" if s[6] else "raw",)) for s in CONV_SHAPES])
+def test_conv3n_matches_fp64(N, H, W, Cin, Cout, stride, lazy):
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    Po = N * Ho * Wo
+    assert Po <= 3000
+    g = gen(300 + Cin + 3 * Cout + stride + H)
+    src = make_src(N, H, W, Cin, g, lazy, ACT_RELU)
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) / (3.0 * Cin ** 0.5)
+    # fp64 statement: zero border AFTER the producer's BN + ReLU
+    u = src.x.double()
+    if lazy:
+        u = torch.relu(u * src.scale.double() + src.shift.double())
+    u = _nchw(u, N, H, W)
+    wd = w.double()
+    y = F.conv2d(u, wd, None, stride, 1)
+    dy = padded(Po, Cout, g)
+    gy = _nchw(dy.double(), N, Ho, Wo)
+    dx = torch.nn.grad.conv2d_input((N, Cin, H, W), wd, gy, stride, 1)
+    dwr = torch.nn.grad.conv2d_weight(u, wd.shape, gy, stride, 1)
+    yr = _rows(y)
+
+    K = hip()
+    sh = act_to(src, DEV)
+    yh = to_dev(padded(Po, Cout, g), DEV)
+    st = torch.zeros(16, 2, Cout, dtype=torch.float64, device=DEV)
+    K.conv3n_fwd(sh, K.relayout_hwio(w.to(DEV)), stride, yh, st)
+    dwh = torch.empty(Cout, Cin, 3, 3, device=DEV)
+    K.conv3n_wgrad(sh, to_dev(dy, DEV), stride, dwh)
+    # input gradient the way the engine forms it: the stride-1 kernel on the (zero-stuffed) gradient with flipped, transposed weights
+    dyf = to_dev(dy, DEV)
+    if stride != 1:
+        dyf = to_dev(padded(N * H * W, Cout, g), DEV)
+        K.rows_stride(to_dev(dy, DEV), N, H, W, stride, dyf, scatter=True)
+    dxh = to_dev(padded(N * H * W, Cin, g), DEV)
+    K.conv3n_fwd(Act(dyf, N, H, W), K.relayout_hwio(w.to(DEV), True), 1, dxh, None)
+    torch.cuda.synchronize()
+    errs = {"y": _rel(yh, yr), "sum": _rel(st.sum(0)[0], yr.sum(0)), "sumsq": _rel(st.sum(0)[1], (yr * yr).sum(0)),
+            "dx": _rel(dxh, _rows(dx)), "dw": _rel(dwh, dwr)}
+    print(errs)
+    assert max(errs.values()) < BOUND, errs
+
+
+def test_statistics_are_added_into():
+    """the statistics epilogue ADDS into its fp64 accumulator (several launches of one BatchNorm share it)"""
+    N, H, W = 1, 9, 40
+    g = gen(5)
+    src = act_to(make_src(N, H, W, 16, g, True, ACT_RELU), DEV)
+    K = hip()
+    w = K.relayout_hwio(torch.randn(16, 16, 3, 3, generator=g).to(DEV))
+    y = to_dev(padded(N * H * W, 16, g), DEV)
+    st = torch.zeros(16, 2, 16, dtype=torch.float64, device=DEV)
+    K.conv3n_fwd(src, w, 1, y, st)
+    once = st.sum(0).clone()
+    K.conv3n_fwd(src, w, 1, y, st)
+    torch.cuda.synchronize()
+    assert _rel(st.sum(0), 2 * once) < 1e-12
+
+
+def test_entries_reject_what_no_kernel_serves():
+    """a width outside 16 / 32 / 64, a dropout mask on the operand: an error naming the limit, not a launch"""
+    K = hip()
+    g = gen(3)
+    src = act_to(make_src(1, 4, 4, 24, g, False, ACT_NONE), DEV)
+    out = to_dev(padded(16, 16, g), DEV)
+    with pytest.raises(RuntimeError, match="16, 32 or 64"):
+        K.conv3n_fwd(src, torch.zeros(3, 3, 24, 16, device=DEV), 1, out)
+    src = act_to(make_src(1, 4, 4, 16, g, False, ACT_NONE), DEV)
+    out = to_dev(padded(16, 128, g), DEV)
+    with pytest.raises(RuntimeError, match="16, 32 or 64"):
+        K.conv3n_fwd(src, torch.zeros(3, 3, 16, 128, device=DEV), 1, out)
+    with pytest.raises(RuntimeError, match="16, 32 or 64"):
+        K.conv3n_wgrad(src, to_dev(padded(16, 128, g), DEV), 1, torch.empty(128, 16, 3, 3, device=DEV))
+    masked = act_to(make_src(1, 4, 4, 16, g, True, ACT_RELU, mask=True), DEV)
+    with pytest.raises(RuntimeError, match="mask"):
+        K.conv3n_fwd(masked, torch.zeros(3, 3, 16, 16, device=DEV), 1, to_dev(padded(16, 16, g), DEV))
+    # the implicit-GEMM entry keeps refusing a narrow stride-2 conv (the engine routes those to the narrow family)
+    w = K.relayout_ohwi(torch.zeros(32, 16, 3, 3, device=DEV))
+    with pytest.raises(RuntimeError, match="stride 2"):
+        K.conv(src, w, 3, 1, to_dev(padded(4, 32, g), DEV), stride=2)

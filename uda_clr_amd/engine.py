@@ -1,4 +1,4 @@
-"""Execution plan of the DeepLabV3+ generator (MobileNetV2, ResNet-101 or Aligned Xception backbone) on the HIP kernels.
+"""Execution plan of the DeepLabV3+ generator (MobileNetV2, ResNet-101, Aligned Xception or DRN-D-54 backbone) on the HIP kernels.
 
 The whole generator is ONE autograd node (``networks.deeplabv3._GeneratorFn``): this module runs
 its forward as a fixed sequence of kernel launches on NHWC buffers and its backward as the
@@ -12,6 +12,7 @@ Reference behaviour reproduced (file:line in /root/reference):
                                          (H+2d)(W+2d) positions and the depthwise conv sees
                                          relu6(shift) on its border
   networks/backbone/resnet.py:23-43,113-124   Bottleneck / ResNet.forward (BASELINE.json configs[4])
+  networks/backbone/drn.py:61-99,123-155,208-234   Bottleneck / DRN-D layers / DRN.forward
   networks/aspp.py:65-78, networks/decoder.py:45-56
 
 Fusion scheme ("kernels"): every conv writes its raw output once and accumulates the
@@ -31,6 +32,18 @@ import os as _os
 
 _MC_VIRTUAL = _os.environ.get("UDA_CLR_MC_VIRTUAL", "1") != "0"      # A/B switch: stochastic passes without the x_feature matrix
 _NATIVE_S2 = _os.environ.get("UDA_CLR_NATIVE_STRIDE2", "1") != "0"    # A/B switch: ResNet's stride-2 3x3 convs on the strided grid (0: stride 1 + subsample)
+# Which narrow 3x3 convolutions of DRN (16 / 32 / 64 channels: layer1, layer2 and layer3's conv2, drn.py:131-136) run on the
+# direct kernels (uda_conv3n_*) instead of the implicit-GEMM route: (pass, Cin, Cout, stride of the LAYER) -> bool, as measured in
+# profiles/drn_head_kernels.md at B = 8 and 16.  "dgrad" runs as the stride-1 conv Cout -> Cin of the (zero-stuffed) gradient.
+# New / old time: head and layer3.0.conv2 0.20 - 0.57 (its input gradient 0.85 - 0.88); the stride-1 64 -> 64 convs of
+# layer3.1 / layer3.2 at 1/4 resolution: weight gradient 0.70 - 0.72, forward 1.70 / 1.00 and input gradient 1.58 / 0.95 at
+# B = 8 / 16 (512 tiles for 256 CUs), so those two stay where they were.  Shapes not listed stay on the implicit-GEMM route.
+# A/B switch UDA_CLR_DRN_NARROW: 1 = all listed shapes, 0 = none (stride 2 then runs at stride 1 + subsampling / zero
+# stuffing, four times the work).
+_DRN_NARROW_ENV = _os.environ.get("UDA_CLR_DRN_NARROW", "")
+_DRN_NARROW = {("fwd", 16, 16, 1): True, ("fwd", 16, 32, 2): True, ("fwd", 64, 64, 2): True, ("fwd", 64, 64, 1): False,
+               ("wgrad", 16, 16, 1): True, ("wgrad", 16, 32, 2): True, ("wgrad", 64, 64, 2): True, ("wgrad", 64, 64, 1): True,
+               ("dgrad", 16, 16, 1): True, ("dgrad", 16, 32, 2): True, ("dgrad", 64, 64, 2): True, ("dgrad", 64, 64, 1): False}
 POISON_BUFFERS = False      # tests/test_generator_gpu.py sets it: every fp32 work matrix starts as NaN / Inf / huge values
 
 from .acts import ACT_NONE, ACT_RELU, ACT_RELU6, Act, BNRec, nchw_view, round4
@@ -167,6 +180,17 @@ class GeneratorEngine:
             for name, inp, planes, stride, has_skip, seps in self.xblocks:
                 n += sum(ci + co for _, ci, co, _, _ in seps) + (planes if has_skip else 0)
             n += sum(ci + co for _, _, ci, co, _ in self.xexit)
+        elif backbone == "drn":
+            from .networks.backbone.drn import drn_plan
+            if output_stride != 8:
+                raise ValueError("the DRN backbone's output sits at 1/8 of the input (deeplabv3.py:14-15): output_stride must be 8")
+            self.dhead, blocks, self.dtail = drn_plan()
+            self.rblocks = [("backbone." + pre,) + tuple(rest) for pre, *rest in blocks]
+            self.dlow = [pre for pre, *_ in self.rblocks if pre.startswith("backbone.layer3.")][-1]
+            self.c_high, self.c_low = 512, 256
+            n = sum(row[3] for row in self.dhead + self.dtail)
+            for pre, inp, planes, stride, dil, has_ds in self.rblocks:
+                n += 2 * planes + 4 * planes * (2 if has_ds else 1)
         else:
             raise NotImplementedError("backbone %r" % (backbone,))
         self.bn_channels = n + 5 * 256 + 256 + 48 + 256 + 256 + 305
@@ -215,6 +239,7 @@ class GeneratorEngine:
                 return t[:, :CF].permute(2, 3, 0, 1).reshape(9 * t.shape[0], CF, 1, 1).contiguous()
             ctx.w_cache[ck] = {"ohwi": K.relayout_ohwi, "dgrad": K.relayout_dgrad,
                                "dw": K.relayout_dw,
+                               "hwio": lambda t: K.relayout_hwio(t), "hwio_dgrad": lambda t: K.relayout_hwio(t, True),
                                "dwflip": lambda t: K.relayout_dw(t).flip(0).contiguous(),
                                # decoder conv0 split into its upsampled-feature part (tap GEMMs at low resolution) and its low-level part
                                "up_taps": lambda t: K.relayout_ohwi(taps(t)),
@@ -416,6 +441,67 @@ class GeneratorEngine:
         K.maxpool_fwd(a0, z, idx)
         S["stem"] = dict(a0=a0, idx=idx)
         a = Act(z, N, Hp, Wp)
+        a, low = self._bottlenecks_forward(ctx, x, a, training, "backbone.layer1.2")
+        return a, low
+
+    # ------------------------------------------------------------------ 3x3 convolutions at stride 1 | 2, any width
+    def _narrow(self, what, cin, cout, stride, dil=1):
+        """True when this pass of a 3x3 convolution layer (cin -> cout at ``stride``) of DRN runs on the narrow direct kernels."""
+        if self.backbone != "drn" or dil != 1 or (what, cin, cout, stride) not in _DRN_NARROW:
+            return False
+        return _DRN_NARROW[(what, cin, cout, stride)] if _DRN_NARROW_ENV == "" else _DRN_NARROW_ENV != "0"
+
+    @staticmethod
+    def _wide_s2(cin, cout):
+        """the implicit-GEMM kernels walk a strided output grid on their wide tiles only (uda_conv_fwd: Cout > 96, K > 192)"""
+        return _NATIVE_S2 and cout > 96 and 9 * cin > 192
+
+    def _conv3x3(self, ctx, src, key, dil, stride, out, st, training):
+        """3x3 conv (pad = dil) of ``src`` at stride 1 | 2 into ``out`` with the statistics epilogue."""
+        K, N, H, W = self.K, src.N, src.H, src.W
+        cin, cout = src.C, out.shape[1]
+        if self._narrow("fwd", cin, cout, stride, dil):
+            K.conv3n_fwd(src, self._w(ctx, key, "hwio"), stride, out, stats=st)
+        elif stride == 1 or self._wide_s2(cin, cout):
+            K.conv(src, self._w(ctx, key, "ohwi"), 3, dil, out, stats=st, **({"stride": stride} if stride != 1 else {}))
+        else:                                   # stride 1 + subsampling: four times the work
+            yfull = self._buf(src.x, N * H * W, cout)
+            K.conv(src, self._w(ctx, key, "ohwi"), 3, dil, yfull)
+            K.rows_stride(yfull, N, H, W, stride, out)
+            if training:
+                K.colstats(out, st, **({"N": N} if self.tn else {}))
+
+    def _conv3x3_backward(self, ctx, G, key, src, dy, dil, stride, out):
+        """Weight gradient of ``_conv3x3`` into G and its input gradient (w.r.t. the activated ``src``) into ``out``; the input
+        gradient of a stride-2 conv is a stride-1 conv of the zero-stuffed gradient."""
+        K, N, H, W = self.K, src.N, src.H, src.W
+        cin, cout = src.C, dy.shape[1]
+        narrow_w = self._narrow("wgrad", cin, cout, stride, dil)
+        native = stride == 1 or self._wide_s2(cin, cout)
+        if narrow_w:
+            dw = torch.empty_like(ctx.params[key])
+            K.conv3n_wgrad(src, dy, stride, dw)
+            G[key] = dw
+        elif native:
+            self._wgrad(ctx, G, key, src, dy, 3, dil, stride)
+        if stride != 1:
+            full = self._buf(src.x, src.P, cout)
+            K.rows_stride(dy, N, H, W, stride, full, scatter=True)
+            dy = full
+        if not narrow_w and not native:
+            self._wgrad(ctx, G, key, src, dy, 3, dil)
+        if self._narrow("dgrad", cin, cout, stride, dil):
+            K.conv3n_fwd(Act(dy, N, H, W), self._w(ctx, key, "hwio_dgrad"), 1, out)
+        else:
+            self._dgrad(ctx, key, dy, N, H, W, 3, dil, out)
+        return out
+
+    # ------------------------------------------------------------------ Bottleneck sequence (ResNet-101 layer1-4, DRN-D-54 layer3-6)
+    def _bottlenecks_forward(self, ctx, x, a, training, low_after):
+        """resnet.py:23-43 = drn.py:79-99 over ``self.rblocks``; ``a`` may carry a pending transform (DRN: layer2's BN + ReLU).
+        Returns the last block's output and the output of block ``low_after``."""
+        K, S = self.K, ctx.S
+        N = ctx.N
         recs, low = [], None
         for pre, inp, planes, stride, dil, has_ds in self.rblocks:
             zin, H, W = a, a.H, a.W
@@ -428,15 +514,7 @@ class GeneratorEngine:
             a1 = self._bn_act(ctx, pre + ".bn1", y1, N, H, W, st, P, training, ACT_RELU)
             y2 = self._buf(x, Po, planes)
             st = self._stats(ctx, planes, training)
-            if stride == 1 or _NATIVE_S2:
-                K.conv(a1, self._w(ctx, pre + ".conv2.weight", "ohwi"), 3, dil, y2, stats=st, **({"stride": stride} if stride != 1 else {}))
-            else:
-                yfull = self._buf(x, P, planes)
-                K.conv(a1, self._w(ctx, pre + ".conv2.weight", "ohwi"), 3, dil, yfull)
-                K.rows_stride(yfull, N, H, W, stride, y2)
-                if training:
-                    K.colstats(y2, st, **({"N": N} if self.tn else {}))
-                del yfull
+            self._conv3x3(ctx, a1, pre + ".conv2.weight", dil, stride, y2, st, training)
             a2 = self._bn_act(ctx, pre + ".bn2", y2, N, Ho, Wo, st, Po, training, ACT_RELU)
             y3 = self._buf(x, Po, 4 * planes)
             st = self._stats(ctx, 4 * planes, training)
@@ -448,7 +526,7 @@ class GeneratorEngine:
                 if stride != 1:
                     zsb = self._buf(x, Po, inp)
                     K.rows_stride(zin.x, N, H, W, stride, zsb)
-                    zs = Act(zsb, N, Ho, Wo)
+                    zs = Act(zsb, N, Ho, Wo, zin.scale, zin.shift, zin.act, bn=zin.bn)     # the pending transform is per channel
                 yd = self._buf(x, Po, 4 * planes)
                 st = self._stats(ctx, 4 * planes, training)
                 K.conv(zs, self._w(ctx, pre + ".downsample.0.weight", "ohwi"), 1, 1, yd, stats=st)
@@ -457,20 +535,21 @@ class GeneratorEngine:
             K.bn_add_relu(a3, ad if has_ds else zin, zo)
             a = Act(zo, N, Ho, Wo)
             recs.append(dict(pre=pre, stride=stride, dil=dil, zin=zin, a1=a1, a2=a2, a3=a3, zs=zs, ad=ad, zo=a))
-            if pre.endswith("layer1.2"):
+            if pre == low_after:
                 low = a
         S["rblocks"] = recs
         return a, low
 
-    def _resnet_backward(self, ctx, G, d_z, d_low):
-        """d_z: gradient w.r.t. the [P16, 2048] backbone output, d_low: w.r.t. the layer1 output."""
+    def _bottlenecks_backward(self, ctx, G, d_z, d_low, low_after):
+        """d_z: gradient w.r.t. the last block's output, d_low: w.r.t. the output of block ``low_after``.  Returns the gradient
+        w.r.t. the (activated) input of the first block."""
         K, S, x = self.K, ctx.S, ctx.x
         N = ctx.N
         for r in reversed(S["rblocks"]):
             pre, stride, dil = r["pre"], r["stride"], r["dil"]
             zin, a1, a2, a3, zs, ad, zo = r["zin"], r["a1"], r["a2"], r["a3"], r["zs"], r["ad"], r["zo"]
             H, W, Ho, Wo = zin.H, zin.W, zo.H, zo.W
-            if pre.endswith("layer1.2"):
+            if pre == low_after:
                 d_z.add_(d_low)
             g = self._buf(x, zo.P, zo.C)
             K.relu_gate(d_z, zo.x, g)
@@ -482,16 +561,8 @@ class GeneratorEngine:
             self._dgrad(ctx, pre + ".conv3.weight", dy3, N, Ho, Wo, 1, 1, dU2)
             del dy3
             dy2 = self._bn_backward(ctx, G, a2, dU2)
-            if _NATIVE_S2:
-                self._wgrad(ctx, G, pre + ".conv2.weight", a1, dy2, 3, dil, stride)
-            if stride != 1:                   # input gradient: stride-1 conv of the zero-stuffed gradient
-                full = self._buf(x, a1.P, a2.C)
-                K.rows_stride(dy2, N, H, W, stride, full, scatter=True)
-                dy2 = full
-            if not _NATIVE_S2:
-                self._wgrad(ctx, G, pre + ".conv2.weight", a1, dy2, 3, dil)
             dU1 = self._buf(x, a1.P, a1.C)
-            self._dgrad(ctx, pre + ".conv2.weight", dy2, N, H, W, 3, dil, dU1)
+            self._conv3x3_backward(ctx, G, pre + ".conv2.weight", a1, dy2, dil, stride, dU1)
             del dU2, dy2
             dy1 = self._bn_backward(ctx, G, a1, dU1)
             self._wgrad(ctx, G, pre + ".conv1.weight", zin, dy1, 1, 1)
@@ -511,6 +582,13 @@ class GeneratorEngine:
                 self._dgrad(ctx, pre + ".conv1.weight", dy1, N, H, W, 1, 1, d_zin, addend=g)
             del g, dU1, dy1
             d_z = d_zin
+        return d_z
+
+    def _resnet_backward(self, ctx, G, d_z, d_low):
+        """d_z: gradient w.r.t. the [P16, 2048] backbone output, d_low: w.r.t. the layer1 output."""
+        K, S, x = self.K, ctx.S, ctx.x
+        N = ctx.N
+        d_z = self._bottlenecks_backward(ctx, G, d_z, d_low, "backbone.layer1.2")
         st = S["stem"]
         a0 = st["a0"]
         dU0 = self._buf(x, a0.P, 64)
@@ -573,6 +651,61 @@ class GeneratorEngine:
         dw0 = torch.empty_like(ctx.params["backbone.features.0.0.weight"])
         K.stem_wgrad(x, dy0, dw0)
         G["backbone.features.0.0.weight"] = dw0
+
+    # ------------------------------------------------------------------ DRN-D-54 backbone
+    def _drn_forward(self, ctx, x, training):
+        """drn.py:208-234.  layer0 - layer2 (the head: 7x7 stem and two narrow 3x3 convs at full / half resolution) and
+        layer7 - layer8 are conv + BN + ReLU with the BN pending in the consumer; layer3 - layer6 are the Bottleneck sequence
+        shared with ResNet-101.  The low-level feature is the layer3 output."""
+        K, S = self.K, ctx.S
+        N, _, H, W = x.shape
+        a, head = None, []
+        for ck, bk, ci, co, k, s, d in self.dhead:
+            key = "backbone." + ck + ".weight"
+            Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+            y = self._buf(x, N * Ho * Wo, co)
+            st = self._stats(ctx, co, training)
+            if k == 7:
+                K.stem7s1_fwd(x, self._w(ctx, key, "hwio"), y, st)
+            else:
+                self._conv3x3(ctx, a, key, d, s, y, st, training)
+            src, H, W = a, Ho, Wo
+            a = self._bn_act(ctx, "backbone." + bk, y, N, H, W, st, N * H * W, training, ACT_RELU)
+            head.append(dict(key=key, src=src, a=a, stride=s, dil=d))
+        a, low = self._bottlenecks_forward(ctx, x, a, training, self.dlow)
+        tail = []
+        for ck, bk, ci, co, k, s, d in self.dtail:
+            key = "backbone." + ck + ".weight"
+            y = self._buf(x, a.P, co)
+            st = self._stats(ctx, co, training)
+            self._conv3x3(ctx, a, key, d, 1, y, st, training)
+            src = a
+            a = self._bn_act(ctx, "backbone." + bk, y, N, a.H, a.W, st, a.P, training, ACT_RELU)
+            tail.append(dict(key=key, src=src, a=a, stride=1, dil=d))
+        out = self._buf(x, a.P, a.C)                # the ASPP's pooling branch reads the activated matrix
+        K.bn_apply(a, out, None)
+        S["dhead"], S["dtail"] = head, tail
+        return Act(out, N, a.H, a.W), low
+
+    def _drn_backward(self, ctx, G, d_a, d_low):
+        """d_a: gradient w.r.t. the activated [P8, 512] backbone output, d_low: w.r.t. the layer3 output."""
+        K, S, x = self.K, ctx.S, ctx.x
+        d_z = d_a
+        for r in reversed(S["dtail"]):
+            dy = self._bn_backward(ctx, G, r["a"], d_z)
+            d_z = self._conv3x3_backward(ctx, G, r["key"], r["src"], dy, r["dil"], 1, self._buf(x, r["src"].P, r["src"].C))
+            del dy
+        d_z = self._bottlenecks_backward(ctx, G, d_z, d_low, self.dlow)
+        for r in reversed(S["dhead"]):
+            dy = self._bn_backward(ctx, G, r["a"], d_z)
+            src = r["src"]
+            if src is None:                          # layer0 reads the image, which needs no gradient
+                dw = torch.empty_like(ctx.params[r["key"]])
+                K.stem7s1_wgrad(x, dy, dw)
+                G[r["key"]] = dw
+            else:
+                d_z = self._conv3x3_backward(ctx, G, r["key"], src, dy, r["dil"], r["stride"], self._buf(x, src.P, src.C))
+            del dy
 
     # ------------------------------------------------------------------ Aligned Xception backbone
     def _sep_forward(self, ctx, v, pre, bn_key, cout, stride, dil, training, act):
@@ -753,6 +886,8 @@ class GeneratorEngine:
             a, low = self._mobilenet_forward(ctx, x, training)
         elif self.backbone == "xception":
             a, low = self._xception_forward(ctx, x, training)
+        elif self.backbone == "drn":
+            a, low = self._drn_forward(ctx, x, training)
         else:
             a, low = self._resnet_forward(ctx, x, training)
         # ---- ASPP (aspp.py:65-78): branches write channel windows of one [P, 1280] buffer
@@ -1155,6 +1290,8 @@ class GeneratorEngine:
             self._mobilenet_backward(ctx, G, d_a, d_low)
         elif self.backbone == "xception":
             self._xception_backward(ctx, G, d_a, d_low)
+        elif self.backbone == "drn":
+            self._drn_backward(ctx, G, d_a, d_low)
         else:
             self._resnet_backward(ctx, G, d_a, d_low)
         self._check_arena(ctx)

@@ -71,6 +71,12 @@ SYMBOLS = {
     "uda_stem7_workspace_bytes": (_U, [_L]),
     "uda_stem7_fwd": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
     "uda_stem7_wgrad": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _U, _P]),
+    "uda_stem7s1_workspace_bytes": (_U, [_L]),
+    "uda_stem7s1_fwd": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
+    "uda_stem7s1_wgrad": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _U, _P]),
+    "uda_conv3n_fwd": (_I, [C.POINTER(UdaSrc), _P, _I, _I, _P, _L, _P, _P]),
+    "uda_conv3n_workspace_bytes": (_U, [_I, _I]),
+    "uda_conv3n_wgrad": (_I, [C.POINTER(UdaSrc), _P, _L, _I, _I, _P, _P, _U, _P]),
     "uda_maxpool_fwd": (_I, [C.POINTER(UdaSrc), _P, _L, _P, _L, _P]),
     "uda_maxpool_bwd": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P]),
     "uda_rows_stride": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
@@ -466,6 +472,55 @@ class HipKernels:
         ws = self._ws(dy, self.lib.uda_stem7_workspace_bytes(Po))
         self._ck(self.lib.uda_stem7_wgrad(x.data_ptr(), N, H, W, g, ldg, dw.data_ptr(), ws.data_ptr(), ws.numel(),
                                           self._stream()))
+
+    # ------------------------------------------------------------------ DRN-D-54 head
+    @staticmethod
+    def relayout_hwio(w, dgrad=False):
+        """[O, I, kh, kw] -> [kh, kw, I, O], the operand of stem7s1_fwd / conv3n_fwd (output channels fastest: one tap's
+        weights of one input channel are consecutive).  dgrad=True: [kh, kw, O, I] with flipped taps, the operand that makes
+        the stride-1 conv3n_fwd the input gradient."""
+        if dgrad:
+            return w.flip(2, 3).permute(2, 3, 0, 1).contiguous()
+        return w.permute(2, 3, 1, 0).contiguous()
+
+    def stem7s1_fwd(self, x, w_hwio, out, stats=None):
+        self._dev(x)
+        N, c3, H, W = x.shape
+        assert c3 == 3 and x.is_contiguous() and w_hwio.is_contiguous() and tuple(w_hwio.shape) == (7, 7, 3, 16)
+        assert out.shape == (N * H * W, 16)
+        y, ldy = _mat(out, "out")
+        if stats is not None:
+            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, 16)
+        self._ck(self.lib.uda_stem7s1_fwd(x.data_ptr(), N, H, W, w_hwio.data_ptr(), y, ldy, _ptr(stats), self._stream()))
+
+    def stem7s1_wgrad(self, x, dy, dw):
+        N, _, H, W = x.shape
+        assert dy.shape == (N * H * W, 16) and dw.is_contiguous() and tuple(dw.shape) == (16, 3, 7, 7)
+        g, ldg = _mat(dy, "dy")
+        ws = self._ws(dy, self.lib.uda_stem7s1_workspace_bytes(N * H * W))
+        self._ck(self.lib.uda_stem7s1_wgrad(x.data_ptr(), N, H, W, g, ldg, dw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            self._stream()))
+
+    def conv3n_fwd(self, src: Act, w_hwio, stride, out, stats=None):
+        """narrow dense 3x3 (16 / 32 / 64 channels on either side, stride 1 | 2; anything else raises from the C side)"""
+        s = self._src(src)
+        Cout = out.shape[1]
+        Ho, Wo = (src.H - 1) // stride + 1, (src.W - 1) // stride + 1
+        assert out.shape[0] == src.N * Ho * Wo and w_hwio.is_contiguous() and tuple(w_hwio.shape) == (3, 3, src.C, Cout)
+        y, ldy = _mat(out, "out")
+        if stats is not None:
+            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, Cout)
+        self._ck(self.lib.uda_conv3n_fwd(C.byref(s), w_hwio.data_ptr(), Cout, stride, y, ldy, _ptr(stats), self._stream()))
+
+    def conv3n_wgrad(self, src: Act, dy, stride, dw):
+        s = self._src(src)
+        Cout = dy.shape[1]
+        Ho, Wo = (src.H - 1) // stride + 1, (src.W - 1) // stride + 1
+        assert dy.shape[0] == src.N * Ho * Wo and dw.is_contiguous() and tuple(dw.shape) == (Cout, src.C, 3, 3)
+        g, ldg = _mat(dy, "dy")
+        ws = self._ws(dy, self.lib.uda_conv3n_workspace_bytes(src.C, Cout))
+        self._ck(self.lib.uda_conv3n_wgrad(C.byref(s), g, ldg, Cout, stride, dw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           self._stream()))
 
     def maxpool_fwd(self, src: Act, out, idx):
         s = self._src(src)

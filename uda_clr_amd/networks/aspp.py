@@ -8,9 +8,9 @@ from ._tree import Holder, child, conv, kaiming_bn_init
 class ASPP(Holder):
     def __init__(self, backbone, output_stride, BatchNorm):
         super().__init__()
-        if backbone not in ('mobilenet', 'resnet', 'xception'):
-            raise NotImplementedError("ASPP is built for the mobilenet (320), resnet and xception (2048) backbones")
-        cin = 320 if backbone == 'mobilenet' else 2048           # aspp.py:37-42
+        if backbone not in ('mobilenet', 'resnet', 'xception', 'drn'):
+            raise NotImplementedError("ASPP is built for the mobilenet (320), drn (512), resnet and xception (2048) backbones")
+        cin = {'mobilenet': 320, 'drn': 512}.get(backbone, 2048)           # aspp.py:37-42
         if output_stride not in (16, 8):
             raise NotImplementedError
         dils = (1, 6, 12, 18) if output_stride == 16 else (1, 12, 24, 36)

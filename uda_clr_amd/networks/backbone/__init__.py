@@ -1,4 +1,4 @@
-from . import mobilenet, resnet, xception
+from . import drn, mobilenet, resnet, xception
 
 
 def build_backbone(backbone, output_stride, BatchNorm):
@@ -8,4 +8,6 @@ def build_backbone(backbone, output_stride, BatchNorm):
         return resnet.ResNet101(output_stride, BatchNorm)
     if backbone == 'xception':
         return xception.AlignedXception(output_stride, BatchNorm)
-    raise NotImplementedError("backbone %r is not built (mobilenet, resnet and xception are)" % (backbone,))
+    if backbone == 'drn':
+        return drn.drn_d_54(BatchNorm)
+    raise NotImplementedError("backbone %r is not built (mobilenet, resnet, xception and drn are)" % (backbone,))

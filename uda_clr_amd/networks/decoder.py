@@ -8,9 +8,9 @@ from ._tree import Holder, child, conv, kaiming_bn_init
 class Decoder(Holder):
     def __init__(self, num_classes, backbone, method, BatchNorm):
         super().__init__()
-        low = {'mobilenet': 24, 'resnet': 256, 'xception': 128}.get(backbone)      # decoder.py:11-16
+        low = {'mobilenet': 24, 'resnet': 256, 'drn': 256, 'xception': 128}.get(backbone)      # decoder.py:11-16
         if low is None:
-            raise NotImplementedError("decoder is built for the mobilenet (24), resnet (256) and xception (128) low-level widths")
+            raise NotImplementedError("decoder is built for the mobilenet (24), resnet / drn (256) and xception (128) low-level widths")
         self.method = method
         child(self, "conv1", conv(low, 48, 1))
         child(self, "bn1", BatchNorm(48))

@@ -1,4 +1,4 @@
-"""DeepLabV3+ generator (MobileNetV2, ResNet-101 or Aligned Xception backbone) - the drop-in for the reference's
+"""DeepLabV3+ generator (MobileNetV2, ResNet-101, Aligned Xception or DRN-D-54 backbone) - the drop-in for the reference's
 ``networks/deeplabv3.py``.
 
 Same constructor, same ``state_dict`` keys (675 entries incl. the aliased backbone slices; 899 with
@@ -80,8 +80,10 @@ class DeepLab(Holder):
             raise NotImplementedError("the fused heads are built for num_classes=2 (cup, disc)")
         # deeplabv3.py:17-23: sync_bn=True is plain nn.BatchNorm2d, sync_bn=False (--use_TN) is TransNorm
         self.transnorm = not sync_bn
-        if self.transnorm and backbone == 'xception':
-            raise NotImplementedError("TransNorm (sync_bn=False) is not built for the xception backbone; use sync_bn=True")
+        if self.transnorm and backbone in ('xception', 'drn'):
+            raise NotImplementedError("TransNorm (sync_bn=False) is not built for the %s backbone; use sync_bn=True" % backbone)
+        if backbone == 'drn':
+            output_stride = 8             # deeplabv3.py:14-15: DRN's output sits at 1/8 whatever is asked for
         BatchNorm = TransNorm2d if self.transnorm else nn.BatchNorm2d
         self.output_stride = output_stride
         self.backbone_name = backbone
