@@ -194,18 +194,18 @@ def _mobilenet_backbone(c, x, output_stride):
     return h, low
 
 
-def deeplab_forward(sd, x, training=True, masks=None, record=None, output_stride=16, bn_training=None):
+def deeplab_forward(sd, x, training=True, masks=None, record=None, output_stride=16, bn_training=None, backbone=None):
     """Returns (x1, x2, feature, x_bu_feature, x_feature, x1_before, x2_before).
 
     ``sd`` maps reference state-dict keys to tensors; BN running stats in it are
-    updated in place when ``training`` (deeplabv3.py:32-41).  The backbone is told
-    from the keys (``backbone.conv1.weight`` exists only in the ResNet).
+    updated in place when ``training`` (deeplabv3.py:32-41).  ``backbone`` is a callable
+    (c, x, output_stride) -> (high-level, low-level feature); by default MobileNetV2 or ResNet-101,
+    told from the keys (of these two ``backbone.conv1.weight`` exists only in the ResNet).
     """
     c = _Ctx(sd, training, masks, record, bn_training)
-    if "backbone.conv1.weight" in sd:
-        h, low = _resnet_backbone(c, x, output_stride)
-    else:
-        h, low = _mobilenet_backbone(c, x, output_stride)
+    if backbone is None:
+        backbone = _resnet_backbone if "backbone.conv1.weight" in sd else _mobilenet_backbone
+    h, low = backbone(c, x, output_stride)
     # --- ASPP (aspp.py:65-78)
     dils = (1, 6, 12, 18) if output_stride == 16 else (1, 12, 24, 36)
     br = []

@@ -103,8 +103,9 @@ def seeded_model(seed=1337, perturb=False, backbone="mobilenet", output_stride=1
     return m
 
 
-def eval_parity(dev, B=2, S=64, perturb=True, backbone="mobilenet", transnorm=False):
-    """HIP eval forward vs the oracle on the same weights; returns {output: rel err}."""
+def eval_parity(dev, B=2, S=64, perturb=True, backbone="mobilenet", transnorm=False, oracle_forward=deeplab_ref.deeplab_forward):
+    """HIP eval forward vs the oracle (``oracle_forward``: the backbone's statement of ``deeplab_ref.deeplab_forward``) on the same
+    weights; returns {output: rel err}."""
     m = seeded_model(perturb=perturb, backbone=backbone, transnorm=transnorm).eval()
     x = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(0))
     if transnorm:
@@ -113,7 +114,7 @@ def eval_parity(dev, B=2, S=64, perturb=True, backbone="mobilenet", transnorm=Fa
         calibrate_running_stats(m, xc)
     sd = deeplab_ref.canonical_state(m.state_dict())
     with torch.no_grad():
-        ref = deeplab_ref.deeplab_forward(sd, x, training=False)
+        ref = oracle_forward(sd, x, training=False)
         m.to(dev)
         out = m(x.to(dev))
     return {n: rel(a, b) for n, a, b in zip(NAMES, out, ref)}
@@ -134,8 +135,8 @@ def calibrate_running_stats(m, x):
 
 
 def train_parity(dev, B=2, S=64, extra_heads=True, backbone="mobilenet", output_stride=16, transnorm=False, frozen_bn=False,
-                 engine=None, seed=3):
-    """HIP training forward + backward (injected dropout masks) vs the fp64 oracle.  Returns
+                 engine=None, seed=3, oracle_forward=deeplab_ref.deeplab_forward):
+    """HIP training forward + backward (injected dropout masks) vs the fp64 oracle (``oracle_forward`` as in ``eval_parity``).  Returns
     (forward errs vs fp32 oracle, {param: (err vs fp64, fp32-oracle err vs fp64)}, running-stat err,
     {output: (err vs fp64, fp32-oracle err vs fp64)})."""
     m = seeded_model(perturb=True, backbone=backbone, output_stride=output_stride, transnorm=transnorm).train()
@@ -178,13 +179,13 @@ def train_parity(dev, B=2, S=64, extra_heads=True, backbone="mobilenet", output_
     torch.set_num_threads(1)
     try:
         o32 = deeplab_ref.canonical_state(sd0, requires_grad=True)
-        r32 = deeplab_ref.deeplab_forward(o32, x, training=True, masks=masks, output_stride=output_stride, bn_training=bn_tr)
+        r32 = oracle_forward(o32, x, training=True, masks=masks, output_stride=output_stride, bn_training=bn_tr)
         total(r32, torch.float32, "cpu").backward()
     finally:
         torch.set_num_threads(threads)
     o64 = {k: (v.detach().double().requires_grad_(v.requires_grad) if v.is_floating_point() else v.clone())
            for k, v in deeplab_ref.canonical_state(sd0, requires_grad=True).items()}
-    r64 = deeplab_ref.deeplab_forward(o64, x.double(), training=True, masks=masks, output_stride=output_stride, bn_training=bn_tr)
+    r64 = oracle_forward(o64, x.double(), training=True, masks=masks, output_stride=output_stride, bn_training=bn_tr)
     total(r64, torch.float64, "cpu").backward()
     m.to(dev)
     m.set_dropout_masks(masks)
@@ -201,13 +202,23 @@ def train_parity(dev, B=2, S=64, extra_heads=True, backbone="mobilenet", output_
     return fwd, grads, stats, fwd64
 
 
-def golden_parity(dev, tag):
+def golden_parity(dev, tag, backbone=None, oracle_forward=deeplab_ref.deeplab_forward, engine=None, stat_floor=1e-3,
+                  n_grad_keys=None, output_stride=None):
     """HIP path vs the fixtures written by the reference itself (tests/golden/forward_<tag>.npz):
     seeded init, seeded input, eval outputs (checksums + samples), train loss and grad norms with the
-    oracle-recovered dropout masks of the reference's own draw."""
+    oracle-recovered dropout masks of the reference's own draw.  ``backbone`` (default: resnet or mobilenet by the tag) with its
+    ``oracle_forward``; the output stride is the fixture's (16 where it names none); ``engine``: the CPU tests' engine on their
+    kernel statement; ``stat_floor``: absolute floor of the running-statistic sums' relative error; ``n_grad_keys`` / ``output_stride``:
+    what the fixture must hold (number of gradient norms, its output stride)."""
     z = np.load(os.path.join(GOLDEN, "forward_%s.npz" % tag))
     B, S = int(z["B"]), int(z["S"])
-    m = seeded_model(backbone="resnet" if tag.startswith("resnet") else "mobilenet", transnorm="tn" in tag.split("_"))
+    os_ = int(z["output_stride"]) if "output_stride" in z else 16
+    assert output_stride is None or os_ == output_stride
+    if backbone is None:
+        backbone = "resnet" if tag.startswith("resnet") else "mobilenet"
+    m = seeded_model(backbone=backbone, output_stride=os_, transnorm="tn" in tag.split("_"))
+    if engine is not None:
+        m._engine_override = engine
     torch.manual_seed(int(z["input_seed"]))
     x = torch.randn(B, 3, S, S)
     errs = {}
@@ -234,7 +245,7 @@ def golden_parity(dev, tag):
     rec = {}
     torch.manual_seed(int(z["dropout_seed"]))
     with torch.no_grad():
-        deeplab_ref.deeplab_forward(sd0, x, training=True, record=rec)
+        oracle_forward(sd0, x, training=True, record=rec, output_stride=os_)
     for k, v in rec.items():
         assert int(v.sum()) == int(z["mask.%s.sum" % k]), "dropout stream differs from the reference's draw"
     m.set_dropout_masks(rec)
@@ -249,6 +260,7 @@ def golden_parity(dev, tag):
         errs["train." + n + ".abs"] = abs(d.abs().sum().item() - float(z["train.%s.abs" % n])) / float(z["train.%s.abs" % n])
     live = m._flat_state()
     keys = [str(k) for k in z["train.grad_keys"]]
+    assert n_grad_keys is None or len(keys) == n_grad_keys
     gn = np.array([live[k].grad.double().norm().item() for k in keys])
     rel_gn = np.abs(gn - z["train.grad_norm"]) / np.maximum(z["train.grad_norm"], 1e-12)
     conv = np.array([live[k].dim() == 4 for k in keys])
@@ -257,5 +269,5 @@ def golden_parity(dev, tag):
     errs["train.grad_norm.conv"] = float(rel_gn[conv].max())
     errs["train.grad_norm.median"] = float(np.median(rel_gn))
     bs = np.array([live[k].double().sum().item() for k in z["train.bn_keys"]])
-    errs["train.bn_sum"] = float(np.max(np.abs(bs - z["train.bn_sum"]) / np.maximum(np.abs(z["train.bn_sum"]), 1e-3)))
+    errs["train.bn_sum"] = float(np.max(np.abs(bs - z["train.bn_sum"]) / np.maximum(np.abs(z["train.bn_sum"]), stat_floor)))
     return errs

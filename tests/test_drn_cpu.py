@@ -5,14 +5,14 @@ tests/drn_spec.py) against the functional oracle of tests/drn_ref.py and against
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 
+import backbone_cases
 import drn_ref
 import model_cases
 from drn_spec import DrnSpecKernels
-from oracle import deeplab_ref, step_ref
+from oracle import deeplab_ref
 from uda_clr_amd.engine import GeneratorEngine
 from uda_clr_amd.networks.deeplabv3 import DeepLab
 
@@ -126,121 +126,30 @@ def test_train_forward_backward_matches_oracle(narrow, monkeypatch):
     parameter left out (every DRN BatchNorm is followed by a ReLU or by the residual add + ReLU: no gradient is analytically
     zero).  Runs on the routes the engine picks, with every head conv on the implicit-GEMM route (stride 2 = stride 1 +
     subsampling / zero stuffing) and with every head conv on the narrow kernels."""
-    from uda_clr_amd import engine
-    monkeypatch.setattr(engine, "_DRN_NARROW_ENV", narrow)
-    with drn_ref.as_deeplab_oracle():
-        fwd, grads, stats, fwd64 = model_cases.train_parity(torch.device("cpu"), backbone="drn", output_stride=8, engine=_engine())
-    for n, (mine, floor) in fwd64.items():
-        assert mine < 3.0 * floor + 2e-4, (n, mine, floor)
-    assert len(grads) == 204
-    assert all(v[0] < float("inf") for v in grads.values()), [k for k, v in grads.items() if v[0] == float("inf")]
-    bad, gmean = model_cases.grads_ok(grads)
-    assert not bad, list(bad.items())[:10]
-    assert gmean < 1.5, gmean
-    assert stats < 1e-3, stats
+    from uda_clr_amd.networks.backbone import drn
+    monkeypatch.setattr(drn, "_DRN_NARROW_ENV", narrow)
+    fwd, grads, stats, fwd64 = model_cases.train_parity(torch.device("cpu"), backbone="drn", output_stride=8, engine=_engine(),
+                                                        oracle_forward=drn_ref.deeplab_forward)
+    backbone_cases.train_checks(fwd64, grads, stats, stats_bound=1e-3, gmean_bound=1.5, n_grads=204)
 
 
 def test_frozen_batchnorm_training_matches_oracle():
     """freeze_bn() while training: eval-mode BatchNorm (running statistics, no batch terms in the backward), live dropout."""
-    with drn_ref.as_deeplab_oracle():
-        fwd, grads, stats, _ = model_cases.train_parity(torch.device("cpu"), backbone="drn", output_stride=8, frozen_bn=True,
-                                                        engine=_engine(), seed=11)
+    fwd, grads, stats, _ = model_cases.train_parity(torch.device("cpu"), backbone="drn", output_stride=8, frozen_bn=True,
+                                                    engine=_engine(), seed=11, oracle_forward=drn_ref.deeplab_forward)
     assert stats == 0.0
     model_cases.frozen_grads_ok(grads)
 
 
 def test_mc_fast_path_equals_plain_stochastic_forwards():
     """GeneratorEngine.mc_forward (the DRN backbone's activations reused) vs plain stochastic forwards on identical masks."""
-    B, S, passes = 2, 64, 2
-    gen = torch.Generator().manual_seed(8)
-    x = torch.randn(B, 3, S, S, generator=gen)
-
-    def masks(n):
-        mk = deeplab_ref.draw_masks(n, S, S, gen)
-        mk["aspp.dropout"] = (torch.rand(n, 256, S // 8, S // 8, generator=gen) >= 0.5).to(torch.uint8)
-        return mk
-    m0 = masks(B)
-    mc_masks = [masks(2 * B) for _ in range(passes)]
-    res = []
-    for fast in (False, True):
-        m = _model().train()
-        m.set_dropout_masks(m0)
-        m(x)
-        if not fast:
-            m._recent = []
-        preds = m.mc_dropout_logits(x, passes=passes, reps=2, masks=mc_masks)
-        res.append((preds, {k: v.clone() for k, v in m.state_dict().items()}))
-    (p0, s0), (p1, s1) = res
-    assert model_cases.rel(p1, p0) < 1e-4
-    for k in s0:
-        if k.endswith("num_batches_tracked"):
-            assert int(s0[k]) == int(s1[k]) == 1 + passes
-        elif k.endswith("running_mean") or k.endswith("running_var"):
-            assert model_cases.rel(s1[k], s0[k]) < 1e-4, k
+    backbone_cases.mc_fast_path_equals_plain_stochastic_forwards(lambda: _model().train(), torch.device("cpu"), 8)
 
 
 def golden_errors(dev, tag, engine=None):
-    """The DRN model (``engine``: CPU tests' kernel statement) against forward_<tag>.npz, as model_cases.golden_parity does for
-    the other backbones."""
-    z = np.load(os.path.join(GOLDEN, "forward_%s.npz" % tag))
-    B, S = int(z["B"]), int(z["S"])
-    assert int(z["output_stride"]) == 8
-    m = model_cases.seeded_model(backbone="drn", output_stride=8)
-    if engine is not None:
-        m._engine_override = engine
-    torch.manual_seed(int(z["input_seed"]))
-    x = torch.randn(B, 3, S, S)
-    errs = {}
-    m.to(dev).eval()
-    with torch.no_grad():
-        out = m(x.to(dev))
-    for n, t in zip(NAMES, out):
-        f = t.double().cpu().reshape(-1)
-        idx = torch.linspace(0, f.numel() - 1, 97).long()
-        ref = torch.from_numpy(z["eval.%s.smp" % n])
-        errs["eval." + n + ".smp"] = (f[idx] - ref).abs().max().item() / max(ref.abs().max().item(), 1e-30)
-        errs["eval." + n + ".abs"] = abs(f.abs().sum().item() - float(z["eval.%s.abs" % n])) / float(z["eval.%s.abs" % n])
-    from make_golden_inputs import synth_targets
-    tmap, tbd = synth_targets(B, S, S, int(z["target_seed"]))
-    m.train()
-    sd0 = deeplab_ref.canonical_state({k: v.cpu() for k, v in m.state_dict().items()})
-    rec = {}
-    torch.manual_seed(int(z["dropout_seed"]))
-    with torch.no_grad():
-        drn_ref.deeplab_forward(sd0, x, training=True, record=rec)
-    for k, v in rec.items():
-        assert int(v.sum()) == int(z["mask.%s.sum" % k]), "dropout stream differs from the reference's draw"
-    m.set_dropout_masks(rec)
-    out = m(x.to(dev))
-    assert all(bool(torch.isfinite(t).all()) for t in out)
-    loss = step_ref.seg_loss(out[0], out[1], tmap.to(dev), tbd.to(dev))
-    loss.backward()
-    errs["train.loss"] = abs(loss.item() - float(z["train.loss"])) / abs(float(z["train.loss"]))
-    for n, t in zip(NAMES, out):
-        d = t.detach().double().cpu()
-        errs["train." + n + ".abs"] = abs(d.abs().sum().item() - float(z["train.%s.abs" % n])) / float(z["train.%s.abs" % n])
-    live = m._flat_state()
-    keys = [str(k) for k in z["train.grad_keys"]]
-    assert len(keys) == 204
-    gn = np.array([live[k].grad.double().norm().item() for k in keys])
-    rel_gn = np.abs(gn - z["train.grad_norm"]) / np.maximum(z["train.grad_norm"], 1e-12)
-    conv = np.array([live[k].dim() == 4 for k in keys])
-    errs["train.grad_norm.conv"] = float(rel_gn[conv].max())
-    errs["train.grad_norm.median"] = float(np.median(rel_gn))
-    bs = np.array([live[k].double().sum().item() for k in z["train.bn_keys"]])
-    errs["train.bn_sum"] = float(np.max(np.abs(bs - z["train.bn_sum"]) / np.maximum(np.abs(z["train.bn_sum"]), 1e-2)))
-    return errs
-
-
-GOLDEN_BOUNDS = {"train.grad_norm.conv": 5e-2, "train.grad_norm.median": 2e-2, "train.bn_sum": 5e-3}      # test_xception_cpu.py's
-
-
-def check_golden(errs):
-    for k, v in errs.items():
-        bound = GOLDEN_BOUNDS.get(k, 1e-3 if k.startswith(("eval.", "train.loss")) else 5e-3)
-        assert v < bound, (k, v, bound)
+    return backbone_cases.golden_errors(dev, tag, "drn", drn_ref.deeplab_forward, engine, n_grad_keys=204, output_stride=8)
 
 
 @pytest.mark.parametrize("tag", ["drn_128", "drn_256"])
 def test_engine_matches_reference_fixture(tag):
-    check_golden(golden_errors(torch.device("cpu"), tag, _engine()))
+    backbone_cases.check_golden(golden_errors(torch.device("cpu"), tag, _engine()))

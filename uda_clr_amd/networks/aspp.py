@@ -3,14 +3,15 @@ initialisation order follow the reference's ``networks/aspp.py:7-95``."""
 import torch.nn as nn
 
 from ._tree import Holder, child, conv, kaiming_bn_init
+from .backbone import BACKBONES
 
 
 class ASPP(Holder):
     def __init__(self, backbone, output_stride, BatchNorm):
         super().__init__()
-        if backbone not in ('mobilenet', 'resnet', 'xception', 'drn'):
+        if backbone not in BACKBONES:
             raise NotImplementedError("ASPP is built for the mobilenet (320), drn (512), resnet and xception (2048) backbones")
-        cin = {'mobilenet': 320, 'drn': 512}.get(backbone, 2048)           # aspp.py:37-42
+        cin = BACKBONES[backbone]['exec'].c_high                            # aspp.py:37-42
         if output_stride not in (16, 8):
             raise NotImplementedError
         dils = (1, 6, 12, 18) if output_stride == 16 else (1, 12, 24, 36)

@@ -1,19 +1,40 @@
-"""DRN-D-54 backbone - parameter tree only (compute: uda_clr_amd.engine).
+"""DRN-D-54 backbone: geometry plan, parameter tree and its execution on the engine's kernels.
 
 Key names, construction order and initialisation of the reference's ``networks/backbone/drn.py:102-206``
 (``DRN(Bottleneck, [1, 1, 3, 4, 6, 3, 1, 1], arch='D')``): ``layer0`` (7x7 stride 1, 3 -> 16), ``layer1`` / ``layer2``
 (3x3 conv layers, the second at stride 2), ``layer3 .. layer6`` of Bottlenecks (layer3 / layer4 at stride 2,
 layer5 / layer6 dilated by 2 / 4), ``layer7`` / ``layer8`` (3x3 conv layers, dilation 2 / 1).  The output sits at
-1/8 of the input, the low-level feature is the ``layer3`` output at 1/4.  ``drn_plan`` is the geometry the engine
-executes.
+1/8 of the input, the low-level feature is the ``layer3`` output at 1/4.  ``drn_plan`` is the geometry.
 """
-import math
 import os
 
 import torch
 import torch.nn as nn
 
-from .._tree import Holder, child, conv
+from ...acts import ACT_RELU, Act
+from .._tree import Holder, child, conv, normal_bn_init
+from ._bottleneck import bottleneck_bn_channels, bottleneck_tree, bottlenecks_backward, bottlenecks_forward, conv3x3, conv3x3_backward
+
+# Which narrow 3x3 convolutions of DRN (16 / 32 / 64 channels: layer1, layer2 and layer3's conv2, drn.py:131-136) run on the
+# direct kernels (uda_conv3n_*) instead of the implicit-GEMM route: (pass, Cin, Cout, stride of the LAYER) -> bool, as measured in
+# profiles/drn_head_kernels.md at B = 8 and 16.  "dgrad" runs as the stride-1 conv Cout -> Cin of the (zero-stuffed) gradient.
+# New / old time: head and layer3.0.conv2 0.20 - 0.57 (its input gradient 0.85 - 0.88); the stride-1 64 -> 64 convs of
+# layer3.1 / layer3.2 at 1/4 resolution: weight gradient 0.70 - 0.72, forward 1.70 / 1.00 and input gradient 1.58 / 0.95 at
+# B = 8 / 16 (512 tiles for 256 CUs), so those two stay where they were.  Shapes not listed stay on the implicit-GEMM route.
+# A/B switch UDA_CLR_DRN_NARROW: 1 = all listed shapes, 0 = none (stride 2 then runs at stride 1 + subsampling / zero
+# stuffing, four times the work).
+_DRN_NARROW_ENV = os.environ.get("UDA_CLR_DRN_NARROW", "")
+_DRN_NARROW = {("fwd", 16, 16, 1): True, ("fwd", 16, 32, 2): True, ("fwd", 64, 64, 2): True, ("fwd", 64, 64, 1): False,
+               ("wgrad", 16, 16, 1): True, ("wgrad", 16, 32, 2): True, ("wgrad", 64, 64, 2): True, ("wgrad", 64, 64, 1): True,
+               ("dgrad", 16, 16, 1): True, ("dgrad", 16, 32, 2): True, ("dgrad", 64, 64, 2): True, ("dgrad", 64, 64, 1): False}
+
+
+def _narrow(what, cin, cout, stride, dil=1):
+    """True when this pass of a 3x3 convolution layer (cin -> cout at ``stride``) runs on the narrow direct kernels."""
+    if dil != 1 or (what, cin, cout, stride) not in _DRN_NARROW:
+        return False
+    return _DRN_NARROW[(what, cin, cout, stride)] if _DRN_NARROW_ENV == "" else _DRN_NARROW_ENV != "0"
+
 
 D54_LAYERS = (1, 1, 3, 4, 6, 3, 1, 1)
 CHANNELS = (16, 32, 64, 128, 256, 512, 512, 512)
@@ -62,26 +83,9 @@ class DRN(Holder):
                 child(self, ck, conv(ci, co, k, s, 3 if k == 7 else d, d))
                 child(self, bk, BatchNorm(co))
         conv_rows(head)
-        for pre, inp, planes, stride, dil, has_ds in blocks:
-            if has_ds:            # the reference builds the shortcut before the block's own convs (drn.py:175-181)
-                ds0, ds1 = conv(inp, 4 * planes, 1, stride), BatchNorm(4 * planes)
-            child(self, pre + ".conv1", conv(inp, planes, 1))
-            child(self, pre + ".bn1", BatchNorm(planes))
-            child(self, pre + ".conv2", conv(planes, planes, 3, stride, dil, dil))
-            child(self, pre + ".bn2", BatchNorm(planes))
-            child(self, pre + ".conv3", conv(planes, 4 * planes, 1))
-            child(self, pre + ".bn3", BatchNorm(4 * planes))
-            if has_ds:
-                child(self, pre + ".downsample.0", ds0)
-                child(self, pre + ".downsample.1", ds1)
+        bottleneck_tree(self, blocks, BatchNorm)
         conv_rows(tail)
-        for m in self.modules():                                   # drn.py:159-169
-            if isinstance(m, nn.Conv2d):
-                n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
-                m.weight.data.normal_(0, math.sqrt(2. / n))
-            elif isinstance(m, (nn.BatchNorm2d, BatchNorm)):
-                m.weight.data.fill_(1)
-                m.bias.data.zero_()
+        normal_bn_init(self.modules(), (nn.BatchNorm2d, BatchNorm))
 
 
 def drn_d_54(BatchNorm, pretrained=True):
@@ -96,3 +100,74 @@ def drn_d_54(BatchNorm, pretrained=True):
         pre.pop("fc.bias", None)
         model.load_state_dict(pre)
     return model
+
+
+class DRNExec:
+    """The backbone's launch sequence on the kernels of one ``GeneratorEngine`` (``engine``: its helpers and kernel binding)."""
+    c_high, c_low = CHANNELS[-1], 4 * CHANNELS[2]
+
+    def __init__(self, engine, output_stride):
+        if output_stride != 8:
+            raise ValueError("the DRN backbone's output sits at 1/8 of the input (deeplabv3.py:14-15): output_stride must be 8")
+        self.E = engine
+        self.head, blocks, self.tail = drn_plan()
+        self.blocks = [("backbone." + pre,) + tuple(rest) for pre, *rest in blocks]
+        self.low_after = [pre for pre, *_ in self.blocks if pre.startswith("backbone.layer3.")][-1]
+        # channels that receive BN statistics in one forward
+        self.bn_channels = sum(row[3] for row in self.head + self.tail) + bottleneck_bn_channels(self.blocks)
+
+    def forward(self, ctx, x, training):
+        """drn.py:208-234.  layer0 - layer2 (the head: 7x7 stem and two narrow 3x3 convs at full / half resolution) and
+        layer7 - layer8 are conv + BN + ReLU with the BN pending in the consumer; layer3 - layer6 are the Bottleneck sequence
+        shared with ResNet-101.  The low-level feature is the layer3 output."""
+        E = self.E
+        K, S = E.K, ctx.S
+        N, _, H, W = x.shape
+        a, head = None, []
+        for ck, bk, ci, co, k, s, d in self.head:
+            key = "backbone." + ck + ".weight"
+            Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+            y = E._buf(x, N * Ho * Wo, co)
+            st = E._stats(ctx, co, training)
+            if k == 7:
+                K.stem7s1_fwd(x, E._w(ctx, key, "hwio"), y, st)
+            else:
+                conv3x3(E, ctx, a, key, d, s, y, st, training, _narrow)
+            src, H, W = a, Ho, Wo
+            a = E._bn_act(ctx, "backbone." + bk, y, N, H, W, st, N * H * W, training, ACT_RELU)
+            head.append(dict(key=key, src=src, a=a, stride=s, dil=d))
+        a, low = bottlenecks_forward(E, ctx, x, a, training, self.blocks, self.low_after, _narrow)
+        tail = []
+        for ck, bk, ci, co, k, s, d in self.tail:
+            key = "backbone." + ck + ".weight"
+            y = E._buf(x, a.P, co)
+            st = E._stats(ctx, co, training)
+            conv3x3(E, ctx, a, key, d, 1, y, st, training, _narrow)
+            src = a
+            a = E._bn_act(ctx, "backbone." + bk, y, N, a.H, a.W, st, a.P, training, ACT_RELU)
+            tail.append(dict(key=key, src=src, a=a, stride=1, dil=d))
+        out = E._buf(x, a.P, a.C)                # the ASPP's pooling branch reads the activated matrix
+        K.bn_apply(a, out, None)
+        S["dhead"], S["dtail"] = head, tail
+        return Act(out, N, a.H, a.W), low
+
+    def backward(self, ctx, G, d_a, d_low):
+        """d_a: gradient w.r.t. the activated [P8, 512] backbone output, d_low: w.r.t. the layer3 output."""
+        E = self.E
+        K, S, x = E.K, ctx.S, ctx.x
+        d_z = d_a
+        for r in reversed(S["dtail"]):
+            dy = E._bn_backward(ctx, G, r["a"], d_z)
+            d_z = conv3x3_backward(E, ctx, G, r["key"], r["src"], dy, r["dil"], 1, E._buf(x, r["src"].P, r["src"].C), _narrow)
+            del dy
+        d_z = bottlenecks_backward(E, ctx, G, d_z, d_low, self.low_after, _narrow)
+        for r in reversed(S["dhead"]):
+            dy = E._bn_backward(ctx, G, r["a"], d_z)
+            src = r["src"]
+            if src is None:                          # layer0 reads the image, which needs no gradient
+                dw = torch.empty_like(ctx.params[r["key"]])
+                K.stem7s1_wgrad(x, dy, dw)
+                G[r["key"]] = dw
+            else:
+                d_z = conv3x3_backward(E, ctx, G, r["key"], src, dy, r["dil"], r["stride"], E._buf(x, src.P, src.C), _narrow)
+            del dy

@@ -3,14 +3,15 @@ Key names / order follow the reference's ``networks/decoder.py:7-74``."""
 import torch.nn as nn
 
 from ._tree import Holder, child, conv, kaiming_bn_init
+from .backbone import BACKBONES
 
 
 class Decoder(Holder):
     def __init__(self, num_classes, backbone, method, BatchNorm):
         super().__init__()
-        low = {'mobilenet': 24, 'resnet': 256, 'drn': 256, 'xception': 128}.get(backbone)      # decoder.py:11-16
-        if low is None:
+        if backbone not in BACKBONES:
             raise NotImplementedError("decoder is built for the mobilenet (24), resnet / drn (256) and xception (128) low-level widths")
+        low = BACKBONES[backbone]['exec'].c_low                             # decoder.py:11-16
         self.method = method
         child(self, "conv1", conv(low, 48, 1))
         child(self, "bn1", BatchNorm(48))

@@ -17,7 +17,7 @@ import torch.nn as nn
 from ..engine import GeneratorEngine
 from ._tree import Holder
 from .aspp import build_aspp
-from .backbone import build_backbone
+from .backbone import backbone_info, build_backbone
 from .decoder import build_decoder
 from .sync_batchnorm.batchnorm import BatchNorm2d as TransNorm2d
 
@@ -80,14 +80,15 @@ class DeepLab(Holder):
             raise NotImplementedError("the fused heads are built for num_classes=2 (cup, disc)")
         # deeplabv3.py:17-23: sync_bn=True is plain nn.BatchNorm2d, sync_bn=False (--use_TN) is TransNorm
         self.transnorm = not sync_bn
-        if self.transnorm and backbone in ('xception', 'drn'):
+        info = backbone_info(backbone)
+        if self.transnorm and not info['transnorm']:
             raise NotImplementedError("TransNorm (sync_bn=False) is not built for the %s backbone; use sync_bn=True" % backbone)
-        if backbone == 'drn':
-            output_stride = 8             # deeplabv3.py:14-15: DRN's output sits at 1/8 whatever is asked for
+        output_stride = info['output_stride'] or output_stride
         BatchNorm = TransNorm2d if self.transnorm else nn.BatchNorm2d
         self.output_stride = output_stride
         self.backbone_name = backbone
         self.backbone = build_backbone(backbone, output_stride, BatchNorm)
+        self._param_root = info['root']   # '' or the child of the backbone tree that holds its parameters (the rest are aliases)
         self.aspp = build_aspp(backbone, output_stride, BatchNorm)
         self.decoder = build_decoder(num_classes, backbone, method, BatchNorm)
         self._engine = None
@@ -116,7 +117,7 @@ class DeepLab(Holder):
                             yield p
 
     def get_1x_lr_params(self):
-        return self._lr_params([self.backbone.features if self.backbone_name == 'mobilenet' else self.backbone])
+        return self._lr_params([self._backbone_root()[1]])
 
     def get_10x_lr_params(self):
         return self._lr_params([self.aspp, self.decoder])
@@ -231,14 +232,18 @@ class DeepLab(Holder):
 
     def _flat_state(self):
         sd = {}
-        bb = ("backbone.features", self.backbone.features) if self.backbone_name == 'mobilenet' \
-            else ("backbone", self.backbone)
-        for name, mod in (bb, ("aspp", self.aspp), ("decoder", self.decoder)):
+        for name, mod in (self._backbone_root(), ("aspp", self.aspp), ("decoder", self.decoder)):
             for k, v in mod.named_parameters(prefix=name):
                 sd[k] = v
             for k, v in mod.named_buffers(prefix=name):
                 sd[k] = v
         return sd
+
+    def _backbone_root(self):
+        """(state-dict prefix, module) of the backbone's parameters."""
+        if self._param_root:
+            return "backbone." + self._param_root, getattr(self.backbone, self._param_root)
+        return "backbone", self.backbone
 
     def _bn_training(self):
         flags = {m.training for m in self.modules() if isinstance(m, _BN_TYPES)}
