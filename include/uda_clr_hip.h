@@ -101,6 +101,13 @@ int uda_conv_uses_x3(const uda_conv_args_t* a);
 /* bytes of workspace these arguments can make use of (0: none; the conv runs the same without it) */
 uint64_t uda_conv_fwd_workspace_bytes(const uda_conv_args_t* a);
 int uda_conv_fwd(const uda_conv_args_t* a, void* stream);
+/* The launch uda_conv_fwd plans for these arguments, as a short stable text "<family> <tile> ..." with the template variants and
+ * splits: "stream 8x3", "narrow 128x96 pipe xf1", "ws 256x256 k3 xf2", "x3+tail 128x256 k3 full 256 tail 40x6", "heads 128x2";
+ * "none" for arguments it refuses.  The plan is a function of the arguments alone (no pointer is dereferenced, no environment
+ * read), and the only place where a kernel is chosen.  Returns the text's length as snprintf does, -1 without a buffer. */
+int uda_conv_route(const uda_conv_args_t* a, char* buf, int len);
+/* every "<family> <tile>" uda_conv_route / uda_conv_wgrad_route can begin with, one per line */
+const char* uda_conv_route_list(void);
 /* Operand packing for UDA_MFMA_BF16X3: every fp32 value as its three bf16 pieces, out[rows][ceil(C/16)][3][16] (96 contiguous
  * bytes per row and 16-wide block), rows = N*H*W of src, values = the TRANSFORMED ones act(x*scale+shift)*mask*mask_scale, so a
  * tensor is split once however many taps, workgroups or convolutions read it.  Weight rows: src with N = H = 1, W = rows,
@@ -126,6 +133,9 @@ typedef struct uda_wgrad_args {
 uint64_t uda_conv_wgrad_workspace_bytes(int64_t P, int Cout, int Cin, int ksize);
 int uda_conv_wgrad_uses_x3(const uda_wgrad_args_t* a);
 int uda_conv_wgrad(const uda_wgrad_args_t* a, void* stream);
+/* as uda_conv_route: "wgrad 64x64 S=12 red8", "wgrad-ws 256x256 xf1 S=2 red8", "wgrad-x3 128x256 S=12 red8" (S: splits of the
+ * pixel range, red: the wgrad_reduce_kernel variant that sums them) */
+int uda_conv_wgrad_route(const uda_wgrad_args_t* a, char* buf, int len);
 
 /* ---- depthwise 3x3 (mobilenet.py:39,53): stride 1|2, dilation 1|2|4, "pad 0 on a padded input"; C <= 1024 on these
  * kernels, C <= 2048 routed to the channel-blocked ones below.

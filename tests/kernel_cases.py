@@ -8,6 +8,7 @@ import torch
 
 from kernel_spec import SpecKernels
 from uda_clr_amd.acts import ACT_NONE, ACT_RELU, ACT_RELU6, Act, BNRec, round4
+from uda_clr_amd.kernels import UdaSrc
 
 SPEC = SpecKernels()
 _HIP = None
@@ -93,7 +94,41 @@ def make_src(N, H, W, C, g, lazy=True, act=ACT_RELU, mask=False, bn=False, q1=Fa
 
 
 # ------------------------------------------------------------------------------------- cases
-def case_conv(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, bias=False, addend=False, stats=True, seed=0, origin=0, stride=1):
+# Dense cases (conv / dgrad / wgrad) declare with ``route=`` the launch the library must plan for their call (HipKernels.conv_route /
+# wgrad_route: family, tile, template variant, splits).  The labels are the test ids and stay as they were written; where a label's
+# parenthesised remark about tiles or kernels and the route differ, the route is what runs - it is asserted.
+def _declared(route, mfma):
+    """a dense case's declared route: one text, or (f32, bf16x3) where the two MFMA modes differ"""
+    return route if isinstance(route, str) else route[mfma]
+
+
+def _check_route(got, route, mfma):
+    assert got == _declared(route, mfma), "planned route %r, the case declares %r (mfma mode %d)" % (got, _declared(route, mfma), mfma)
+
+
+def plan_route(K, q):
+    """The route of a dense case's call from its recorded shape (``run.plan_query``) alone, without a GPU: stand-in addresses,
+    the row strides of ``padded``."""
+    s = UdaSrc()
+    s.x, s.ldx, s.N, s.H, s.W, s.C = 0x10000, round4(q["C"]) + 4, q["N"], q["H"], q["W"], q["C"]
+    if q["lazy"]:
+        s.scale, s.shift, s.act = 0x20000, 0x30000, ACT_RELU
+    if q["mask"]:
+        s.mask, s.ldm = 0x40000, round4(q["C"])
+    ld = round4(q["Cout"]) + 4
+    if q["kind"] == "wgrad":
+        return K.route(K.wgrad_args(s, q["Cout"], q["k"], q["dil"], q["origin"], q["stride"], 0x50000, ld, 0x60000))
+    return K.route(K.conv_args(s, q["Cout"], q["k"], q["dil"], q["origin"], q["stride"], 0x50000, 0x70000 if q["bias"] else None,
+                               0x80000 if q["addend"] else None, ld if q["addend"] else 0, 0x90000, ld, 0xa0000 if q["stats"] else None))
+
+
+def _query(kind, N, H, W, C, Cout, k, dil, lazy=False, mask=False, bias=False, addend=False, stats=False, origin=0, stride=1):
+    return dict(kind=kind, N=N, H=H, W=W, C=C, Cout=Cout, k=k, dil=dil, lazy=lazy, mask=mask, bias=bias, addend=addend, stats=stats,
+                origin=origin, stride=stride)
+
+
+def case_conv(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, bias=False, addend=False, stats=True, seed=0, origin=0, stride=1, *, route):
+    """route: what HipKernels.conv_route must say about this call (asserted in the run, and without a GPU by test_conv_plan_cpu.py)"""
     def run(dev):
         g = gen(seed)
         src = make_src(N, H, W, Cin, g, lazy, ACT_RELU6 if Cin % 8 else ACT_RELU, mask)
@@ -110,15 +145,18 @@ def case_conv(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, bias=False, add
         st_h = torch.zeros(16, 2, Cout, dtype=torch.float64, device=dev) if stats else None
         wl = K.relayout_ohwi(w.to(dev))
         errs = [rel(wl, SPEC.relayout_ohwi(w))]
-        K.conv(act_to(src, dev), wl, k, dil, out_h, None if b is None else b.to(dev), to_dev(ad, dev), st_h, origin=origin, **kw)
+        args = (act_to(src, dev), wl, k, dil, out_h, None if b is None else b.to(dev), to_dev(ad, dev), st_h)
+        _check_route(K.conv_route(*args, origin=origin, **kw), route, K.mfma)
+        K.conv(*args, origin=origin, **kw)
         errs.append(rel(out_h, out_r))
         if stats:
             errs.append(rel(st_h.sum(0), st_r.sum(0)))
         return max(errs), 2e-5
+    run.plan_query, run.route = _query("conv", N, H, W, Cin, Cout, k, dil, lazy, mask, bias, addend, stats, origin, stride), route
     return run
 
 
-def case_dgrad(N, H, W, Cin, Cout, k, dil, accumulate=False, seed=1):
+def case_dgrad(N, H, W, Cin, Cout, k, dil, accumulate=False, seed=1, *, route):
     """input-gradient of a conv = conv of dy with the dgrad weight layout"""
     def run(dev):
         g = gen(seed)
@@ -138,12 +176,15 @@ def case_dgrad(N, H, W, Cin, Cout, k, dil, accumulate=False, seed=1):
         if accumulate:      # in-place accumulate, as the engine uses it
             out.copy_(adh)
             adh = out
-        K.conv(Act(to_dev(dy, dev), N, H, W), wd, k, dil, out, addend=adh)
+        args = (Act(to_dev(dy, dev), N, H, W), wd, k, dil, out)
+        _check_route(K.conv_route(*args, addend=adh), route, K.mfma)
+        K.conv(*args, addend=adh)
         return max(e0, rel(out, ref)), 2e-5
+    run.plan_query, run.route = _query("conv", N, H, W, Cout, Cin, k, dil, addend=accumulate), route
     return run
 
 
-def case_wgrad(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, seed=2, origin=0, stride=1):
+def case_wgrad(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, seed=2, origin=0, stride=1, *, route):
     def run(dev):
         g = gen(seed)
         src = make_src(N, H, W, Cin, g, lazy, ACT_RELU, mask)
@@ -152,8 +193,12 @@ def case_wgrad(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, seed=2, origin
         kw = {"stride": stride} if stride != 1 else {}
         SPEC.conv_wgrad(src, dy, k, dil, ref, origin=origin, **kw)
         out = torch.empty(Cout, Cin, k, k, device=dev)
-        hip().conv_wgrad(act_to(src, dev), to_dev(dy, dev), k, dil, out, origin=origin, **kw)
+        K = hip()
+        args = (act_to(src, dev), to_dev(dy, dev), k, dil, out)
+        _check_route(K.wgrad_route(*args, origin=origin, **kw), route, K.mfma)
+        K.conv_wgrad(*args, origin=origin, **kw)
         return rel(out, ref), 3e-5
+    run.plan_query, run.route = _query("wgrad", N, H, W, Cin, Cout, k, dil, lazy, mask, origin=origin, stride=stride), route
     return run
 
 
@@ -502,45 +547,45 @@ def case_dropout(P, C, p, seed=9):
 
 CASES = [
     # 1x1 convs of the backbone (narrow N configs, small K, Q1-style sizes)
-    ("conv1x1 16->96 relu6", case_conv(2, 24, 20, 16, 96, 1, 1)),
-    ("conv1x1 96->24 none-lazy", case_conv(2, 17, 13, 96, 24, 1, 1, lazy=False)),
-    ("conv1x1 144->32", case_conv(1, 16, 16, 144, 32, 1, 1)),
-    ("conv1x1 32->192 (128-wide tiles)", case_conv(2, 12, 12, 32, 192, 1, 1)),
-    ("conv1x1 960->320", case_conv(2, 8, 8, 960, 320, 1, 1, stats=True)),
-    ("conv1x1 1280->256 relu", case_conv(2, 8, 8, 1280, 256, 1, 1)),
-    ("conv1x1 305->2 bias mask (C%4!=0)", case_conv(2, 16, 16, 305, 2, 1, 1, mask=True, bias=True, stats=False)),
-    ("conv1x1 256->1 bias mask", case_conv(2, 16, 16, 256, 1, 1, 1, mask=True, bias=True, stats=False)),
-    ("conv1x1 100->2 addend, ragged P (heads kernel, raw operand)", case_conv(2, 17, 13, 100, 2, 1, 1, lazy=False, addend=True, stats=False)),
-    ("conv1x1 68->1 lazy, P < 128 (heads kernel)", case_conv(1, 9, 7, 68, 1, 1, 1, bias=True, stats=False)),
-    ("conv1x1 320->256 P=N (gap branch)", case_conv(4, 1, 1, 320, 256, 1, 1, lazy=False)),
-    ("conv1x1 24->48 addend", case_conv(2, 16, 16, 24, 48, 1, 1, addend=True, stats=False)),
+    ("conv1x1 16->96 relu6", case_conv(2, 24, 20, 16, 96, 1, 1, route="low 64x128 xf1")),
+    ("conv1x1 96->24 none-lazy", case_conv(2, 17, 13, 96, 24, 1, 1, lazy=False, route="low 64x64 xf0")),
+    ("conv1x1 144->32", case_conv(1, 16, 16, 144, 32, 1, 1, route="low 64x64 xf1")),
+    ("conv1x1 32->192 (128-wide tiles)", case_conv(2, 12, 12, 32, 192, 1, 1, route="narrow 128x96 xf1")),
+    ("conv1x1 960->320", case_conv(2, 8, 8, 960, 320, 1, 1, stats=True, route="ws 64x128 k1 xf1")),
+    ("conv1x1 1280->256 relu", case_conv(2, 8, 8, 1280, 256, 1, 1, route=("ws 64x128 k1 xf1", "x3 128x128 k1"))),
+    ("conv1x1 305->2 bias mask (C%4!=0)", case_conv(2, 16, 16, 305, 2, 1, 1, mask=True, bias=True, stats=False, route="heads 128x2")),
+    ("conv1x1 256->1 bias mask", case_conv(2, 16, 16, 256, 1, 1, 1, mask=True, bias=True, stats=False, route="heads 128x1")),
+    ("conv1x1 100->2 addend, ragged P (heads kernel, raw operand)", case_conv(2, 17, 13, 100, 2, 1, 1, lazy=False, addend=True, stats=False, route="heads 128x2")),
+    ("conv1x1 68->1 lazy, P < 128 (heads kernel)", case_conv(1, 9, 7, 68, 1, 1, 1, bias=True, stats=False, route="heads 128x1")),
+    ("conv1x1 320->256 P=N (gap branch)", case_conv(4, 1, 1, 320, 256, 1, 1, lazy=False, route="ws 64x128 k1 xf0")),
+    ("conv1x1 24->48 addend", case_conv(2, 16, 16, 24, 48, 1, 1, addend=True, stats=False, route="low 64x64 xf1")),
     # 3x3 convs
-    ("conv3x3 304->256 p1 mask", case_conv(2, 16, 16, 304, 256, 3, 1, lazy=False)),
-    ("conv3x3 256->256 relu mask", case_conv(2, 16, 12, 256, 256, 3, 1, mask=True)),
-    ("conv3x3 320->256 dil6", case_conv(2, 8, 8, 320, 256, 3, 6, lazy=False)),
-    ("conv3x3 320->256 dil12 (mostly padding)", case_conv(2, 8, 8, 320, 256, 3, 12, lazy=False)),
-    ("conv3x3 64->40 dil2 odd sizes", case_conv(1, 11, 9, 64, 40, 3, 2)),
-    ("conv3x3 256->48 (long K, narrow tile)", case_conv(2, 16, 16, 256, 48, 3, 1, lazy=False)),
-    ("conv3x3 128->64 relu mask stats (long K, narrow tile)", case_conv(2, 12, 12, 128, 64, 3, 1, mask=True)),
-    ("dgrad3x3 48<-256 addend (the decoder's low-level input gradient)", case_dgrad(2, 16, 16, 48, 256, 3, 1, accumulate=True)),
+    ("conv3x3 304->256 p1 mask", case_conv(2, 16, 16, 304, 256, 3, 1, lazy=False, route=("ws 64x128 k3 xf0", "x3 128x128 k3"))),
+    ("conv3x3 256->256 relu mask", case_conv(2, 16, 12, 256, 256, 3, 1, mask=True, route=("ws 64x128 k3 xf2", "x3 128x128 k3"))),
+    ("conv3x3 320->256 dil6", case_conv(2, 8, 8, 320, 256, 3, 6, lazy=False, route=("ws 64x128 k3 xf0", "x3 128x128 k3"))),
+    ("conv3x3 320->256 dil12 (mostly padding)", case_conv(2, 8, 8, 320, 256, 3, 12, lazy=False, route=("ws 64x128 k3 xf0", "x3 128x128 k3"))),
+    ("conv3x3 64->40 dil2 odd sizes", case_conv(1, 11, 9, 64, 40, 3, 2, route="low 64x64 pipe")),
+    ("conv3x3 256->48 (long K, narrow tile)", case_conv(2, 16, 16, 256, 48, 3, 1, lazy=False, route=("low 64x64 pipe", "x3 256x64 k3"))),
+    ("conv3x3 128->64 relu mask stats (long K, narrow tile)", case_conv(2, 12, 12, 128, 64, 3, 1, mask=True, route=("low 64x64 pipe", "x3 256x64 k3"))),
+    ("dgrad3x3 48<-256 addend (the decoder's low-level input gradient)", case_dgrad(2, 16, 16, 48, 256, 3, 1, accumulate=True, route=("low 64x64 pipe", "x3 256x64 k3"))),
     # dgrad through the same kernel
-    ("dgrad1x1 96<-16", case_dgrad(2, 12, 12, 96, 16, 1, 1)),
-    ("dgrad1x1 305<-2", case_dgrad(2, 16, 16, 305, 2, 1, 1)),
-    ("dgrad1x1 256<-1", case_dgrad(2, 16, 16, 256, 1, 1, 1)),
-    ("dgrad3x3 304<-256 accumulate", case_dgrad(2, 12, 12, 304, 256, 3, 1, accumulate=True)),
-    ("dgrad3x3 320<-256 dil6 accumulate", case_dgrad(2, 8, 8, 320, 256, 3, 6, accumulate=True)),
+    ("dgrad1x1 96<-16", case_dgrad(2, 12, 12, 96, 16, 1, 1, route="low 64x128 xf0")),
+    ("dgrad1x1 305<-2", case_dgrad(2, 16, 16, 305, 2, 1, 1, route="narrow 128x160 xf0")),
+    ("dgrad1x1 256<-1", case_dgrad(2, 16, 16, 256, 1, 1, 1, route="narrow 128x128 xf0")),
+    ("dgrad3x3 304<-256 accumulate", case_dgrad(2, 12, 12, 304, 256, 3, 1, accumulate=True, route=("ws 64x128 k3 xf0", "x3+tail 128x128 k3 full 0 tail 9x8"))),
+    ("dgrad3x3 320<-256 dil6 accumulate", case_dgrad(2, 8, 8, 320, 256, 3, 6, accumulate=True, route=("ws 64x128 k3 xf0", "x3+tail 128x128 k3 full 0 tail 3x8"))),
     # wgrad
-    ("wgrad1x1 16->96", case_wgrad(2, 24, 20, 16, 96, 1, 1)),
-    ("wgrad1x1 96->24", case_wgrad(2, 17, 13, 96, 24, 1, 1)),
-    ("wgrad1x1 32->16 (64x64 tiles)", case_wgrad(2, 16, 16, 32, 16, 1, 1)),
-    ("wgrad1x1 960->320", case_wgrad(2, 8, 8, 960, 320, 1, 1)),
-    ("wgrad1x1 305->2 mask", case_wgrad(2, 16, 16, 305, 2, 1, 1, mask=True)),
-    ("wgrad1x1 256->1 mask", case_wgrad(2, 16, 16, 256, 1, 1, 1, mask=True)),
-    ("wgrad1x1 320->256 P=4", case_wgrad(4, 1, 1, 320, 256, 1, 1, lazy=False)),
-    ("wgrad3x3 304->256", case_wgrad(2, 16, 16, 304, 256, 3, 1, lazy=False)),
-    ("wgrad3x3 256->256 mask", case_wgrad(2, 16, 12, 256, 256, 3, 1, mask=True)),
-    ("wgrad3x3 320->256 dil6", case_wgrad(2, 8, 8, 320, 256, 3, 6, lazy=False)),
-    ("wgrad3x3 64->40 dil2", case_wgrad(1, 11, 9, 64, 40, 3, 2)),
+    ("wgrad1x1 16->96", case_wgrad(2, 24, 20, 16, 96, 1, 1, route="wgrad 128x32 S=3 red8")),
+    ("wgrad1x1 96->24", case_wgrad(2, 17, 13, 96, 24, 1, 1, route="wgrad 32x128 S=1 red8")),
+    ("wgrad1x1 32->16 (64x64 tiles)", case_wgrad(2, 16, 16, 32, 16, 1, 1, route="wgrad 64x64 S=2 red8")),
+    ("wgrad1x1 960->320", case_wgrad(2, 8, 8, 960, 320, 1, 1, route="wgrad-ws 128x128 xf1 S=1 red8")),
+    ("wgrad1x1 305->2 mask", case_wgrad(2, 16, 16, 305, 2, 1, 1, mask=True, route="wgrad 32x128 S=2 red8")),
+    ("wgrad1x1 256->1 mask", case_wgrad(2, 16, 16, 256, 1, 1, 1, mask=True, route="wgrad 32x128 S=2 red8")),
+    ("wgrad1x1 320->256 P=4", case_wgrad(4, 1, 1, 320, 256, 1, 1, lazy=False, route="wgrad-ws 128x128 xf0 S=1 red8")),
+    ("wgrad3x3 304->256", case_wgrad(2, 16, 16, 304, 256, 3, 1, lazy=False, route="wgrad-ws 128x128 xf0 S=4 red8")),
+    ("wgrad3x3 256->256 mask", case_wgrad(2, 16, 12, 256, 256, 3, 1, mask=True, route="wgrad-ws 128x128 xf2 S=3 red8")),
+    ("wgrad3x3 320->256 dil6", case_wgrad(2, 8, 8, 320, 256, 3, 6, lazy=False, route="wgrad-ws 128x128 xf0 S=1 red8")),
+    ("wgrad3x3 64->40 dil2", case_wgrad(1, 11, 9, 64, 40, 3, 2, route="wgrad-ws 128x128 xf1 S=1 red8")),
     # depthwise
     ("dw 32 s1 d1 border0", case_dw(2, 16, 16, 32, 1, 1, 0)),
     ("dw 96 s2 d1 border1", case_dw(2, 16, 16, 96, 2, 1, 1)),
@@ -706,10 +751,10 @@ def case_feat4(P, C, seed=14):
 CASES += [
     ("feat dot4/rank4 C=305", case_feat4(3000, 305)),
     # wide warp-specialised tiles (BN = 256 needs >= 512 workgroups: P >= 65536)
-    ("conv3x3 16->256 P=65536 (BN=256 tiles) relu mask", case_conv(4, 128, 128, 16, 256, 3, 1, mask=True)),
-    ("conv1x1 64->200 P=65536 (BN=256 tiles) bias addend", case_conv(4, 128, 128, 64, 200, 1, 1, bias=True, addend=True)),
-    ("dgrad3x3 304<-32 P=65536 accumulate", case_dgrad(4, 128, 128, 304, 32, 3, 1, accumulate=True)),
-    ("wgrad3x3 16->256 P=65536 mask", case_wgrad(4, 128, 128, 16, 256, 3, 1, mask=True)),
+    ("conv3x3 16->256 P=65536 (BN=256 tiles) relu mask", case_conv(4, 128, 128, 16, 256, 3, 1, mask=True, route="narrow 128x128")),
+    ("conv1x1 64->200 P=65536 (BN=256 tiles) bias addend", case_conv(4, 128, 128, 64, 200, 1, 1, bias=True, addend=True, route="narrow 128x128 xf1")),
+    ("dgrad3x3 304<-32 P=65536 accumulate", case_dgrad(4, 128, 128, 304, 32, 3, 1, accumulate=True, route=("ws 128x320 k3 xf0", "x3 256x128 k3"))),
+    ("wgrad3x3 16->256 P=65536 mask", case_wgrad(4, 128, 128, 16, 256, 3, 1, mask=True, route="wgrad-ws 128x128 xf2 S=256 red8")),
     ("seg loss 2x64", case_seg_loss(2, 64)),
     ("seg counts 3x96", case_seg_counts(3, 96)),
     ("proto hard C=305 h=32", case_proto(2, 32, 305, 0)),
@@ -826,31 +871,31 @@ CASES += [
     ("rows stride 2 C=128 8x12", case_rows_stride(1, 8, 12, 128, 2)),
     ("bottleneck tail C=256", case_bottleneck_tail(2, 16, 16, 256)),
     ("bottleneck tail C=2048", case_bottleneck_tail(2, 4, 4, 2048)),
-    ("conv1x1 2048->512 (ResNet layer4)", case_conv(2, 8, 8, 2048, 512, 1, 1)),
-    ("conv3x3 512->512 dil4 (ResNet layer4)", case_conv(2, 8, 8, 512, 512, 3, 4)),
-    ("conv3x3 2048->256 dil6 (ResNet ASPP)", case_conv(2, 8, 8, 2048, 256, 3, 6, lazy=False)),
-    ("dgrad1x1 1024<-256", case_dgrad(2, 8, 8, 1024, 256, 1, 1, accumulate=True)),
-    ("wgrad1x1 1024->2048", case_wgrad(2, 8, 8, 1024, 2048, 1, 1)),
-    ("wgrad3x3 2048->256 dil6", case_wgrad(2, 8, 8, 2048, 256, 3, 6, lazy=False)),
+    ("conv1x1 2048->512 (ResNet layer4)", case_conv(2, 8, 8, 2048, 512, 1, 1, route=("ws 64x128 k1 xf1", "x3 128x128 k1"))),
+    ("conv3x3 512->512 dil4 (ResNet layer4)", case_conv(2, 8, 8, 512, 512, 3, 4, route=("ws 64x128 k3 xf1", "x3 128x128 k3"))),
+    ("conv3x3 2048->256 dil6 (ResNet ASPP)", case_conv(2, 8, 8, 2048, 256, 3, 6, lazy=False, route=("ws 64x128 k3 xf0", "x3 128x128 k3"))),
+    ("dgrad1x1 1024<-256", case_dgrad(2, 8, 8, 1024, 256, 1, 1, accumulate=True, route=("ws 64x128 k1 xf0", "x3 128x128 k1"))),
+    ("wgrad1x1 1024->2048", case_wgrad(2, 8, 8, 1024, 2048, 1, 1, route="wgrad-ws 128x128 xf1 S=1 red8")),
+    ("wgrad3x3 2048->256 dil6", case_wgrad(2, 8, 8, 2048, 256, 3, 6, lazy=False, route="wgrad-ws 128x128 xf0 S=1 red8")),
 ]
 
 # 256-pixel workgroup tiles of the wide-tile kernel (taken when >= 512 of them exist: P >= 131072 at Cout = 256)
 CASES += [
-    ("conv3x3 32->256 P=131580 (256x256 tiles, ragged) relu mask", case_conv(2, 255, 258, 32, 256, 3, 1, mask=True)),
-    ("conv1x1 200->256 P=131072 (256x256 tiles) bias addend", case_conv(2, 256, 256, 200, 256, 1, 1, bias=True, addend=True)),
-    ("conv3x3 24->250 P=131072 dil2 (256x256 tiles) raw", case_conv(2, 256, 256, 24, 250, 3, 2, lazy=False)),
+    ("conv3x3 32->256 P=131580 (256x256 tiles, ragged) relu mask", case_conv(2, 255, 258, 32, 256, 3, 1, mask=True, route=("ws 128x128 k3 xf2", "x3 128x256 k3"))),
+    ("conv1x1 200->256 P=131072 (256x256 tiles) bias addend", case_conv(2, 256, 256, 200, 256, 1, 1, bias=True, addend=True, route="ws 256x256 k1 xf1")),
+    ("conv3x3 24->250 P=131072 dil2 (256x256 tiles) raw", case_conv(2, 256, 256, 24, 250, 3, 2, lazy=False, route="narrow 128x128 pipe")),
 ]
 
 
 # 2x2 taps (the space-to-depth form of the discriminators' 4x4 stride-2 convs, GAN.py:90-101)
 CASES += [
-    ("conv2x2 o0 8->64 (narrow) raw", case_conv(2, 18, 18, 8, 64, 2, 1, lazy=False, origin=0)),
-    ("conv2x2 o0 256->128 (wide)", case_conv(2, 19, 17, 256, 128, 2, 1, lazy=False, origin=0)),
-    ("conv2x2 o1 128->256 (wide, dgrad form) addend", case_conv(2, 19, 17, 128, 256, 2, 1, lazy=False, addend=True, origin=1)),
-    ("conv2x2 o0 2048->1", case_conv(2, 9, 9, 2048, 1, 2, 1, lazy=False, origin=0)),
-    ("wgrad2x2 o0 8->64", case_wgrad(2, 18, 18, 8, 64, 2, 1, lazy=False, origin=0)),
-    ("wgrad2x2 o0 256->128", case_wgrad(2, 19, 17, 256, 128, 2, 1, lazy=False, origin=0)),
-    ("wgrad2x2 o0 2048->1", case_wgrad(2, 9, 9, 2048, 1, 2, 1, lazy=False, origin=0)),
+    ("conv2x2 o0 8->64 (narrow) raw", case_conv(2, 18, 18, 8, 64, 2, 1, lazy=False, origin=0, route="low 64x64")),
+    ("conv2x2 o0 256->128 (wide)", case_conv(2, 19, 17, 256, 128, 2, 1, lazy=False, origin=0, route=("ws 64x128 k3 xf0", "x3 128x128 k3"))),
+    ("conv2x2 o1 128->256 (wide, dgrad form) addend", case_conv(2, 19, 17, 128, 256, 2, 1, lazy=False, addend=True, origin=1, route=("ws 64x128 k3 xf0", "x3 128x128 k3"))),
+    ("conv2x2 o0 2048->1", case_conv(2, 9, 9, 2048, 1, 2, 1, lazy=False, origin=0, route="low 64x64 pipe")),
+    ("wgrad2x2 o0 8->64", case_wgrad(2, 18, 18, 8, 64, 2, 1, lazy=False, origin=0, route="wgrad 64x64 S=2 red8")),
+    ("wgrad2x2 o0 256->128", case_wgrad(2, 19, 17, 256, 128, 2, 1, lazy=False, origin=0, route="wgrad-ws 128x128 xf0 S=5 red8")),
+    ("wgrad2x2 o0 2048->1", case_wgrad(2, 9, 9, 2048, 1, 2, 1, lazy=False, origin=0, route="wgrad 32x128 S=1 red8")),
 ]
 
 
@@ -944,81 +989,100 @@ CASES += [("relayout s2d 64<-2", case_relayout_s2d(64, 2)), ("relayout s2d 128<-
 
 # 256 x 256 weight-gradient tiles (Cout >= 192, J >= 256, >= 4096 pixel chunks = 131072 pixels)
 CASES += [
-    ("wgrad3x3 32->256 P=131072 (256x256 tiles)", case_wgrad(2, 256, 256, 32, 256, 3, 1, lazy=False)),
-    ("wgrad3x3 40->200 P=131325 mask (256x256 tiles, ragged)", case_wgrad(1, 255, 515, 40, 200, 3, 2, mask=True)),
-    ("wgrad1x1 300->320 P=131072 lazy (256x256 tiles)", case_wgrad(2, 256, 256, 300, 320, 1, 1)),
-    ("wgrad2x2 o0 64->256 P=131841 (256x256 tiles)", case_wgrad(1, 363, 363, 64, 256, 2, 1, lazy=False)),
+    ("wgrad3x3 32->256 P=131072 (256x256 tiles)", case_wgrad(2, 256, 256, 32, 256, 3, 1, lazy=False, route=("wgrad-ws 256x256 xf0 S=256 red8", "wgrad-x3 256x256 S=256 red8"))),
+    ("wgrad3x3 40->200 P=131325 mask (256x256 tiles, ragged)", case_wgrad(1, 255, 515, 40, 200, 3, 2, mask=True, route="wgrad-ws 256x256 xf2 S=242 red8")),
+    ("wgrad1x1 300->320 P=131072 lazy (256x256 tiles)", case_wgrad(2, 256, 256, 300, 320, 1, 1, route="wgrad-ws 256x256 xf1 S=128 red8")),
+    ("wgrad2x2 o0 64->256 P=131841 (256x256 tiles)", case_wgrad(1, 363, 363, 64, 256, 2, 1, lazy=False, route=("wgrad-ws 256x256 xf0 S=243 red8", "wgrad-x3 256x256 S=243 red8"))),
 ]
 
 # weight gradients the bf16x3 mode routes to its own kernel (Cin % 16 == 0, Cout >= 96, k >= 2, P >= 4096; transposed LDS reads)
 CASES += [
-    ("wgrad3x3 256->256 P=4608 mask (x3 128 tiles)", case_wgrad(2, 48, 48, 256, 256, 3, 1, mask=True)),
-    ("wgrad3x3 304->256 P=8192 (x3 128 tiles)", case_wgrad(2, 64, 64, 304, 256, 3, 1, lazy=False)),
-    ("wgrad3x3 320->256 dil12 P=4608 (x3)", case_wgrad(2, 48, 48, 320, 256, 3, 12)),
-    ("wgrad3x3 48->100 P=4700 ragged (x3)", case_wgrad(2, 50, 47, 48, 100, 3, 1)),
-    ("wgrad2x2 o0 256->128 P=8978 (x3)", case_wgrad(2, 67, 67, 256, 128, 2, 1, lazy=False, origin=0)),
-    ("wgrad2x2 o0 64->200 P=70225 (x3 256 tiles, ragged)", case_wgrad(1, 265, 265, 64, 200, 2, 1, lazy=False, origin=0)),
-    ("wgrad1x1 256->2304 P=4608 (x3, tap GEMM of the re-associated decoder conv)", case_wgrad(2, 48, 48, 256, 2304, 1, 1, lazy=False)),
-    ("wgrad2x2 o0 1024->512 P=9248 (x3 256 tiles on few pixels)", case_wgrad(2, 68, 68, 1024, 512, 2, 1, lazy=False, origin=0)),
+    ("wgrad3x3 256->256 P=4608 mask (x3 128 tiles)", case_wgrad(2, 48, 48, 256, 256, 3, 1, mask=True, route=("wgrad-ws 128x128 xf2 S=24 red8", "wgrad-x3 128x256 S=24 red8"))),
+    ("wgrad3x3 304->256 P=8192 (x3 128 tiles)", case_wgrad(2, 64, 64, 304, 256, 3, 1, lazy=False, route=("wgrad-ws 128x128 xf0 S=22 red8", "wgrad-x3 256x256 S=22 red8"))),
+    ("wgrad3x3 320->256 dil12 P=4608 (x3)", case_wgrad(2, 48, 48, 320, 256, 3, 12, route=("wgrad-ws 128x128 xf1 S=21 red8", "wgrad-x3 128x256 S=21 red8"))),
+    ("wgrad3x3 48->100 P=4700 ragged (x3)", case_wgrad(2, 50, 47, 48, 100, 3, 1, route=("wgrad-ws 128x128 xf1 S=30 red8", "wgrad-x3 128x256 S=30 red8"))),
+    ("wgrad2x2 o0 256->128 P=8978 (x3)", case_wgrad(2, 67, 67, 256, 128, 2, 1, lazy=False, origin=0, route=("wgrad-ws 128x128 xf0 S=57 red8", "wgrad-x3 128x256 S=57 red8"))),
+    ("wgrad2x2 o0 64->200 P=70225 (x3 256 tiles, ragged)", case_wgrad(1, 265, 265, 64, 200, 2, 1, lazy=False, origin=0, route=("wgrad-ws 128x128 xf0 S=244 red8", "wgrad-x3 256x256 S=244 red8"))),
+    ("wgrad1x1 256->2304 P=4608 (x3, tap GEMM of the re-associated decoder conv)", case_wgrad(2, 48, 48, 256, 2304, 1, 1, lazy=False, route=("wgrad-ws 128x128 xf0 S=24 red8", "wgrad-x3 128x256 S=24 red8"))),
+    ("wgrad2x2 o0 1024->512 P=9248 (x3 256 tiles on few pixels)", case_wgrad(2, 68, 68, 1024, 512, 2, 1, lazy=False, origin=0, route=("wgrad-ws 128x128 xf0 S=8 red8", "wgrad-x3 256x256 S=8 red8"))),
 ]
 # bf16x3: the last, partly filled round of tiles split over K (no statistics epilogue; fp32 partial tiles + x3_tail_reduce_kernel)
 CASES += [
-    ("conv3x3 64->128 P=37965 bias addend, no stats (x3 tail split, ragged rows)", case_conv(1, 195, 195 - 0, 64, 128, 3, 1, bias=True, addend=True, stats=False)),
-    ("conv2x2 o1 256->250 P=38000 raw, no stats (x3 tail split, ragged columns)", case_conv(1, 200, 190, 256, 250, 2, 1, lazy=False, stats=False, origin=1)),
-    ("conv1x1 256->2304 P=4864 no stats (x3 tail split, wide 1x1)", case_conv(1, 38, 128, 256, 2304, 1, 1, lazy=False, stats=False)),
-    ("dgrad3x3 304<-256 P=37888 accumulate (x3 tail split)", case_dgrad(2, 148, 128, 304, 256, 3, 1, accumulate=True)),
+    ("conv3x3 64->128 P=37965 bias addend, no stats (x3 tail split, ragged rows)", case_conv(1, 195, 195 - 0, 64, 128, 3, 1, bias=True, addend=True, stats=False, route=("ws 128x128 k3 xf1", "x3 256x128 k3"))),
+    ("conv2x2 o1 256->250 P=38000 raw, no stats (x3 tail split, ragged columns)", case_conv(1, 200, 190, 256, 250, 2, 1, lazy=False, stats=False, origin=1, route=("ws 128x128 k3 xf0", "x3 128x128 k3"))),
+    ("conv1x1 256->2304 P=4864 no stats (x3 tail split, wide 1x1)", case_conv(1, 38, 128, 256, 2304, 1, 1, lazy=False, stats=False, route=("ws 128x192 k1 xf0", "x3 128x128 k1"))),
+    ("dgrad3x3 304<-256 P=37888 accumulate (x3 tail split)", case_dgrad(2, 148, 128, 304, 256, 3, 1, accumulate=True, route=("ws 128x128 k3 xf0", "x3 256x128 k3"))),
 ]
 # bf16x3 routes added with the 256 x 64 tile and the wide 1x1 route
 CASES += [
-    ("conv1x1 256->2304 stats (x3 wide 1x1)", case_conv(2, 40, 36, 256, 2304, 1, 1, lazy=False)),
-    ("conv1x1 144->1030 relu6 ragged (x3 wide 1x1)", case_conv(1, 37, 29, 144, 1030, 1, 1)),
-    ("conv3x3 256->48 P=2442 ragged (x3 256 x 64 tile)", case_conv(2, 33, 37, 256, 48, 3, 1, lazy=False)),
-    ("conv3x3 160->60 dil2 mask stats (x3 256 x 64 tile)", case_conv(1, 45, 41, 160, 60, 3, 2, mask=True)),
-    ("conv2x2 o1 256->56 addend (x3 256 x 64 tile)", case_conv(2, 30, 30, 256, 56, 2, 1, lazy=False, addend=True, origin=1)),
+    ("conv1x1 256->2304 stats (x3 wide 1x1)", case_conv(2, 40, 36, 256, 2304, 1, 1, lazy=False, route=("ws 128x256 k1 xf0", "x3 128x256 k1"))),
+    ("conv1x1 144->1030 relu6 ragged (x3 wide 1x1)", case_conv(1, 37, 29, 144, 1030, 1, 1, route="narrow 128x96 xf1")),
+    ("conv3x3 256->48 P=2442 ragged (x3 256 x 64 tile)", case_conv(2, 33, 37, 256, 48, 3, 1, lazy=False, route=("low 64x64 pipe", "x3 256x64 k3"))),
+    ("conv3x3 160->60 dil2 mask stats (x3 256 x 64 tile)", case_conv(1, 45, 41, 160, 60, 3, 2, mask=True, route=("low 64x64 pipe", "x3 256x64 k3"))),
+    ("conv2x2 o1 256->56 addend (x3 256 x 64 tile)", case_conv(2, 30, 30, 256, 56, 2, 1, lazy=False, addend=True, origin=1, route="low 64x64 pipe")),
 ]
 # narrow 1x1 convs: 64-pixel tiles when 128-pixel tiles would leave half of the CUs without a workgroup (the 32x32-map layers at
 # B = 16: P = 16384), and the 128-pixel tiles of the same routes on more pixels (round 3)
 CASES += [
-    ("conv1x1 384->64 P=16384 relu6 stats (64-pixel tiles)", case_conv(16, 32, 32, 384, 64, 1, 1)),
-    ("conv1x1 576->96 P=16384 addend no stats (64-pixel tiles, 128 columns)", case_conv(16, 32, 32, 576, 96, 1, 1, addend=True, stats=False)),
-    ("conv1x1 192->30 P=5655 ragged mask bias (64-pixel tiles)", case_conv(3, 65, 29, 192, 30, 1, 1, mask=True, bias=True)),
-    ("dgrad1x1 64<-384 P=16384 accumulate (64-pixel tiles)", case_dgrad(16, 32, 32, 64, 384, 1, 1, accumulate=True)),
-    ("conv1x1 384->64 P=32000 ragged stats (128-pixel tiles)", case_conv(2, 125, 128, 384, 64, 1, 1)),
-    ("conv1x1 96->24 P=40000 raw addend (128-pixel tiles)", case_conv(1, 200, 200, 96, 24, 1, 1, lazy=False, addend=True)),
-    ("conv1x1 64->96 P=28900 relu6 mask (128-pixel tiles)", case_conv(1, 170, 170, 64, 96, 1, 1, mask=True)),
+    ("conv1x1 384->64 P=16384 relu6 stats (64-pixel tiles)", case_conv(16, 32, 32, 384, 64, 1, 1, route="low 64x64 pipe xf1")),
+    ("conv1x1 576->96 P=16384 addend no stats (64-pixel tiles, 128 columns)", case_conv(16, 32, 32, 576, 96, 1, 1, addend=True, stats=False, route="low 64x128 pipe xf1")),
+    ("conv1x1 192->30 P=5655 ragged mask bias (64-pixel tiles)", case_conv(3, 65, 29, 192, 30, 1, 1, mask=True, bias=True, route="low 64x64 pipe")),
+    ("dgrad1x1 64<-384 P=16384 accumulate (64-pixel tiles)", case_dgrad(16, 32, 32, 64, 384, 1, 1, accumulate=True, route="low 64x64 pipe xf0")),
+    ("conv1x1 384->64 P=32000 ragged stats (128-pixel tiles)", case_conv(2, 125, 128, 384, 64, 1, 1, route="narrow 128x64 pipe xf1")),
+    ("conv1x1 96->24 P=40000 raw addend (128-pixel tiles)", case_conv(1, 200, 200, 96, 24, 1, 1, lazy=False, addend=True, route="narrow 128x32 xf0")),
+    ("conv1x1 64->96 P=28900 relu6 mask (128-pixel tiles)", case_conv(1, 170, 170, 64, 96, 1, 1, mask=True, route="narrow 128x96")),
 ]
 # bf16x3 on long-K 1x1 convs towards >= 256 outputs (ResNet-101's bottleneck convs on the 32x32 maps, round 3)
 CASES += [
-    ("conv1x1 1024->256 P=8192 raw stats (x3 long-K 1x1)", case_conv(8, 32, 32, 1024, 256, 1, 1, lazy=False)),
-    ("conv1x1 2048->512 P=2312 relu ragged (x3 long-K 1x1)", case_conv(2, 34, 34, 2048, 512, 1, 1)),
-    ("dgrad1x1 1024<-256 P=8192 accumulate (x3 wide 1x1)", case_dgrad(8, 32, 32, 1024, 256, 1, 1, accumulate=True)),
-    ("wgrad1x1 1024->256 P=8192 raw (x3 long-K 1x1)", case_wgrad(8, 32, 32, 1024, 256, 1, 1, lazy=False)),
-    ("wgrad1x1 2048->512 P=4624 relu (x3 long-K 1x1)", case_wgrad(4, 34, 34, 2048, 512, 1, 1)),
+    ("conv1x1 1024->256 P=8192 raw stats (x3 long-K 1x1)", case_conv(8, 32, 32, 1024, 256, 1, 1, lazy=False, route=("ws 64x128 k1 xf0", "x3 128x128 k1"))),
+    ("conv1x1 2048->512 P=2312 relu ragged (x3 long-K 1x1)", case_conv(2, 34, 34, 2048, 512, 1, 1, route=("ws 64x128 k1 xf1", "x3 128x128 k1"))),
+    ("dgrad1x1 1024<-256 P=8192 accumulate (x3 wide 1x1)", case_dgrad(8, 32, 32, 1024, 256, 1, 1, accumulate=True, route=("ws 128x256 k1 xf0", "x3 128x256 k1"))),
+    ("wgrad1x1 1024->256 P=8192 raw (x3 long-K 1x1)", case_wgrad(8, 32, 32, 1024, 256, 1, 1, lazy=False, route=("wgrad-ws 128x128 xf0 S=64 red8", "wgrad-x3 256x256 S=64 red8"))),
+    ("wgrad1x1 2048->512 P=4624 relu (x3 long-K 1x1)", case_wgrad(4, 34, 34, 2048, 512, 1, 1, route=("wgrad-ws 128x128 xf1 S=15 red8", "wgrad-x3 128x256 S=15 red8"))),
 ]
 # short-K 1x1 convs over >= 32768 pixels: the barrier-free one-wave-per-32-pixels kernel (conv1x1_stream_kernel)
 CASES += [
-    ("conv1x1 16->96 P=33800 relu6 stats (stream kernel, ragged last tile)", case_conv(2, 130, 130, 16, 96, 1, 1)),
-    ("conv1x1 16->90 P=33800 raw addend no stats (stream kernel, ragged columns)", case_conv(2, 130, 130, 16, 90, 1, 1, lazy=False, addend=True, stats=False)),
-    ("conv1x1 24->144 P=40000 raw addend (stream kernel, two column groups)", case_conv(1, 200, 200, 24, 144, 1, 1, lazy=False, addend=True)),
-    ("conv1x1 24->48 P=36100 relu stats (stream kernel)", case_conv(1, 190, 190, 24, 48, 1, 1)),
-    ("conv1x1 32->192 P=36300 relu stats addend (stream kernel, two column groups)", case_conv(3, 110, 110, 32, 192, 1, 1, addend=True)),
-    ("conv1x1 32->130 P=32768 raw (stream kernel, second group ragged)", case_conv(2, 128, 128, 32, 130, 1, 1, lazy=False)),
-    ("conv1x1 32->192 P=262144 relu6 stats (stream kernel, two column groups)", case_conv(4, 256, 256, 32, 192, 1, 1)),
-    ("conv1x1 16->32 P=33800 raw addend (stream kernel, one block)", case_conv(2, 130, 130, 16, 32, 1, 1, lazy=False, addend=True, stats=False)),
-    ("conv1x1 24->96 P=40000 raw addend (stream kernel, three blocks)", case_conv(1, 200, 200, 24, 96, 1, 1, lazy=False, addend=True, stats=False)),
+    ("conv1x1 16->96 P=33800 relu6 stats (stream kernel, ragged last tile)", case_conv(2, 130, 130, 16, 96, 1, 1, route="stream 8x3")),
+    ("conv1x1 16->90 P=33800 raw addend no stats (stream kernel, ragged columns)", case_conv(2, 130, 130, 16, 90, 1, 1, lazy=False, addend=True, stats=False, route="stream 8x3")),
+    ("conv1x1 24->144 P=40000 raw addend (stream kernel, two column groups)", case_conv(1, 200, 200, 24, 144, 1, 1, lazy=False, addend=True, route="stream 12x5")),
+    ("conv1x1 24->48 P=36100 relu stats (stream kernel)", case_conv(1, 190, 190, 24, 48, 1, 1, route="stream 12x2")),
+    ("conv1x1 32->192 P=36300 relu stats addend (stream kernel, two column groups)", case_conv(3, 110, 110, 32, 192, 1, 1, addend=True, route="narrow 128x96 xf1")),
+    ("conv1x1 32->130 P=32768 raw (stream kernel, second group ragged)", case_conv(2, 128, 128, 32, 130, 1, 1, lazy=False, route="narrow 128x160 xf0")),
+    ("conv1x1 32->192 P=262144 relu6 stats (stream kernel, two column groups)", case_conv(4, 256, 256, 32, 192, 1, 1, route="stream 16x3")),
+    ("conv1x1 16->32 P=33800 raw addend (stream kernel, one block)", case_conv(2, 130, 130, 16, 32, 1, 1, lazy=False, addend=True, stats=False, route="stream 8x1")),
+    ("conv1x1 24->96 P=40000 raw addend (stream kernel, three blocks)", case_conv(1, 200, 200, 24, 96, 1, 1, lazy=False, addend=True, stats=False, route="stream 12x3")),
 ]
 # stride 2 on the wide tiles: the loaders walk the strided output grid (ResNet-101 layer2.0 / layer3.0 conv2, resnet.py:66, and their
 # weight gradients; the 1x1 form is the shortcut conv, resnet.py:93)
 CASES += [
-    ("conv3x3 s2 128->128 65x67 relu stats (strided grid, odd sizes)", case_conv(2, 65, 67, 128, 128, 3, 1, stride=2)),
-    ("conv3x3 s2 256->256 P=8192 raw addend no stats (tail split)", case_conv(8, 64, 64, 256, 256, 3, 1, lazy=False, addend=True, stats=False, stride=2)),
-    ("conv3x3 s2 dil2 160->200 mask ragged", case_conv(3, 41, 38, 160, 200, 3, 2, mask=True, stride=2)),
-    ("conv1x1 s2 256->512 33x40 relu bias", case_conv(2, 33, 40, 256, 512, 1, 1, bias=True, stride=2)),
-    ("conv1x1 s2 512->1024 raw (x3 wide 1x1)", case_conv(2, 64, 64, 512, 1024, 1, 1, lazy=False, stride=2)),
-    ("wgrad3x3 s2 128->128 65x67 relu", case_wgrad(2, 65, 67, 128, 128, 3, 1, stride=2)),
-    ("wgrad3x3 s2 256->256 P=16384 raw (x3)", case_wgrad(4, 128, 128, 256, 256, 3, 1, lazy=False, stride=2)),
-    ("wgrad3x3 s2 128->128 41 images of 20x20 (rows shorter than a chunk)", case_wgrad(41, 20, 20, 128, 128, 3, 1, stride=2)),
-    ("wgrad1x1 s2 256->512 33x40 mask", case_wgrad(2, 33, 40, 256, 512, 1, 1, mask=True, stride=2)),
+    ("conv3x3 s2 128->128 65x67 relu stats (strided grid, odd sizes)", case_conv(2, 65, 67, 128, 128, 3, 1, stride=2, route=("ws 64x128 k3 xf1", "x3 128x128 k3"))),
+    ("conv3x3 s2 256->256 P=8192 raw addend no stats (tail split)", case_conv(8, 64, 64, 256, 256, 3, 1, lazy=False, addend=True, stats=False, stride=2, route=("ws 64x128 k3 xf0", "x3+tail 128x256 k3 full 0 tail 64x4"))),
+    ("conv3x3 s2 dil2 160->200 mask ragged", case_conv(3, 41, 38, 160, 200, 3, 2, mask=True, stride=2, route=("ws 64x128 k3 xf2", "x3 128x128 k3"))),
+    ("conv1x1 s2 256->512 33x40 relu bias", case_conv(2, 33, 40, 256, 512, 1, 1, bias=True, stride=2, route="ws 64x128 k1 xf1")),
+    ("conv1x1 s2 512->1024 raw (x3 wide 1x1)", case_conv(2, 64, 64, 512, 1024, 1, 1, lazy=False, stride=2, route=("ws 64x128 k1 xf0", "x3 128x128 k1"))),
+    ("wgrad3x3 s2 128->128 65x67 relu", case_wgrad(2, 65, 67, 128, 128, 3, 1, stride=2, route="wgrad-ws 128x128 xf1 S=15 red8")),
+    ("wgrad3x3 s2 256->256 P=16384 raw (x3)", case_wgrad(4, 128, 128, 256, 256, 3, 1, lazy=False, stride=2, route=("wgrad-ws 128x128 xf0 S=27 red8", "wgrad-x3 256x256 S=27 red8"))),
+    ("wgrad3x3 s2 128->128 41 images of 20x20 (rows shorter than a chunk)", case_wgrad(41, 20, 20, 128, 128, 3, 1, stride=2, route=("wgrad-ws 128x128 xf1 S=26 red8", "wgrad-x3 128x256 S=26 red8"))),
+    ("wgrad1x1 s2 256->512 33x40 mask", case_wgrad(2, 33, 40, 256, 512, 1, 1, mask=True, stride=2, route="wgrad-ws 128x128 xf2 S=5 red8")),
+]
+
+
+# Routes that no case above takes (tests/test_conv_plan_cpu.py holds every entry of uda_conv_route_list() against the declared
+# routes): the bf16x3 K-split of the last round of tiles on each tile shape - alone, after full rounds, with ragged rows and
+# columns, on a long-K 1x1 conv and as an accumulating input gradient - and the remaining tiles of the other families
+CASES += [
+    ("conv3x3 256->256 P=1152 bias addend, no stats", case_conv(2, 24, 24, 256, 256, 3, 1, bias=True, addend=True, stats=False, route=("ws 64x128 k3 xf1", "x3+tail 128x128 k3 full 0 tail 18x8"))),
+    ("conv2x2 o1 384->250 P=1147 raw, no stats, ragged rows and columns", case_conv(1, 37, 31, 384, 250, 2, 1, lazy=False, stats=False, origin=1, route=("ws 64x128 k3 xf0", "x3+tail 128x128 k3 full 0 tail 18x8"))),
+    ("conv1x1 1536->300 P=1147 relu, no stats", case_conv(1, 37, 31, 1536, 300, 1, 1, stats=False, route=("ws 64x128 k1 xf1", "x3+tail 128x128 k1 full 0 tail 27x8"))),
+    ("dgrad3x3 304<-256 P=1152 accumulate", case_dgrad(2, 24, 24, 304, 256, 3, 1, accumulate=True, route=("ws 64x128 k3 xf0", "x3+tail 128x128 k3 full 0 tail 27x8"))),
+    ("conv3x3 256->256 P=16637 raw, no stats", case_conv(1, 131, 127, 256, 256, 3, 1, lazy=False, stats=False, route=("ws 128x256 k3 xf0", "x3+tail 128x128 k3 full 256 tail 4x8"))),
+    ("conv2x2 o1 384->300 P=3811 raw addend, no stats", case_conv(1, 37, 103, 384, 300, 2, 1, lazy=False, addend=True, stats=False, origin=1, route=("ws 64x128 k3 xf0", "x3+tail 256x128 k3 full 0 tail 45x5"))),
+    ("conv2x2 o1 384->500 P=37201 raw, no stats", case_conv(1, 193, 193, 384, 500, 2, 1, lazy=False, stats=False, origin=1, route=("ws 128x128 k3 xf0", "x3+tail 256x256 k3 full 256 tail 36x7"))),
+    ("conv2x2 o0 64->160 P=49729 relu stats", case_conv(1, 223, 223, 64, 160, 2, 1, route=("ws 128x192 k3 xf1", "x3 256x256 k3"))),
+    ("conv2x2 o0 256->1 bias raw, no stats", case_conv(2, 9, 7, 256, 1, 2, 1, lazy=False, bias=True, stats=False, route="cout1 4x1")),
+    ("conv1x1 196->160 P=12285 relu6 stats", case_conv(3, 65, 63, 196, 160, 1, 1, route="few 64x192 pipe xf1")),
+    ("conv1x1 200->300 P=12285 relu mask addend", case_conv(3, 65, 63, 200, 300, 1, 1, mask=True, addend=True, route="few 64x320 pipe")),
+    ("wgrad1x1 128->1024 P=4096 raw", case_wgrad(1, 64, 64, 128, 1024, 1, 1, lazy=False, route=("wgrad-ws 128x128 xf0 S=32 red8", "wgrad-x3 128x128 S=32 red8"))),
 ]
 
 

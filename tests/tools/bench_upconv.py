@@ -1,6 +1,6 @@
 """Timing of uda_upconv_fwd (decoder conv0's interpolation pass, upconv.hip) at the step's shapes.  (TEST TOOL, GPU box.)
 
-    python tests/tools/bench_upconv.py        # UDA_UPCONV_TILE=0 selects the strip kernel"""
+    python tests/tools/bench_upconv.py"""
 import os
 import sys
 

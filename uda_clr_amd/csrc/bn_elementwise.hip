@@ -10,7 +10,6 @@
 // Reductions are two-stage and deterministic: per-workgroup fp32 partials, then an fp64 sum.
 // Thread mapping: cg = tid % G float4 channel groups, pl = tid / G pixel lanes (coalesced rows).
 #include "common.h"
-#include <stdlib.h>
 
 int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hipStream_t st);
 
@@ -450,8 +449,7 @@ static inline int red_nwg(int64_t P, int C, int iter) {
     return uda_cdiv(P, (int64_t)PP * iter);
 }
 static inline bool red_short(int64_t P, int C) {
-    static const int thr = getenv("UDA_RED_SHORT_WGS") ? atoi(getenv("UDA_RED_SHORT_WGS")) : 2048;
-    return (int64_t)red_nwg(P, C, RED_ITER) * uda_cdiv(C, RED_CBLK_SUM) < thr;
+    return (int64_t)red_nwg(P, C, RED_ITER) * uda_cdiv(C, RED_CBLK_SUM) < 2048;
 }
 
 extern "C" int uda_colstats_window(const float* x, int64_t ldx, int64_t P, int C, int nq, double* out, int out_C, void* stream);

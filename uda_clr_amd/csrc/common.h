@@ -52,6 +52,18 @@ static inline int uda_device_slot() {
     return d % UDA_MAX_DEVICES;
 }
 
+// Raise the dynamic-LDS limit of kernel FN to `bytes`, once per device; up to the 64 KiB default there is nothing to raise.
+template <auto FN>
+static inline int uda_reserve_lds(size_t bytes, const char* who) {
+    static bool done_dev[UDA_MAX_DEVICES] = {};
+    bool& done = done_dev[uda_device_slot()];
+    if (done || bytes <= 64 * 1024) return 0;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(FN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return uda_set_error("%s: cannot reserve %zu B of LDS: %s", who, bytes, hipGetErrorString(e));
+    done = true;
+    return 0;
+}
+
 // Blocks b and b+8 share an XCD (round-robin dispatch).  Give every XCD one contiguous chunk of
 // the logical tile order so neighbouring tiles (shared halo rows / shared weight panels) hit the
 // same 4 MiB L2.  Bijective for any nwg (cdna_hip_programming.md, 8-phase template notes).

@@ -7,7 +7,6 @@
 // Thread mapping (shared by the depthwise kernels): channel group cg = tid % G (G = C/4 float4
 // groups), pixel lane pl = tid / G; a workgroup walks ITER strips of PP = 256/G consecutive
 // output pixels, so the 64 lanes of a wave read G*16 contiguous bytes per pixel.
-#include <stdlib.h>
 #include "common.h"
 
 int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hipStream_t st);
@@ -712,8 +711,7 @@ static int dw_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, i
     if (cb) return dwb_fwd(a, st);
     const int64_t Pout = (int64_t)src->N * a.Ho * a.Wo;
     const int nwg = uda_cdiv(Pout, dw_pixels_per_wg(src->C, DW_ITER_FWD));     // (C <= 1024 here: at least one pixel per workgroup)
-    static const bool flat = getenv("UDA_DW_FLAT") != nullptr;      // diagnostics: the untiled kernel
-    if (!flat && dil <= 2) return stride == 1 ? launch_dw_tiled<1, 8, 16>(a, st) : launch_dw_tiled<2, 8, 8>(a, st);
+    if (dil <= 2) return stride == 1 ? launch_dw_tiled<1, 8, 16>(a, st) : launch_dw_tiled<2, 8, 8>(a, st);
     hipLaunchKernelGGL(dwconv_fwd_kernel, dim3(nwg), dim3(256), 0, st, a);
     UDA_LAUNCH_CHECK("dwconv_fwd");
     return 0;
@@ -777,8 +775,7 @@ static int dw_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int str
     UDA_REQUIRE(workspace && workspace_bytes >= uda_dwconv_workspace_bytes(Pout, C), "uda_dwconv_wgrad: workspace too small");
     if (cb) return dwb_wgrad(a, reinterpret_cast<double*>(workspace), dw, st);
     const int nwg = uda_cdiv(Pout, dw_pixels_per_wg(C, DW_ITER_RED));
-    static const bool flat = getenv("UDA_DW_FLAT") != nullptr;
-    if (!flat && dil <= 2) {
+    if (dil <= 2) {
         double* slot_sums = reinterpret_cast<double*>(workspace);
         return stride == 1 ? launch_dw_wgrad_tiled<1, 8, 16>(a, slot_sums, dw, st) : launch_dw_wgrad_tiled<2, 8, 8>(a, slot_sums, dw, st);
     }

@@ -35,11 +35,6 @@ struct WgradKArgs {
 #define IG_BK 32
 #define IG_LD 36
 #define WG_BKP 32
-
-int launch_conv_ws(ConvKArgs& k, int64_t P, hipStream_t st);          // 128 x {128,256} tiles
-int launch_wgrad_ws(WgradKArgs& k, int S, bool big, hipStream_t st);  // 128 x 128 or 256 x 256 tiles
-bool conv_x3_eligible(const ConvKArgs& k);
-bool wgrad_x3_eligible(int Cin, int Cout, int ksize, int64_t P);
-int launch_wgrad_x3(const WgradKArgs& k, int64_t P, int S_max, const void* x3_src, const void* x3_dy, hipStream_t st, int& S_out);   // bf16x3 weight gradient
-int launch_conv_x3(ConvKArgs& k, int64_t P, const void* x3_src, const void* x3_w, hipStream_t st, void* ws, uint64_t ws_bytes);
-uint64_t conv_x3_workspace_bytes(const ConvKArgs& k, int64_t P);      // bytes the tail split of this conv wants (0: none)   // bf16x3 forward / dgrad (igemm_x3.hip)
+#define WGN_BKP 64        // pixels per K-chunk of the narrow (HBM-bound) weight-gradient kernel: one barrier pair per 64 pixels
+#define X3_BK 16          // K depth of a bf16x3 chunk
+#define X3_ROW 56         // bf16 per staged row: 3 pieces x 16 + 8 pad = 112 B: a row's 96 B arrive as they lie in the packed operand

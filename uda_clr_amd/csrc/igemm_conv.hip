@@ -22,8 +22,7 @@
 //   tile and spatially adjacent pixel tiles share one XCD's L2.
 #include <algorithm>
 #include "common.h"
-#include <stdlib.h>
-#include "igemm_args.h"
+#include "conv_plan.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -384,13 +383,6 @@ int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hi
     return 0;
 }
 
-// floats per weight row of a conv with C input channels and ksize x ksize taps
-static inline int uda_k_row(int C, int ksize) {
-    const int Kc = ((C + 3) / 4) * 4;
-    if (ksize == 1 || Kc < IG_BK) return ksize * ksize * Kc;      // fewer than 32 channels: tap-major, unpadded
-    return ((Kc + IG_BK - 1) / IG_BK) * ksize * ksize * IG_BK;
-}
-
 static int check_src(const uda_src_t& s, const char* who) {
     UDA_REQUIRE(s.x && uda_aligned16(s.x), "%s: src.x must be 16-byte aligned", who);
     UDA_REQUIRE(s.ldx % 4 == 0 && s.ldx >= ((s.C + 3) / 4) * 4, "%s: src.ldx=%lld must be a multiple of 4 and >= round4(C=%d)",
@@ -656,105 +648,63 @@ static int launch_stream(ConvKArgs& k, int64_t P, hipStream_t st) {
     return 0;
 }
 
-// the short-K streaming form applies: 1x1, stride 1, K = Cin in {16, 24, 32}, no keep-mask, no bias, >= 32768 pixels, aligned rows
-static int conv_stream_shape(const uda_conv_args_t* a, int64_t P) {
-    static const int on = getenv("UDA_CONV_STREAM") ? atoi(getenv("UDA_CONV_STREAM")) : 1;      // A/B switch
-    if (!on || a->ksize != 1 || (a->stride > 1) || a->src.mask || a->bias || P < 32768) return 0;
-    if (!uda_aligned16(a->src.x) || a->src.ldx % 4 || (a->src.C != 16 && a->src.C != 24 && a->src.C != 32)) return 0;
-    if (P * a->ldy >= ((int64_t)1 << 29) || (a->addend && P * a->ld_add >= ((int64_t)1 << 29))) return 0;
-    const int C = a->src.C, Cout = a->Cout;
-    if (C == 16 && Cout <= 32) return 5;
-    if (C == 16 && Cout <= 96) return 1;
-    if (C == 24 && Cout <= 64) return 2;
-    if (C == 24 && Cout <= 96) return 6;
-    if (C == 24 && Cout <= 160) return 3;
-    if (C == 32 && Cout > 96 && Cout <= 192 && P >= 262144) return 4;      // (at 65536 pixels, and towards few columns, the tiled kernel is as fast or faster)
-    return 0;
-}
-
 template <int TM, int TN, int WM, int WN, bool PIPE, int XF>
-static int launch_conv_one(ConvKArgs& k, hipStream_t st, size_t lds) {
-    auto fn = igemm_conv_kernel<TM, TN, WM, WN, PIPE, XF>;
-    if (lds > 64 * 1024) {                                  // beyond the default dynamic-LDS limit: raise it once per device
-        static bool configured_dev[UDA_MAX_DEVICES] = {};
-        bool& configured = configured_dev[uda_device_slot()];
-        if (!configured) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return uda_set_error("igemm_conv: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-            configured = true;
-        }
-    }
-    hipLaunchKernelGGL(fn, dim3(k.nMt * k.nNt), dim3(256), lds, st, k);
+static int launch_conv_one(ConvKArgs& k, const ConvPlan& p, hipStream_t st) {
+    static_assert(2 * igc_tile_bytes(32 * TM * WM, 32 * TN * WN) <= 160 * 1024, "two tile images must fit the LDS");
+    if (int e = uda_reserve_lds<igemm_conv_kernel<TM, TN, WM, WN, PIPE, XF>>(p.lds, "igemm_conv")) return e;
+    k.nMt = uda_cdiv(p.P, 32 * TM * WM);
+    k.nNt = uda_cdiv(k.Cout, 32 * TN * WN);
+    hipLaunchKernelGGL((igemm_conv_kernel<TM, TN, WM, WN, PIPE, XF>), dim3(p.grid), dim3(256), p.lds, st, k);
     UDA_LAUNCH_CHECK("igemm_conv");
     return 0;
 }
 
 template <int TM, int TN, int WM, int WN>
-static int launch_conv_xf(ConvKArgs& k, int xf, hipStream_t st, bool pipe, size_t tile_bytes) {
-    if (pipe) return xf == 0 ? launch_conv_one<TM, TN, WM, WN, true, 0>(k, st, 2 * tile_bytes) : launch_conv_one<TM, TN, WM, WN, true, 1>(k, st, 2 * tile_bytes);
-    return xf == 0 ? launch_conv_one<TM, TN, WM, WN, false, 0>(k, st, tile_bytes) : launch_conv_one<TM, TN, WM, WN, false, 1>(k, st, tile_bytes);
+static int launch_conv(ConvKArgs& k, const ConvPlan& p, hipStream_t st) {
+    if (p.pipe) return p.xf == 0 ? launch_conv_one<TM, TN, WM, WN, true, 0>(k, p, st) : p.xf == 1 ? launch_conv_one<TM, TN, WM, WN, true, 1>(k, p, st)
+                                                                                                 : launch_conv_one<TM, TN, WM, WN, true, -1>(k, p, st);
+    return p.xf == 0 ? launch_conv_one<TM, TN, WM, WN, false, 0>(k, p, st) : p.xf == 1 ? launch_conv_one<TM, TN, WM, WN, false, 1>(k, p, st)
+                                                                                       : launch_conv_one<TM, TN, WM, WN, false, -1>(k, p, st);
 }
 
-template <int TM, int TN, int WM, int WN>
-static int launch_conv(ConvKArgs& k, int64_t P, hipStream_t st) {
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    static_assert(BM == 128 || BM == 64, "tiles of 128 or 64 pixels");
-    constexpr size_t tile_bytes = (size_t)(BM + BN) * IG_LD * sizeof(float);
-    static_assert(2 * tile_bytes <= 160 * 1024, "two tile images must fit the LDS");
-    k.nMt = uda_cdiv(P, BM);
-    k.nNt = uda_cdiv(k.Cout, BN);
-    // long K: the pipelined form (two tile images, loads two chunks ahead); short K keeps the lean one (more workgroups per CU)
-    static const int pipe_min = getenv("UDA_CONV_PIPE_MIN_K") ? atoi(getenv("UDA_CONV_PIPE_MIN_K")) : 192;
-    // 1x1 without a keep-mask: the lean loader (XF 0: also no transform and no activation - gradient matrices; XF 1: the rest)
-    static const int lean = getenv("UDA_CONV_LEAN") ? atoi(getenv("UDA_CONV_LEAN")) : 1;       // A/B switch
-    const int xf = (lean && k.ksize == 1 && !k.src.mask) ? ((!k.src.scale && k.src.act == ACT_NONE) ? 0 : 1) : -1;
-    if (xf >= 0) return launch_conv_xf<TM, TN, WM, WN>(k, xf, st, k.Ktot >= pipe_min, tile_bytes);
-    if (k.Ktot >= pipe_min) {
-        auto fn = igemm_conv_kernel<TM, TN, WM, WN, true>;
-        if (2 * tile_bytes > 64 * 1024) {                   // beyond the default dynamic-LDS limit: raise it once per device
-            static bool configured_dev[UDA_MAX_DEVICES] = {};
-            bool& configured = configured_dev[uda_device_slot()];
-            if (!configured) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * tile_bytes));
-                if (e != hipSuccess) return uda_set_error("igemm_conv: cannot reserve %zu B of LDS: %s", 2 * tile_bytes, hipGetErrorString(e));
-                configured = true;
-            }
+// CF_FEW / CF_LOW / CF_NARROW: the planned tile of igemm_conv_kernel
+static int launch_conv_tile(ConvKArgs& k, const ConvPlan& p, hipStream_t st) {
+    if (p.bm == 64) {
+        switch (p.bn) {
+            case 64: return launch_conv<1, 1, 2, 2>(k, p, st);
+            case 128: return launch_conv<1, 2, 2, 2>(k, p, st);
+            case 192: return launch_conv<1, 3, 2, 2>(k, p, st);
+            default: return launch_conv<1, 5, 2, 2>(k, p, st);
         }
-        hipLaunchKernelGGL(fn, dim3(k.nMt * k.nNt), dim3(256), 2 * tile_bytes, st, k);
     }
-    else hipLaunchKernelGGL((igemm_conv_kernel<TM, TN, WM, WN, false>), dim3(k.nMt * k.nNt), dim3(256), tile_bytes, st, k);
-    UDA_LAUNCH_CHECK("igemm_conv");
-    return 0;
+    switch (p.bn) {
+        case 32: return launch_conv<1, 1, 4, 1>(k, p, st);
+        case 64: return launch_conv<1, 2, 4, 1>(k, p, st);
+        case 96: return launch_conv<1, 3, 4, 1>(k, p, st);
+        case 128: return launch_conv<2, 2, 2, 2>(k, p, st);
+        default: return launch_conv<1, 5, 4, 1>(k, p, st);
+    }
 }
 
-// true when uda_conv_fwd routes these arguments to the wide-tile (MFMA-bound) kernels
-static bool conv_is_wide(const uda_conv_args_t* a, int Kc, int Ktot) {
-    if (a->Cout == 1 && !a->src.scale && !a->src.mask && a->src.act == ACT_NONE && !a->stats && Ktot >= 1024) return false;
-    if (a->Cout <= 2 && a->ksize == 1 && !a->stats && Kc >= 64 && Kc <= 2048) return false;
-    if (a->Cout <= 96)      // narrow outputs: only the bf16x3 mode has a 64-column wide tile (long-K multi-tap convs)
-        return a->mfma == UDA_MFMA_BF16X3 && a->ksize >= 2 && a->Cout >= 40 && a->Cout <= 64 && Kc >= 128 && Ktot >= 1024;
-    if (Ktot <= 192 || (a->ksize >= 2 && Kc < IG_BK)) return false;
-    return true;
+static int launch_stream_shape(ConvKArgs& k, const ConvPlan& p, hipStream_t st) {
+    switch (p.bm * 10 + p.bn) {
+        case 81: return launch_stream<8, 1>(k, p.P, st);
+        case 83: return launch_stream<8, 3>(k, p.P, st);
+        case 122: return launch_stream<12, 2>(k, p.P, st);
+        case 123: return launch_stream<12, 3>(k, p.P, st);
+        case 125: return launch_stream<12, 5>(k, p.P, st);      // 144 columns in one group of five blocks
+        default: return launch_stream<16, 3>(k, p.P, st);       // two column groups of 96
+    }
 }
 
 /* 1 when uda_conv_fwd will run these arguments on the bf16x3 wide-tile kernel, i.e. needs a->x3_src / a->x3_w (uda_x3_pack) */
 extern "C" int uda_conv_uses_x3(const uda_conv_args_t* a) {
-    if (!a || a->mfma != UDA_MFMA_BF16X3 || a->ksize < 1 || a->ksize > 3) return 0;
-    const int Kc = ((a->src.C + 3) / 4) * 4, Ktot = uda_k_row(a->src.C, a->ksize);
-    ConvKArgs k;
-    k.Kc = Kc; k.ksize = a->ksize; k.Cout = a->Cout;
-    return conv_is_wide(a, Kc, Ktot) && conv_x3_eligible(k) ? 1 : 0;
+    if (!conv_plannable(a)) return 0;
+    const int f = conv_plan(a).family;
+    return f == CF_X3 || f == CF_X3_TAIL;
 }
 
-extern "C" uint64_t uda_conv_fwd_workspace_bytes(const uda_conv_args_t* a) {
-    if (!uda_conv_uses_x3(a)) return 0;
-    ConvKArgs k;
-    k.src = a->src; k.Cout = a->Cout; k.ksize = a->ksize; k.stats = a->stats;
-    k.Kc = ((a->src.C + 3) / 4) * 4;
-    k.Ktot = uda_k_row(a->src.C, a->ksize);
-    const int sd = a->stride <= 1 ? 1 : a->stride;
-    return conv_x3_workspace_bytes(k, (int64_t)a->src.N * ((a->src.H - 1) / sd + 1) * ((a->src.W - 1) / sd + 1));
-}
+extern "C" uint64_t uda_conv_fwd_workspace_bytes(const uda_conv_args_t* a) { return conv_plannable(a) ? conv_plan(a).ws_bytes : 0; }
 
 extern "C" int uda_conv_fwd(const uda_conv_args_t* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -765,22 +715,22 @@ extern "C" int uda_conv_fwd(const uda_conv_args_t* a, void* stream) {
     UDA_REQUIRE(a->Cout > 0 && a->dil >= 1 && a->y && a->w, "uda_conv_fwd: bad args");
     UDA_REQUIRE(uda_aligned16(a->w), "uda_conv_fwd: weights must be 16-byte aligned");
     UDA_REQUIRE(a->ldy >= a->Cout, "uda_conv_fwd: ldy < Cout");
-    // stride 2 (resnet.py:66 conv2 of the first bottleneck of layer2 / layer3, :93 their 1x1 shortcut): output pixel (n, oh, ow) is
-    // centred on input pixel (n, 2 oh, 2 ow); P counts OUTPUT rows from here on
-    const int sd = a->stride <= 1 ? 1 : a->stride;
-    UDA_REQUIRE(sd <= 2, "uda_conv_fwd: stride must be 1 or 2");
-    const int Ho = (a->src.H - 1) / sd + 1, Wo = (a->src.W - 1) / sd + 1;
-    const int64_t Pin = (int64_t)a->src.N * a->src.H * a->src.W, P = (int64_t)a->src.N * Ho * Wo;
+    UDA_REQUIRE(a->stride <= 2, "uda_conv_fwd: stride must be 1 or 2");
+    const int64_t Pin = (int64_t)a->src.N * a->src.H * a->src.W;
+    UDA_REQUIRE((Pin + 128) * a->src.ldx < ((int64_t)1 << 29) && (Pin + 128) * (a->src.mask ? a->src.ldm : 1) < ((int64_t)1 << 31),
+                "uda_conv_fwd: operand too large for 32-bit byte offsets (P * ld must stay below 2^29 elements)");
+    const ConvPlan p = conv_plan(a);
+    if (p.error) return uda_set_error("%s", p.error);
     ConvKArgs k;
     k.src = a->src;
-    k.stride = sd; k.Ho = Ho; k.Wo = Wo;
+    k.stride = p.stride; k.Ho = p.Ho; k.Wo = p.Wo;
     k.w = a->w;
     k.Cout = a->Cout;
     k.ksize = a->ksize;
     k.dil = a->dil;
     k.cen = a->ksize == 3 ? 1 : (a->ksize == 2 ? a->origin : 0);
-    k.Kc = ((a->src.C + 3) / 4) * 4;
-    k.Ktot = uda_k_row(a->src.C, a->ksize);
+    k.Kc = p.Kc;
+    k.Ktot = p.Ktot;
     k.bias = a->bias;
     k.addend = a->addend;
     k.ld_add = a->ld_add;
@@ -789,68 +739,22 @@ extern "C" int uda_conv_fwd(const uda_conv_args_t* a, void* stream) {
     k.stats = a->stats;
     k.debug = 0;
     k.x3 = a->mfma == UDA_MFMA_BF16X3;
-    UDA_REQUIRE((Pin + 128) * a->src.ldx < ((int64_t)1 << 29) && (Pin + 128) * (a->src.mask ? a->src.ldm : 1) < ((int64_t)1 << 31),
-                "uda_conv_fwd: operand too large for 32-bit byte offsets (P * ld must stay below 2^29 elements)");
-    int e;
-    switch (conv_stream_shape(a, P)) {
-        case 1: return launch_stream<8, 3>(k, P, st);
-        case 2: return launch_stream<12, 2>(k, P, st);
-        case 3: return launch_stream<12, 5>(k, P, st);      // 144 columns in one group of five blocks
-        case 4: return launch_stream<16, 3>(k, P, st);      // two column groups of 96
-        case 5: return launch_stream<8, 1>(k, P, st);
-        case 6: return launch_stream<12, 3>(k, P, st);
-        default: break;
+    switch (p.family) {
+        case CF_STREAM: return launch_stream_shape(k, p, st);
+        case CF_COUT1:
+            hipLaunchKernelGGL(conv_cout1_kernel, dim3(p.grid), dim3(256), 0, st, k);
+            UDA_LAUNCH_CHECK("conv_cout1");
+            return 0;
+        case CF_HEADS:
+            if (p.bn == 1) hipLaunchKernelGGL(conv_heads_kernel<1>, dim3(p.grid), dim3(256), p.lds, st, k);
+            else hipLaunchKernelGGL(conv_heads_kernel<2>, dim3(p.grid), dim3(256), p.lds, st, k);
+            UDA_LAUNCH_CHECK("conv_heads");
+            return 0;
+        case CF_FEW: case CF_LOW: case CF_NARROW: return launch_conv_tile(k, p, st);
+        case CF_WS: return launch_conv_ws(k, p, st);
+        case CF_X3: case CF_X3_TAIL: return launch_conv_x3(k, p, a->x3_src, a->x3_w, a->workspace, st);
+        default: return uda_set_error("uda_conv_fwd: no kernel planned");
     }
-    if (sd != 1) {       // only the wide-tile kernels walk a strided output grid
-        const bool wide = conv_is_wide(a, k.Kc, k.Ktot) && a->Cout > 96 && !(k.Ktot <= 192 || (a->ksize >= 2 && k.Kc < IG_BK));
-        UDA_REQUIRE(wide, "uda_conv_fwd: stride 2 is built on the wide-tile kernels only (Cout > 96, K > 192)");
-        return (k.x3 && conv_x3_eligible(k)) ? launch_conv_x3(k, P, a->x3_src, a->x3_w, st, a->workspace, a->workspace_bytes) : launch_conv_ws(k, P, st);
-    }
-    if (a->Cout == 1 && !a->src.scale && !a->src.mask && a->src.act == ACT_NONE && !a->stats && k.Ktot >= 1024) {
-        hipLaunchKernelGGL(conv_cout1_kernel, dim3(uda_cdiv(P, 4)), dim3(256), 0, st, k);
-        UDA_LAUNCH_CHECK("conv_cout1");
-        return 0;
-    }
-    if (a->Cout <= 2 && a->ksize == 1 && !a->stats && k.Kc >= 64 && k.Kc <= 2048) {
-        const size_t lds = (size_t)(2 + a->Cout) * k.Kc * sizeof(float);
-        if (a->Cout == 1) hipLaunchKernelGGL(conv_heads_kernel<1>, dim3(uda_cdiv(P, 128)), dim3(256), lds, st, k);
-        else hipLaunchKernelGGL(conv_heads_kernel<2>, dim3(uda_cdiv(P, 128)), dim3(256), lds, st, k);
-        UDA_LAUNCH_CHECK("conv_heads");
-        return 0;
-    }
-    // few pixels (the 32x32-map layers at B = 16: 128 tiles of 128 pixels for 256 CUs): 64-pixel tiles, twice the workgroups
-    static const int low_env = getenv("UDA_CONV_LOW") ? atoi(getenv("UDA_CONV_LOW")) : 1;
-    const bool low = low_env && P > 64 && uda_cdiv(P, 128) * uda_cdiv(a->Cout, a->Cout <= 64 ? 64 : 128) <= 192;
-    // few pixels, wide output, long K (the project convs of the 32x32-map layers: 960 -> 160, 576 -> 160, 960 -> 320 at P = 16384): the
-    // 128 x 128 wide tiles pad 160 columns to 256 and give one workgroup per CU; 64-pixel tiles of 192 or 320 columns give the same 256
-    // workgroups with 17 % / no padding
-    static const int few_env = getenv("UDA_CONV_FEW") ? atoi(getenv("UDA_CONV_FEW")) : 1;
-    int few_w = 0;
-    if (few_env && P > 64 && uda_cdiv(P, 128) <= 192 && a->Cout <= 320 && k.Ktot <= 1024) {      // (MobileNetV2's shapes; ResNet-101's wider / longer
-        const int c192 = uda_cdiv(a->Cout, 192) * 192, c320 = uda_cdiv(a->Cout, 320) * 320;       // 1x1 convs stay on the wide-tile kernels: measured)
-        const int64_t t192 = uda_cdiv(P, 64) * (c192 / 192), t320 = uda_cdiv(P, 64) * (c320 / 320);
-        if (c192 <= c320 && t192 >= 192 && t192 <= 512) few_w = 192;
-        else if (t320 >= 192 && t320 <= 512) few_w = 320;
-    }
-    const bool few = few_w != 0;
-    if (uda_conv_uses_x3(a)) e = launch_conv_x3(k, P, a->x3_src, a->x3_w, st, a->workspace, a->workspace_bytes);
-    else if (few && k.Ktot > 192 && a->ksize == 1 && a->Cout > 128 && few_w == 192) e = launch_conv<1, 3, 2, 2>(k, P, st);
-    else if (few && k.Ktot > 192 && a->ksize == 1 && a->Cout > 128 && few_w == 320) e = launch_conv<1, 5, 2, 2>(k, P, st);
-    else if (low && a->Cout <= 64) e = launch_conv<1, 1, 2, 2>(k, P, st);
-    else if (low && a->Cout <= 128 && (k.Ktot <= 192 || a->Cout <= 96 || (a->ksize >= 2 && k.Kc < IG_BK))) e = launch_conv<1, 2, 2, 2>(k, P, st);
-    else if (a->Cout <= 32) e = launch_conv<1, 1, 4, 1>(k, P, st);
-    else if (a->Cout <= 64) e = launch_conv<1, 2, 4, 1>(k, P, st);
-    else if (a->Cout <= 96) e = launch_conv<1, 3, 4, 1>(k, P, st);
-    else if (k.Ktot <= 192 || (a->ksize >= 2 && k.Kc < IG_BK)) {     // (the wide-tile kernel only walks the tap-chunked K order)
-        // short K (the backbone's expand convs): output-bound; pick the tile width that wastes the fewest columns
-        // (Cout = 144 -> one 160-wide tile instead of two 128-wide ones, 576 -> six 96-wide tiles, ...)
-        const int w96 = uda_cdiv(a->Cout, 96) * 96, w128 = uda_cdiv(a->Cout, 128) * 128, w160 = uda_cdiv(a->Cout, 160) * 160;
-        if (w160 <= w128 && w160 <= w96) e = launch_conv<1, 5, 4, 1>(k, P, st);
-        else if (w128 <= w96) e = launch_conv<2, 2, 2, 2>(k, P, st);
-        else e = launch_conv<1, 3, 4, 1>(k, P, st);
-    }
-    else e = (k.x3 && conv_x3_eligible(k)) ? launch_conv_x3(k, P, a->x3_src, a->x3_w, st, a->workspace, a->workspace_bytes) : launch_conv_ws(k, P, st);
-    return e;
 }
 
 // ==========================================================================================
@@ -859,8 +763,6 @@ extern "C" int uda_conv_fwd(const uda_conv_args_t* a, void* stream) {
 // of 32 consecutive dwords.  The pixel range is split over blockIdx.y; every split writes its
 // own fp32 slab and a second kernel sums the slabs (bitwise reproducible, no float atomics).
 
-// pixels per K-chunk of the narrow (HBM-bound) weight-gradient kernel: one barrier pair per 64 pixels
-#define WGN_BKP 64
 
 template <int TM, int TN, int WM, int WN>
 __global__ __launch_bounds__(256) void igemm_wgrad_kernel(WgradKArgs a) {
@@ -1067,49 +969,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
 }
 
-struct WgradPlan {
-    int bm, bn, nCot, nJt, S, cps, nchunks;
-};
-
-static WgradPlan wgrad_plan(int64_t P, int Cout, int Cin, int ksize) {
-    WgradPlan p;
-    const int Kc = ((Cin + 3) / 4) * 4, J = ksize * ksize * Kc;
-    const int cm = Cout <= 32 ? 32 : (Cout <= 64 ? 64 : 128);
-    const int cn = J <= 32 ? 32 : (J <= 64 ? 64 : 128);
-    const bool big = Cout >= 192 && J >= 256 && uda_cdiv(P, WG_BKP) >= 4096;      // (measured: a loss below ~100k pixels)
-    if (big) { p.bm = 256; p.bn = 256; }
-    else if (cm == 128 && cn == 32) { p.bm = 128; p.bn = 32; }
-    else if (cm == 32 && cn == 128) { p.bm = 32; p.bn = 128; }
-    else if (cm <= 64 && cn <= 64) { p.bm = 64; p.bn = 64; }
-    else { p.bm = 128; p.bn = 128; }
-    p.nCot = uda_cdiv(Cout, p.bm);
-    p.nJt = uda_cdiv(J, p.bn);
-    p.nchunks = uda_cdiv(P, ((p.bm == 128 && p.bn == 128) || p.bm == 256) ? WG_BKP : WGN_BKP);
-    int S = (p.bm == 256 ? 512 : 1024) / (p.nCot * p.nJt);      // 256 x 256 tiles: one workgroup per CU, two rounds
-    if (S > p.nchunks / 4) S = p.nchunks / 4;
-    if (S < 1) S = 1;
-    // up to 256 slabs; up to 1024 for a tiny weight (one or two tiles over a million pixels: the backbone's first blocks, the decoder's
-    // 24 -> 48 conv): with 256 workgroups each walks thousands of pixels at one chunk's load latency per chunk, and its slabs are small
-    const int scap = (int64_t)Cout * J <= 8192 ? 1024 : 256;
-    if (S > scap) S = scap;
-    p.cps = uda_cdiv(p.nchunks, S);
-    p.S = uda_cdiv(p.nchunks, p.cps);
-    return p;
-}
-
-extern "C" uint64_t uda_conv_wgrad_workspace_bytes(int64_t P, int Cout, int Cin, int ksize) {
-    const WgradPlan p = wgrad_plan(P, Cout, Cin, ksize);
-    const int Kc = ((Cin + 3) / 4) * 4;
-    return (uint64_t)p.S * Cout * ksize * ksize * Kc * sizeof(float);
-}
+extern "C" uint64_t uda_conv_wgrad_workspace_bytes(int64_t P, int Cout, int Cin, int ksize) { return wgrad_plan(P, Cout, Cin, ksize).ws_bytes; }
 
 extern "C" int uda_conv_wgrad_uses_x3(const uda_wgrad_args_t* a) {
-    if (!a || a->mfma != UDA_MFMA_BF16X3 || a->ksize < 1 || a->ksize > 3) return 0;
-    const int sd = a->stride <= 1 ? 1 : a->stride;
-    const int64_t P = (int64_t)a->src.N * ((a->src.H - 1) / sd + 1) * ((a->src.W - 1) / sd + 1);      // pixels of dy
-    const WgradPlan p = wgrad_plan(P, a->Cout, a->src.C, a->ksize);
-    const bool wide = p.bm == 256 || (p.bm == 128 && p.bn == 128);
-    return wide && wgrad_x3_eligible(a->src.C, a->Cout, a->ksize, P) ? 1 : 0;
+    return a && a->ksize >= 1 && a->ksize <= 3 && wgrad_plan(a).family == CF_WGRAD_X3 ? 1 : 0;
 }
 
 extern "C" int uda_conv_wgrad(const uda_wgrad_args_t* a, void* stream) {
@@ -1120,51 +983,108 @@ extern "C" int uda_conv_wgrad(const uda_wgrad_args_t* a, void* stream) {
     UDA_REQUIRE(a->ksize != 2 || a->origin == 0 || a->origin == 1, "uda_conv_wgrad: origin must be 0 or 1 for ksize 2");
     UDA_REQUIRE(a->dy && uda_aligned16(a->dy) && a->lddy % 4 == 0 && a->lddy >= ((a->Cout + 3) / 4) * 4,
                 "uda_conv_wgrad: dy must be 16-byte aligned with lddy %% 4 == 0 and >= round4(Cout)");
-    // stride 2: dy lives on the output grid, its pixel (n, oh, ow) pairs with source pixel (n, 2 oh, 2 ow); P = pixels of dy
-    const int sd = a->stride <= 1 ? 1 : a->stride;
-    UDA_REQUIRE(sd <= 2, "uda_conv_wgrad: stride must be 1 or 2");
-    const int Ho = (a->src.H - 1) / sd + 1, Wo = (a->src.W - 1) / sd + 1;
-    const int64_t P = (int64_t)a->src.N * Ho * Wo;
-    const WgradPlan p = wgrad_plan(P, a->Cout, a->src.C, a->ksize);
-    UDA_REQUIRE(a->workspace && a->workspace_bytes >= uda_conv_wgrad_workspace_bytes(P, a->Cout, a->src.C, a->ksize),
-                "uda_conv_wgrad: workspace too small");
-    UDA_REQUIRE(sd == 1 || p.bm == 256 || (p.bm == 128 && p.bn == 128),
-                "uda_conv_wgrad: stride 2 is built on the wide-tile kernels only (Cout > 64, K > 64)");
+    UDA_REQUIRE(a->stride <= 2, "uda_conv_wgrad: stride must be 1 or 2");
+    const WgradPlan p = wgrad_plan(a);
+    UDA_REQUIRE(a->workspace && a->workspace_bytes >= p.ws_bytes, "uda_conv_wgrad: workspace too small");
+    if (p.error) return uda_set_error("%s", p.error);
     WgradKArgs k;
     k.src = a->src;
-    k.stride = sd; k.Ho = Ho; k.Wo = Wo;
+    k.stride = p.stride; k.Ho = p.Ho; k.Wo = p.Wo;
     k.dy = a->dy;
     k.lddy = a->lddy;
     k.Cout = a->Cout;
     k.ksize = a->ksize;
     k.dil = a->dil;
     k.cen = a->ksize == 3 ? 1 : (a->ksize == 2 ? a->origin : 0);
-    k.Kc = ((a->src.C + 3) / 4) * 4;
-    k.Jtot = a->ksize * a->ksize * k.Kc;
+    k.Kc = p.Kc;
+    k.Jtot = p.Jtot;
     k.slab = a->workspace;
     k.nCot = p.nCot;
     k.nJt = p.nJt;
     k.chunks_per_split = p.cps;
     k.nchunks = p.nchunks;
-    dim3 grid(p.nCot * p.nJt, p.S);
-    int S_used = p.S;
-    if (uda_conv_wgrad_uses_x3(a)) { if (int e = launch_wgrad_x3(k, P, p.S, a->x3_src, a->x3_dy, st, S_used)) return e; }
-    else if (p.bm == 256) { if (int e = launch_wgrad_ws(k, p.S, true, st)) return e; }
-    else if (p.bm == 128 && p.bn == 128) { if (int e = launch_wgrad_ws(k, p.S, false, st)) return e; }
-    else if (p.bm == 64) hipLaunchKernelGGL((igemm_wgrad_kernel<1, 1, 2, 2>), grid, dim3(256), 0, st, k);
-    else if (p.bm == 128) hipLaunchKernelGGL((igemm_wgrad_kernel<1, 1, 4, 1>), grid, dim3(256), 0, st, k);
-    else hipLaunchKernelGGL((igemm_wgrad_kernel<1, 1, 1, 4>), grid, dim3(256), 0, st, k);
-    UDA_LAUNCH_CHECK("igemm_wgrad");
+    const dim3 grid(p.nCot * p.nJt, p.S);
+    switch (p.family) {
+        case CF_WGRAD_X3: if (int e = launch_wgrad_x3(k, p, a->x3_src, a->x3_dy, st)) return e; break;
+        case CF_WGRAD_WS: if (int e = launch_wgrad_ws(k, p, st)) return e; break;
+        default:
+            if (p.bm == 64) hipLaunchKernelGGL((igemm_wgrad_kernel<1, 1, 2, 2>), grid, dim3(256), 0, st, k);
+            else if (p.bm == 128) hipLaunchKernelGGL((igemm_wgrad_kernel<1, 1, 4, 1>), grid, dim3(256), 0, st, k);
+            else hipLaunchKernelGGL((igemm_wgrad_kernel<1, 1, 1, 4>), grid, dim3(256), 0, st, k);
+            UDA_LAUNCH_CHECK("igemm_wgrad");
+    }
     const int T = a->ksize * a->ksize;
     const int64_t total = (int64_t)a->Cout * T * a->src.C;
-    if (S_used > 256)
+    if (p.red_q == 64)
         hipLaunchKernelGGL(wgrad_reduce_kernel<64>, dim3(uda_cdiv(total, 4) > 4096 ? 4096 : uda_cdiv(total, 4)), dim3(256), 0, st,
-                           k.slab, S_used, a->Cout, a->src.C, T, k.Kc, a->dw);
+                           k.slab, p.S, a->Cout, a->src.C, T, k.Kc, a->dw);
     else
         hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3(uda_cdiv(total, 32) > 4096 ? 4096 : uda_cdiv(total, 32)), dim3(256), 0, st,
-                           k.slab, S_used, a->Cout, a->src.C, T, k.Kc, a->dw);
+                           k.slab, p.S, a->Cout, a->src.C, T, k.Kc, a->dw);
     UDA_LAUNCH_CHECK("wgrad_reduce");
     return 0;
+}
+
+// ==========================================================================================
+// Routes: the plan as a short stable text, for tests and tools (one row per family; the tiles each can choose)
+struct RouteRow {
+    int family;
+    const char* name;
+    int ntiles;
+    int tile[6][2];
+};
+static const RouteRow ROUTES[CF_COUNT] = {
+    {CF_NONE, "none", 0, {}},
+    {CF_STREAM, "stream", 6, {{8, 1}, {8, 3}, {12, 2}, {12, 3}, {12, 5}, {16, 3}}},
+    {CF_COUT1, "cout1", 1, {{4, 1}}},
+    {CF_HEADS, "heads", 2, {{128, 1}, {128, 2}}},
+    {CF_FEW, "few", 2, {{64, 192}, {64, 320}}},
+    {CF_LOW, "low", 2, {{64, 64}, {64, 128}}},
+    {CF_NARROW, "narrow", 5, {{128, 32}, {128, 64}, {128, 96}, {128, 128}, {128, 160}}},
+    {CF_WS, "ws", 6, {{64, 128}, {128, 128}, {128, 192}, {128, 256}, {128, 320}, {256, 256}}},
+    {CF_X3, "x3", 5, {{256, 64}, {256, 256}, {128, 256}, {256, 128}, {128, 128}}},
+    {CF_X3_TAIL, "x3+tail", 4, {{256, 256}, {128, 256}, {256, 128}, {128, 128}}},
+    {CF_WGRAD, "wgrad", 3, {{64, 64}, {128, 32}, {32, 128}}},
+    {CF_WGRAD_WS, "wgrad-ws", 2, {{128, 128}, {256, 256}}},
+    {CF_WGRAD_X3, "wgrad-x3", 3, {{256, 256}, {128, 256}, {128, 128}}},
+};
+
+/* "<family> <tile>" + the template variants and splits, e.g. "narrow 128x96 pipe xf1", "ws 256x256 k3 xf2", "x3+tail 128x256 k3 full 256 tail 40x6";
+ * "none" for arguments uda_conv_fwd refuses.  Returns the text's length (as snprintf), -1 without a buffer. */
+extern "C" int uda_conv_route(const uda_conv_args_t* a, char* buf, int len) {
+    if (!buf || len < 1) return -1;
+    if (!conv_plannable(a)) return snprintf(buf, len, "%s", ROUTES[CF_NONE].name);
+    const ConvPlan p = conv_plan(a);
+    if (p.error || p.family == CF_NONE) return snprintf(buf, len, "%s", ROUTES[CF_NONE].name);
+    int n = snprintf(buf, len, "%s %dx%d", ROUTES[p.family].name, p.bm, p.bn);
+    auto more = [&](const char* fmt, auto... v) { if (n < len) n += snprintf(buf + n, len - n, fmt, v...); };
+    if (p.family == CF_WS || p.family == CF_X3 || p.family == CF_X3_TAIL) more(" k%d", p.ks);
+    if (p.pipe) more("%s", " pipe");
+    if (p.xf >= 0) more(" xf%d", p.xf);
+    if (p.family == CF_X3_TAIL) more(" full %lld tail %lldx%d", (long long)p.full, (long long)p.tail, p.ksplit);
+    return n;
+}
+
+/* e.g. "wgrad 64x64 S=12 red8", "wgrad-ws 256x256 xf1 S=32 red8", "wgrad-x3 128x256 S=12 red8" */
+extern "C" int uda_conv_wgrad_route(const uda_wgrad_args_t* a, char* buf, int len) {
+    if (!buf || len < 1) return -1;
+    if (!a || a->ksize < 1 || a->ksize > 3) return snprintf(buf, len, "%s", ROUTES[CF_NONE].name);
+    const WgradPlan p = wgrad_plan(a);
+    if (p.error) return snprintf(buf, len, "%s", ROUTES[CF_NONE].name);
+    if (p.family == CF_WGRAD_WS) return snprintf(buf, len, "%s %dx%d xf%d S=%d red%d", ROUTES[p.family].name, p.bm, p.bn, p.xf, p.S, p.red_q);
+    return snprintf(buf, len, "%s %dx%d S=%d red%d", ROUTES[p.family].name, p.bm, p.bn, p.S, p.red_q);
+}
+
+/* every "<family> <tile>" the planners can choose, one per line */
+extern "C" const char* uda_conv_route_list(void) {
+    static char text[1024];
+    if (!text[0]) {
+        int n = 0;
+        for (int f = CF_NONE + 1; f < CF_COUNT; ++f)
+            for (int t = 0; t < ROUTES[f].ntiles; ++t)
+                n += snprintf(text + n, sizeof(text) - n, "%s%s %dx%d", n ? "\n" : "", ROUTES[f].name, ROUTES[f].tile[t][0], ROUTES[f].tile[t][1]);
+    }
+    return text;
 }
 
 // ==========================================================================================

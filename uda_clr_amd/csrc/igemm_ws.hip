@@ -16,8 +16,7 @@
 // Tile: BM = 128 pixels x BN = 64*TN couts (TN = 2 -> 128, TN = 4 -> 256: whole Cout = 256 of the
 // decoder / ASPP convs in one tile, so the activation tile is staged once), BK = 32.
 #include "common.h"
-#include <stdlib.h>
-#include "igemm_args.h"
+#include "conv_plan.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -347,76 +346,44 @@ __global__ __launch_bounds__((MW + 4) * 64) void igemm_conv_ws_kernel(ConvKArgs 
 }
 
 template <int KS, int XF, int TN, int BM>
-static int launch_ws(ConvKArgs& k, int64_t P, hipStream_t st) {
+static int launch_ws(ConvKArgs& k, const ConvPlan& p, hipStream_t st) {
     constexpr int BN = 64 * TN;
     constexpr int MW = BM == 64 ? 4 : ((BM == 256 || TN % 2 == 0) ? UDA_WS_MATH_WAVES_EVEN : 4);
-    constexpr size_t lds = 2 * (BM + BN) * IG_LD * sizeof(float);
-    static_assert(lds <= 160 * 1024, "tile does not fit the 160 KiB LDS");
-    static bool configured_dev[UDA_MAX_DEVICES] = {};       // hipFuncSetAttribute is per device
-    bool& configured = configured_dev[uda_device_slot()];
-    auto fn = igemm_conv_ws_kernel<KS, XF, TN, MW, BM>;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return uda_set_error("igemm_conv_ws: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-        configured = true;
-    }
-    k.nMt = uda_cdiv(P, BM);
+    static_assert(ws_lds_bytes(BM, BN) <= 160 * 1024, "tile does not fit the 160 KiB LDS");
+    if (int e = uda_reserve_lds<igemm_conv_ws_kernel<KS, XF, TN, MW, BM>>(p.lds, "igemm_conv_ws")) return e;
+    k.nMt = uda_cdiv(p.P, BM);
     k.nNt = uda_cdiv(k.Cout, BN);
-    #ifdef UDA_DIAG          // diagnostic builds only (make DIAG=1): the ablation modes change the results
+#ifdef UDA_DIAG          // diagnostic builds only (make DIAG=1): the ablation modes change the results
     static const int dbg = getenv("UDA_WS_DEBUG") ? atoi(getenv("UDA_WS_DEBUG")) : 0;
-#else
-    const int dbg = 0;
-#endif
     k.debug = dbg;
-    hipLaunchKernelGGL(fn, dim3(k.nMt * k.nNt), dim3((MW + 4) * 64), lds, st, k);
+#endif
+    hipLaunchKernelGGL((igemm_conv_ws_kernel<KS, XF, TN, MW, BM>), dim3(p.grid), dim3((MW + 4) * 64), p.lds, st, k);
     UDA_LAUNCH_CHECK("igemm_conv_ws");
     return 0;
 }
 
 template <int KS, int TN, int BM>
-static int launch_ws_xf(ConvKArgs& k, int64_t P, hipStream_t st) {
-    if (k.src.mask) return launch_ws<KS, 2, TN, BM>(k, P, st);
-    if (k.src.scale) return launch_ws<KS, 1, TN, BM>(k, P, st);
-    if (k.src.act != ACT_NONE) return launch_ws<KS, 1, TN, BM>(k, P, st);
-    return launch_ws<KS, 0, TN, BM>(k, P, st);
+static int launch_ws_xf(ConvKArgs& k, const ConvPlan& p, hipStream_t st) {
+    return p.xf == 2 ? launch_ws<KS, 2, TN, BM>(k, p, st) : p.xf == 1 ? launch_ws<KS, 1, TN, BM>(k, p, st) : launch_ws<KS, 0, TN, BM>(k, p, st);
 }
 
 template <int KS>
-static int launch_ws_tn(ConvKArgs& k, int64_t P, int tn, bool tall, bool low, hipStream_t st) {
-    if (low) return launch_ws_xf<KS, 2, 64>(k, P, st);          // 64 x 128 tiles: few pixels (32x32 maps), fill the CUs first
-    switch (tn) {
-        case 2: return launch_ws_xf<KS, 2, 128>(k, P, st);      // two 128x128 workgroups per CU beat one 256x128 (measured)
-        case 3: return launch_ws_xf<KS, 3, 128>(k, P, st);
-        case 4: return tall ? launch_ws_xf<KS, 4, 256>(k, P, st) : launch_ws_xf<KS, 4, 128>(k, P, st);
-        default: return launch_ws_xf<KS, 5, 128>(k, P, st);
+static int launch_ws_tile(ConvKArgs& k, const ConvPlan& p, hipStream_t st) {
+    if (p.bm == 64) return launch_ws_xf<KS, 2, 64>(k, p, st);
+    if (p.bm == 256) return launch_ws_xf<KS, 4, 256>(k, p, st);
+    switch (p.bn) {
+        case 128: return launch_ws_xf<KS, 2, 128>(k, p, st);
+        case 192: return launch_ws_xf<KS, 3, 128>(k, p, st);
+        case 256: return launch_ws_xf<KS, 4, 128>(k, p, st);
+        default: return launch_ws_xf<KS, 5, 128>(k, p, st);
     }
 }
 
-int launch_conv_ws(ConvKArgs& k, int64_t P, hipStream_t st) {
-    const int64_t lim = (int64_t)1 << 31, Pin = (int64_t)k.src.N * k.src.H * k.src.W;      // (P: output rows)
+int launch_conv_ws(ConvKArgs& k, const ConvPlan& p, hipStream_t st) {
+    const int64_t lim = (int64_t)1 << 31, Pin = (int64_t)k.src.N * k.src.H * k.src.W;      // (p.P: output rows)
     UDA_REQUIRE((Pin + 128) * k.src.ldx < lim / 4 && (Pin + 128) * (k.src.mask ? k.src.ldm : 1) < lim && (int64_t)(k.Cout + 320) * k.Ktot < lim,
                 "uda_conv_fwd: operand too large for the 32-bit element offsets of the wide-tile kernel");
-    // Tile width BN = 64*TN chosen by a wave-quantisation model: workgroups run one per CU, a K-chunk
-    // costs ~TN MFMA-units, so time ~ ceil(#tiles / 256 CUs) * TN.  E.g. Cout = 304 at P = 262144 ->
-    // TN = 5 (one 320-wide tile, 5 % padding); Cout = 320 at P = 16384 -> TN = 3 (256 workgroups).
-    const int64_t nMt = uda_cdiv(P, 128);
-    int best = 2;
-    int64_t best_cost = -1;
-    for (int tn = 2; tn <= 5; ++tn) {
-        const int64_t tiles = nMt * uda_cdiv(k.Cout, 64 * tn);
-        const int64_t cost = ((tiles + 255) / 256) * tn * 16 + (tn == 2 ? 3 : 0);   // BN=128 stages A twice as often
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = tn;
-        }
-    }
-    // 256-pixel tiles (a third less operand staging per MFMA) once they still fill the chip twice over
-    static const int tall_env = getenv("UDA_WS_TALL") ? atoi(getenv("UDA_WS_TALL")) : 1;
-    const bool tall = tall_env && best == 4 && uda_cdiv(P, 256) * uda_cdiv(k.Cout, 256) >= 512;
-    // few pixels (ResNet's 32x32-map layers at B = 8: 64 tiles of 128 rows for 256 CUs): 64-row tiles, twice the workgroups
-    static const int low_env = getenv("UDA_WS_LOW") ? atoi(getenv("UDA_WS_LOW")) : 1;
-    const bool low = low_env && nMt * uda_cdiv(k.Cout, 64 * best) <= 192 && nMt * uda_cdiv(k.Cout, 128) <= 256;
-    return k.ksize >= 2 ? launch_ws_tn<3>(k, P, best, tall, low, st) : launch_ws_tn<1>(k, P, best, tall, low, st);
+    return p.ks == 3 ? launch_ws_tile<3>(k, p, st) : launch_ws_tile<1>(k, p, st);
 }
 
 // ==========================================================================================
@@ -635,31 +602,23 @@ __global__ __launch_bounds__(BIG ? 768 : 512) void igemm_wgrad_ws_kernel(WgradKA
 }
 
 template <int KS, int XF, bool BIG>
-static int launch_wg(WgradKArgs& k, int S, hipStream_t st) {
-    constexpr size_t lds = 2 * WG_BKP * (BIG ? 512 : 256) * sizeof(float);
-    static bool configured_dev[UDA_MAX_DEVICES] = {};       // hipFuncSetAttribute is per device
-    bool& configured = configured_dev[uda_device_slot()];
-    auto fn = igemm_wgrad_ws_kernel<KS, XF, BIG>;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return uda_set_error("igemm_wgrad_ws: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-        configured = true;
-    }
-    hipLaunchKernelGGL(fn, dim3(k.nCot * k.nJt, S), dim3(BIG ? 768 : 512), lds, st, k);
+static int launch_wg(WgradKArgs& k, const WgradPlan& p, hipStream_t st) {
+    if (int e = uda_reserve_lds<igemm_wgrad_ws_kernel<KS, XF, BIG>>(p.lds, "igemm_wgrad_ws")) return e;
+    hipLaunchKernelGGL((igemm_wgrad_ws_kernel<KS, XF, BIG>), dim3(p.nCot * p.nJt, p.S), dim3(BIG ? 768 : 512), p.lds, st, k);
     UDA_LAUNCH_CHECK("igemm_wgrad_ws");
     return 0;
 }
 
 template <int KS, bool BIG>
-static int launch_wg_xf(WgradKArgs& k, int S, int xf, hipStream_t st) {
-    return xf == 2 ? launch_wg<KS, 2, BIG>(k, S, st) : xf == 1 ? launch_wg<KS, 1, BIG>(k, S, st) : launch_wg<KS, 0, BIG>(k, S, st);
+static int launch_wg_xf(WgradKArgs& k, const WgradPlan& p, hipStream_t st) {
+    return p.xf == 2 ? launch_wg<KS, 2, BIG>(k, p, st) : p.xf == 1 ? launch_wg<KS, 1, BIG>(k, p, st) : launch_wg<KS, 0, BIG>(k, p, st);
 }
 
-int launch_wgrad_ws(WgradKArgs& k, int S, bool big, hipStream_t st) {
+int launch_wgrad_ws(WgradKArgs& k, const WgradPlan& p, hipStream_t st) {
     const int64_t lim = (int64_t)1 << 31, P = (int64_t)k.src.N * k.src.H * k.src.W;
     UDA_REQUIRE((P + 64) * k.src.ldx < lim / 4 && (P + 64) * k.lddy < lim / 4 && (P + 64) * (k.src.mask ? k.src.ldm : 1) < lim,
                 "uda_conv_wgrad: operand too large for the 32-bit byte offsets of the wide-tile kernel (P * ld must stay below 2^29 elements)");
-    const int xf = k.src.mask ? 2 : ((k.src.scale || k.src.act != ACT_NONE) ? 1 : 0);
-    if (k.ksize >= 2) return big ? launch_wg_xf<3, true>(k, S, xf, st) : launch_wg_xf<3, false>(k, S, xf, st);
-    return big ? launch_wg_xf<1, true>(k, S, xf, st) : launch_wg_xf<1, false>(k, S, xf, st);
+    const bool big = p.bm == 256;
+    if (k.ksize >= 2) return big ? launch_wg_xf<3, true>(k, p, st) : launch_wg_xf<3, false>(k, p, st);
+    return big ? launch_wg_xf<1, true>(k, p, st) : launch_wg_xf<1, false>(k, p, st);
 }

@@ -20,15 +20,12 @@
 //   * the loader keeps TWO chunks of global loads in flight (two register sets): with one, its loads were issued only a barrier
 //     before they were needed and the kernel ran at the load latency (2.3 us per chunk against 1.5 us of MFMA work).
 #include "common.h"
-#include <stdlib.h>
-#include "igemm_args.h"
+#include "conv_plan.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-#define X3_BK 16
-#define X3_ROW 56         // bf16 per staged row: 3 pieces x 16 + 8 pad = 112 B: a row's 96 B arrive as they lie in the packed operand
                           // (linear, conflict-free ds_write_b128), and the fragment reads of 16 lanes (rows r, byte r*112 + q*32 + h*16)
                           // fall on 64 distinct banks
 
@@ -516,98 +513,39 @@ __global__ __launch_bounds__(256) void x3_tail_reduce_kernel(X3TailArgs a) {
     }
 }
 
-// Tail plan of a tile choice: the last, partly filled round of tiles is computed by ksplit workgroups per tile over consecutive K
-// ranges (x3_tail_reduce_kernel sums the partial tiles) when the conv has no statistics epilogue and the caller gave a workspace.
-struct X3Tail {
-    int64_t tiles, full, tail;
-    int ksplit;
-};
-
-static X3Tail x3_tail_plan(int64_t P, int Cout, int nchunks, int BM, int BN, bool allow) {
-    X3Tail t;
-    t.tiles = uda_cdiv(P, BM) * uda_cdiv(Cout, BN);
-    t.full = (t.tiles / 256) * 256;
-    t.tail = t.tiles - t.full;
-    t.ksplit = 1;
-    // only where it clearly pays: a long K (the fp32 partial tiles are extra traffic - one write and one read per split - and on the
-    // short-K layers the split bought 2-3 %) and at least three splits (measured: discriminator L3 / L4 forward 10 % / 16 %)
-    static const int mode = getenv("UDA_X3_TAIL_MODE") ? atoi(getenv("UDA_X3_TAIL_MODE")) : 1;      // experiment: 2 = every tail <= 128 tiles
-    if (allow && t.tail > 0 && (mode == 2 ? t.tail <= 128 : (t.tail <= 85 && nchunks >= 96))) {
-        int s = (int)(256 / t.tail);
-        if (s > 8) s = 8;
-        if (s > nchunks / 8) s = nchunks / 8;       // at least 8 chunks per workgroup
-        if (s >= (mode == 2 ? 2 : 3)) t.ksplit = s;
-    }
-    return t;
-}
-
-static uint64_t x3_tail_bytes(const X3Tail& t, int BM, int BN) {
-    return t.ksplit > 1 ? (uint64_t)t.tail * t.ksplit * BM * BN * sizeof(float) : 0;
-}
-
+// One forward launch as planned (conv_plan): the main grid over the tiles of the full rounds (all tiles without a split), then the
+// K-split tail launch and its reduction.
 template <int KS, int TN, int BM>
-static int launch_x3(X3KArgs& k, int64_t P, hipStream_t st, void* ws = nullptr, uint64_t ws_bytes = 0) {
+static int launch_x3(X3KArgs& k, const ConvPlan& p, float* ws, hipStream_t st) {
     constexpr int BN = 64 * TN;
-    constexpr size_t lds = 2 * (BM + BN) * X3_ROW * sizeof(__bf16);
-    static_assert(lds <= 160 * 1024, "tile does not fit the 160 KiB LDS");
-    static bool configured_dev[UDA_MAX_DEVICES] = {};       // hipFuncSetAttribute is per device
-    bool& configured = configured_dev[uda_device_slot()];
-    auto fn = igemm_conv_x3_kernel<KS, TN, BM>;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return uda_set_error("igemm_conv_x3: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-        configured = true;
-    }
-    k.nMt = uda_cdiv(P, BM);
+    static_assert(x3_lds_bytes(BM, BN) <= 160 * 1024, "tile does not fit the 160 KiB LDS");
+    k.nMt = uda_cdiv(p.P, BM);
     k.nNt = uda_cdiv(k.Cout, BN);
-    #ifdef UDA_DIAG          // diagnostic builds only (make DIAG=1): bit0 skips the MFMAs - results are WRONG with it
+    k.debug = 0;
+#ifdef UDA_DIAG          // diagnostic builds only (make DIAG=1): bit0 skips the MFMAs - results are WRONG with it
     static const int dbg = getenv("UDA_X3_DEBUG") ? atoi(getenv("UDA_X3_DEBUG")) : 0;
-#else
-    const int dbg = 0;
-#endif
     k.debug = dbg;
-    X3Tail t = x3_tail_plan(P, k.Cout, k.nchunks, BM, BN, k.stats == nullptr && ws != nullptr);
-    if (x3_tail_bytes(t, BM, BN) > ws_bytes) t.ksplit = 1;
+#endif
     k.tile_off = 0; k.ksplit = 1; k.partial = nullptr;
-    k.ntiles_main = (int)(t.ksplit > 1 ? t.full : t.tiles);
+    k.ntiles_main = p.grid;
     if (k.ntiles_main > 0) {
-        hipLaunchKernelGGL(fn, dim3(k.ntiles_main), dim3(768), lds, st, k);
+        if (int e = uda_reserve_lds<igemm_conv_x3_kernel<KS, TN, BM>>(p.lds, "igemm_conv_x3")) return e;
+        hipLaunchKernelGGL((igemm_conv_x3_kernel<KS, TN, BM>), dim3(k.ntiles_main), dim3(768), p.lds, st, k);
         UDA_LAUNCH_CHECK("igemm_conv_x3");
     }
-    if (t.ksplit > 1) {
-        k.tile_off = (int)t.full; k.ksplit = t.ksplit; k.partial = reinterpret_cast<float*>(ws);
-        static bool configured_tail_dev[UDA_MAX_DEVICES] = {};
-        bool& configured_tail = configured_tail_dev[uda_device_slot()];
-        auto fnt = igemm_conv_x3_kernel<KS, TN, BM, true>;
-        if (!configured_tail) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fnt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return uda_set_error("igemm_conv_x3 (tail): cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-            configured_tail = true;
-        }
-        hipLaunchKernelGGL(fnt, dim3((int)t.tail * t.ksplit), dim3(768), lds, st, k);
+    if (p.ksplit > 1) {
+        k.tile_off = (int)p.full; k.ksplit = p.ksplit; k.partial = ws;
+        if (int e = uda_reserve_lds<igemm_conv_x3_kernel<KS, TN, BM, true>>(p.lds, "igemm_conv_x3 (tail)")) return e;
+        hipLaunchKernelGGL((igemm_conv_x3_kernel<KS, TN, BM, true>), dim3((int)p.tail * p.ksplit), dim3(768), p.lds, st, k);
         UDA_LAUNCH_CHECK("igemm_conv_x3 (tail)");
         X3TailArgs r;
-        r.partial = k.partial; r.ksplit = t.ksplit; r.tile_off = (int)t.full; r.ntail = (int)t.tail; r.nNt = k.nNt; r.BM = BM; r.BN = BN;
-        r.Cout = k.Cout; r.P = P; r.bias = k.bias; r.addend = k.addend; r.ld_add = k.ld_add; r.y = k.y; r.ldy = k.ldy;
-        const int64_t work = (int64_t)t.tail * BM * (BN / 4);
+        r.partial = k.partial; r.ksplit = p.ksplit; r.tile_off = (int)p.full; r.ntail = (int)p.tail; r.nNt = k.nNt; r.BM = BM; r.BN = BN;
+        r.Cout = k.Cout; r.P = p.P; r.bias = k.bias; r.addend = k.addend; r.ld_add = k.ld_add; r.y = k.y; r.ldy = k.ldy;
+        const int64_t work = (int64_t)p.tail * BM * (BN / 4);
         hipLaunchKernelGGL(x3_tail_reduce_kernel, dim3((int)uda_cdiv(work, 256)), dim3(256), 0, st, r);
         UDA_LAUNCH_CHECK("x3_tail_reduce");
     }
     return 0;
-}
-
-// Eligibility: the tap-chunked K order (>= 32 channels per tap), and enough MFMA work per packed element to pay for the packing
-// pass (2 * Cout * taps FLOPs per activation element).  Measured (tests/bench_x3.py, profiles/r02_bf16x3_vs_f32_conv_microbench.txt):
-// 3x3 / 2x2 convs with >= 128 outputs run 1.5-2.0x faster incl. the pass; a 3x3 conv towards 48 channels over K = 2304 1.9x on
-// the 256 x 64 tile; 1x1 convs only when very wide (256 -> 2304 tap GEMM of the re-associated decoder conv: 1.6-1.8x; 1280 -> 256
-// at 16384 pixels: 1.0x, stays on the fp32 pipe).
-bool conv_x3_eligible(const ConvKArgs& k) {
-    // 1x1: very wide outputs (the 256 -> 2304 tap GEMM), or a long K towards >= 256 outputs (ResNet-101's bottleneck convs 1024 -> 256 and
-    // 2048 -> 512 on the 32x32 maps: their operands are block inputs / gradients that the weight gradient packs anyway).
-    // (measured with Cout >= 128 on MobileNetV2's 1x1 convs: they gain nothing, the packing pass eats it)
-    static const int long_k = getenv("UDA_X3_LONGK_1X1") ? atoi(getenv("UDA_X3_LONGK_1X1")) : 1;
-    if (k.ksize == 1) return k.Kc >= 128 && (k.Cout >= 1024 || (long_k && k.Kc >= 1024 && k.Cout >= 256));
-    return k.Kc >= IG_BK && k.Cout * k.ksize * k.ksize >= 432;
 }
 
 static inline int x3_nb(int C) { return uda_cdiv(C, X3_BK); }
@@ -674,45 +612,19 @@ extern "C" int uda_x3_pack_s2d_bwd(const float* dz, int64_t ld_z, int Hz, int Wz
     return 0;
 }
 
-// Tile choice: the cheapest of 256 x 256, 128 x 256, 256 x 128, 128 x 128 under  rounds x tile area / tile efficiency, a round
-// being one tile per CU - padding waste (Cout = 304 fits three 128-wide tiles better than two 256-wide ones) and the partly
-// filled last round both count; with a workspace and no statistics epilogue that last round is split over K (x3_tail_plan) and
-// costs 1 / ksplit of a round plus the reduce.  Efficiencies fitted to the discriminator layers (tests/bench_x3.py with
-// UDA_X3_TILE forcing a tile; the tiles stage 32 / 48 / 48 / 64 B per MFMA clock and CU, two 128 x 128 workgroups can share a CU).
-static int x3_pick_tile(int64_t P, int Cout, int nchunks, bool allow_tail) {
-    static const int force = getenv("UDA_X3_TILE") ? atoi(getenv("UDA_X3_TILE")) : -1;
-    if (force >= 0 && force < 4) return force;
-    const int bm[4] = {256, 128, 256, 128}, bn[4] = {256, 256, 128, 128};
-    const double eff[4] = {1.0, 0.97, 0.92, 0.84};
-    int best = 0;
-    double bestc = 1e300;
-    for (int t = 0; t < 4; ++t) {
-        const X3Tail tp = x3_tail_plan(P, Cout, nchunks, bm[t], bn[t], allow_tail);
-        double rounds = (double)(tp.full / 256);
-        if (tp.tail > 0) rounds += tp.ksplit > 1 ? 1.0 / tp.ksplit + 0.12 : 1.0;
-        const double c = rounds * bm[t] * bn[t] / eff[t];
-        if (c < bestc) { bestc = c; best = t; }
-    }
-    return best;
+template <int KS>
+static int launch_x3_tile(X3KArgs& x, const ConvPlan& p, float* ws, hipStream_t st) {
+    if (p.bn == 64) return launch_x3<3, 1, 256>(x, p, ws, st);      // input gradient towards a narrow tensor (decoder low-level branch)
+    if (p.bm == 256) return p.bn == 256 ? launch_x3<KS, 4, 256>(x, p, ws, st) : launch_x3<KS, 2, 256>(x, p, ws, st);
+    return p.bn == 256 ? launch_x3<KS, 4, 128>(x, p, ws, st) : launch_x3<KS, 2, 128>(x, p, ws, st);
 }
 
-static const int X3_TILE_BM[4] = {256, 128, 256, 128}, X3_TILE_BN[4] = {256, 256, 128, 128};
-
-// workspace the tail split of this conv wants (0: none)
-uint64_t conv_x3_workspace_bytes(const ConvKArgs& k, int64_t P) {
-    static const bool off = getenv("UDA_X3_NO_TAIL") != nullptr;
-    if (off || k.stats || (k.ksize >= 2 && k.Cout <= 64)) return 0;
-    const int nch = uda_cdiv(k.Ktot, X3_BK);
-    const int t = x3_pick_tile(P, k.Cout, nch, true);
-    return x3_tail_bytes(x3_tail_plan(P, k.Cout, nch, X3_TILE_BM[t], X3_TILE_BN[t], true), X3_TILE_BM[t], X3_TILE_BN[t]);
-}
-
-int launch_conv_x3(ConvKArgs& k, int64_t P, const void* x3_src, const void* x3_w, hipStream_t st, void* ws, uint64_t ws_bytes) {
+int launch_conv_x3(const ConvKArgs& k, const ConvPlan& p, const void* x3_src, const void* x3_w, void* ws, hipStream_t st) {
     const int64_t lim = (int64_t)1 << 31;
     const int nbA = x3_nb(k.src.C), nch = uda_cdiv(k.Ktot, X3_BK);
     UDA_REQUIRE(x3_src && x3_w && uda_aligned16(x3_src) && uda_aligned16(x3_w),
                 "uda_conv_fwd (bf16x3): the packed operands x3_src / x3_w are missing (uda_x3_pack; uda_conv_uses_x3 tells when they are needed)");
-    const int64_t Pin = (int64_t)k.src.N * k.src.H * k.src.W;      // (P: output rows)
+    const int64_t Pin = (int64_t)k.src.N * k.src.H * k.src.W;      // (p.P: output rows)
     UDA_REQUIRE((Pin + 256) * nbA * 6 < lim / 16 && (int64_t)(k.Cout + 320) * nch * 6 < lim / 16,
                 "uda_conv_fwd (bf16x3): operand too large for the 32-bit offsets of the wide-tile kernel");
     X3KArgs x;
@@ -721,25 +633,7 @@ int launch_conv_x3(ConvKArgs& k, int64_t P, const void* x3_src, const void* x3_w
     x.stride = k.stride; x.Ho = k.Ho; x.Wo = k.Wo;
     x.Cout = k.Cout; x.ksize = k.ksize; x.dil = k.dil; x.cen = k.cen; x.nchunks = nch;
     x.bias = k.bias; x.addend = k.addend; x.ld_add = k.ld_add; x.y = k.y; x.ldy = k.ldy; x.stats = k.stats;
-    if (k.ksize >= 2 && k.Cout <= 64) return launch_x3<3, 1, 256>(x, P, st);      // input gradient towards a narrow tensor (decoder low-level branch)
-    const uint64_t want = conv_x3_workspace_bytes(k, P);
-    const bool tail_ok = want > 0 && ws != nullptr && ws_bytes >= want && uda_aligned16(ws);
-    if (!tail_ok) { ws = nullptr; ws_bytes = 0; }
-    const int best = x3_pick_tile(P, k.Cout, nch, tail_ok);
-    if (k.ksize >= 2) {
-        switch (best) {
-            case 0: return launch_x3<3, 4, 256>(x, P, st, ws, ws_bytes);
-            case 1: return launch_x3<3, 4, 128>(x, P, st, ws, ws_bytes);
-            case 2: return launch_x3<3, 2, 256>(x, P, st, ws, ws_bytes);
-            default: return launch_x3<3, 2, 128>(x, P, st, ws, ws_bytes);
-        }
-    }
-    switch (best) {
-        case 0: return launch_x3<1, 4, 256>(x, P, st, ws, ws_bytes);
-        case 1: return launch_x3<1, 4, 128>(x, P, st, ws, ws_bytes);
-        case 2: return launch_x3<1, 2, 256>(x, P, st, ws, ws_bytes);
-        default: return launch_x3<1, 2, 128>(x, P, st, ws, ws_bytes);
-    }
+    return p.ks == 3 ? launch_x3_tile<3>(x, p, reinterpret_cast<float*>(ws), st) : launch_x3_tile<1>(x, p, reinterpret_cast<float*>(ws), st);
 }
 
 // ==========================================================================================================================
@@ -950,56 +844,29 @@ __global__ __launch_bounds__(768) void igemm_wgrad_x3_kernel(X3WgArgs a) {
     }
 }
 
-// Eligibility of the weight gradient: 16-wide channel blocks must not straddle taps (Kc % 16 == 0), enough work to pay for the
-// packing of dy (the source's packed form usually exists already from the forward conv).
-bool wgrad_x3_eligible(int Cin, int Cout, int ksize, int64_t P) {
-    static const int long_k = getenv("UDA_X3_LONGK_1X1") ? atoi(getenv("UDA_X3_LONGK_1X1")) : 1;
-    if (ksize == 1) return Cin % 16 == 0 && P >= 4096 && ((Cin >= 128 && Cout >= 1024) || (long_k && Cin >= 1024 && Cout >= 256));
-    return Cin % 16 == 0 && Cin >= 32 && Cout >= 96 && P >= 4096;
+template <int BM, int BN>
+static int launch_wg_x3(const X3WgArgs& x, const WgradPlan& p, hipStream_t st) {
+    if (int e = uda_reserve_lds<igemm_wgrad_x3_kernel<BM, BN>>(p.lds, "igemm_wgrad_x3")) return e;
+    hipLaunchKernelGGL((igemm_wgrad_x3_kernel<BM, BN>), dim3(p.nCot * p.nJt, p.S), dim3(768), p.lds, st, x);
+    UDA_LAUNCH_CHECK("igemm_wgrad_x3");
+    return 0;
 }
 
-int launch_wgrad_x3(const WgradKArgs& k, int64_t P, int S_max, const void* x3_src, const void* x3_dy, hipStream_t st, int& S_out) {
+int launch_wgrad_x3(const WgradKArgs& k, const WgradPlan& p, const void* x3_src, const void* x3_dy, hipStream_t st) {
     UDA_REQUIRE(x3_src && x3_dy && uda_aligned16(x3_src) && uda_aligned16(x3_dy),
                 "uda_conv_wgrad (bf16x3): the packed operands x3_src / x3_dy are missing (uda_x3_pack; uda_conv_wgrad_uses_x3)");
     const int64_t lim = (int64_t)1 << 31;
     const int nbCo = x3_nb(k.Cout), nbC = x3_nb(k.src.C);
-    const int64_t Pin = (int64_t)k.src.N * k.src.H * k.src.W;      // (P: pixels of dy)
-    UDA_REQUIRE((P + 64) * nbCo * 6 < lim / 16 && (Pin + 64 + 4 * k.src.W * k.dil) * nbC * 6 < lim / 16,
+    const int64_t Pin = (int64_t)k.src.N * k.src.H * k.src.W;      // (p.P: pixels of dy)
+    UDA_REQUIRE((p.P + 64) * nbCo * 6 < lim / 16 && (Pin + 64 + 4 * k.src.W * k.dil) * nbC * 6 < lim / 16,
                 "uda_conv_wgrad (bf16x3): operand too large for the 32-bit offsets of the wide-tile kernel");
-    // tiles (Cout x J): 256 x 256 for wide outputs; 128 x 256 otherwise (128 x 128 tiles would stage 64 B per MFMA clock and CU and
-    // are load-bound); 128 x 128 only for short J
-    const bool big = k.Cout >= 192 && k.Jtot >= 256 && P >= 8192;
-    const bool wideJ = !big && k.Jtot >= 256;
-    const int BM = big ? 256 : 128, BN = (big || wideJ) ? 256 : 128;
     X3WgArgs x;
     x.xdy = reinterpret_cast<const uint32_t*>(x3_dy); x.xs = reinterpret_cast<const uint32_t*>(x3_src);
     x.N = k.src.N; x.H = k.src.H; x.W = k.src.W; x.nbCo = nbCo; x.nbC = nbC;
     x.stride = k.stride; x.Ho = k.Ho; x.Wo = k.Wo;
     x.Cout = k.Cout; x.Jtot = k.Jtot; x.Kc = k.Kc; x.ksize = k.ksize; x.dil = k.dil; x.cen = k.cen;
     x.slab = k.slab;
-    x.nCot = uda_cdiv(k.Cout, BM); x.nJt = uda_cdiv(k.Jtot, BN);
-    x.nchunks = uda_cdiv(P, X3_BK);
-    int S = (big ? 512 : (wideJ ? 768 : 1024)) / (x.nCot * x.nJt);
-    if (S > x.nchunks / 8) S = x.nchunks / 8;
-    if (S > S_max) S = S_max;           // the caller's slab holds S_max splits
-    if (S < 1) S = 1;
-    x.cps = uda_cdiv(x.nchunks, S);
-    S = uda_cdiv(x.nchunks, x.cps);
-    S_out = S;
-    static bool configured_dev[UDA_MAX_DEVICES] = {};       // hipFuncSetAttribute is per device
-    bool& configured = configured_dev[uda_device_slot()];
-    auto ldsz = [](int bm, int bn) { return (size_t)2 * 3 * 16 * ((bm * 2 + 64) + (bn * 2 + 64)); };
-    if (!configured) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_wgrad_x3_kernel<256, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz(256, 256));
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_wgrad_x3_kernel<128, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz(128, 256));
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_wgrad_x3_kernel<128, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz(128, 128));
-        if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess) return uda_set_error("igemm_wgrad_x3: cannot reserve LDS");
-        configured = true;
-    }
-    const dim3 grid(x.nCot * x.nJt, S);
-    if (big) hipLaunchKernelGGL((igemm_wgrad_x3_kernel<256, 256>), grid, dim3(768), ldsz(256, 256), st, x);
-    else if (wideJ) hipLaunchKernelGGL((igemm_wgrad_x3_kernel<128, 256>), grid, dim3(768), ldsz(128, 256), st, x);
-    else hipLaunchKernelGGL((igemm_wgrad_x3_kernel<128, 128>), grid, dim3(768), ldsz(128, 128), st, x);
-    UDA_LAUNCH_CHECK("igemm_wgrad_x3");
-    return 0;
+    x.nCot = p.nCot; x.nJt = p.nJt; x.nchunks = p.nchunks; x.cps = p.cps;
+    if (p.bm == 256) return launch_wg_x3<256, 256>(x, p, st);
+    return p.bn == 256 ? launch_wg_x3<128, 256>(x, p, st) : launch_wg_x3<128, 128>(x, p, st);
 }

@@ -189,15 +189,10 @@ extern "C" int uda_upsample_fwd_stats(const float* x, int64_t ldx, int N, int h,
         hipLaunchKernelGGL((upsample_fwd_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, N, h, w, C, out, ldo,
                            H, W, bil_scale(h, H), bil_scale(w, W), stats, stat_C);
     else {      // out = NULL: the statistics of the upsampled tensor without forming it (uda_mc_seg_head re-derives its values): per source cell
-        static const int cells = getenv("UDA_UPSAMPLE_STATS_CELLS") ? atoi(getenv("UDA_UPSAMPLE_STATS_CELLS")) : 1;      // A/B switch
         int gc = uda_cdiv((int64_t)N * h * w * (C / 4), 256);
         if (gc > 1024) gc = 1024;
-        if (cells)
-            hipLaunchKernelGGL(upsample_stats_cells_kernel, dim3(gc), dim3(256), 0, (hipStream_t)stream, x, ldx, N, h, w, C, H, W,
-                               bil_scale(h, H), bil_scale(w, W), stats, stat_C);
-        else
-            hipLaunchKernelGGL((upsample_fwd_kernel<true, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, N, h, w, C, out, ldo,
-                               H, W, bil_scale(h, H), bil_scale(w, W), stats, stat_C);
+        hipLaunchKernelGGL(upsample_stats_cells_kernel, dim3(gc), dim3(256), 0, (hipStream_t)stream, x, ldx, N, h, w, C, H, W,
+                           bil_scale(h, H), bil_scale(w, W), stats, stat_C);
     }
     UDA_LAUNCH_CHECK("upsample_fwd_stats");
     return 0;

@@ -402,8 +402,7 @@ extern "C" int uda_upconv_fwd(const float* g, int64_t ldg, int N, int h, int w, 
     if (upconv_strip_ok(w, W, C, dil, H) && (int64_t)N * H * W < lim32 && (int64_t)N * H * (W / 4) * G < lim32 - 65536 * 256 &&
         (int64_t)N * h * w * ldg * 4 < lim32 && (!addend || addend_rows * ld_add < lim32 * 4)) {
         // the LDS-tiled kernel where the tiling fits (x4-like upsampling of a map whose sides are multiples of 16)
-        static const int tile_env = getenv("UDA_UPCONV_TILE") ? atoi(getenv("UDA_UPCONV_TILE")) : 1;      // A/B switch
-        if (tile_env && 3.f * sw < 0.98f && H % UPT_TH == 0 && W % UPT_TW == 0 && C % UPT_CS == 0) {
+        if (3.f * sw < 0.98f && H % UPT_TH == 0 && W % UPT_TW == 0 && C % UPT_CS == 0) {
             int R = 1, RC = 1;
             for (int ty = 0; ty < H / UPT_TH; ++ty) R = std::max(R, upconv_foot(ty * UPT_TH - 1, ty * UPT_TH + UPT_TH, sh, h, H));
             for (int tx = 0; tx < W / UPT_TW; ++tx) RC = std::max(RC, upconv_foot(tx * UPT_TW - 1, tx * UPT_TW + UPT_TW, sw, w, W));
@@ -568,8 +567,7 @@ extern "C" int uda_upconv_bwd(const float* dy, int64_t ldy, int N, int H, int W,
     if (grid > 65536) grid = 65536;
     const float sh = bil_scale(h, H), sw = bil_scale(w, W);
     // one wave per low-resolution pixel when its 64 lanes are exactly the channel granules and the tap ranges fit the 32-entry weight tables
-    static const int wave_env = getenv("UDA_UPCONV_BWD_WAVE") ? atoi(getenv("UDA_UPCONV_BWD_WAVE")) : 1;      // A/B switch
-    if (wave_env && C == 256 && dil == 1 && sh > 0.f && sw > 0.f && 2.f / sh + 6.f <= 32.f && 2.f / sw + 6.f <= 32.f && (int64_t)N * h * w < ((int64_t)1 << 31)) {
+    if (C == 256 && dil == 1 && sh > 0.f && sw > 0.f && 2.f / sh + 6.f <= 32.f && 2.f / sw + 6.f <= 32.f && (int64_t)N * h * w < ((int64_t)1 << 31)) {
         const int64_t npix = (int64_t)N * h * w;
         int gw = (int)uda_cdiv(npix, 4);
         if (gw > 65536) gw = 65536;

@@ -11,14 +11,11 @@ lives on its own z grid with Ho = H // 2 + 1 valid rows/columns (257, 129, 65, 3
 """
 from __future__ import annotations
 
-import os
-
 import torch
 
 from .acts import Act, round4
 
 SLOPE = 0.2
-_S2D_PACK = os.environ.get("UDA_CLR_S2D_PACK", "1") != "0"      # A/B switch of the one-pass packed space-to-depth operands
 
 
 def _zgrid(v):
@@ -58,7 +55,7 @@ class PatchDiscriminatorEngine:
             # bf16x3 mode, layers whose conv (and weight gradient) run on the packed operands: the z image is written in packed form
             # only, straight from the previous layer's output (uda_x3_pack_s2d_fwd) - no fp32 image, no separate packing pass; the
             # backward then takes the LeakyReLU gate from the sign of that source (z = lrelu(source)), which is kept instead
-            packed = (li > 0 and Cc % 8 == 0 and hasattr(K, "s2d_pack_fwd") and _S2D_PACK and K.conv_route_x3(N, Hz, Wz, 4 * Cc, O, 2)
+            packed = (li > 0 and Cc % 8 == 0 and hasattr(K, "s2d_pack_fwd") and K.conv_route_x3(N, Hz, Wz, 4 * Cc, O, 2)
                       and (not need_grad or K.wgrad_route_x3(N, Hz, Wz, 4 * Cc, O, 2)))
             if packed:
                 z = K.s2d_pack_fwd(src, N, Hs, Ws, Cc, vh, vw, slope)
@@ -115,7 +112,7 @@ class PatchDiscriminatorEngine:
                 # on packed operands it is written in packed form only (uda_x3_pack_s2d_bwd)
                 below = layers[l - 1]
                 need_dx_below = (l - 1 > 0) or need_x
-                pack_dy = (gate is not None and hasattr(K, "s2d_pack_bwd") and _S2D_PACK and Cc % 8 == 0
+                pack_dy = (gate is not None and hasattr(K, "s2d_pack_bwd") and Cc % 8 == 0
                            and (not need_w or K.wgrad_route_x3(N, Hs, Ws, 4 * below[1], Cc, 2))
                            and (not need_dx_below or K.conv_route_x3(N, Hs, Ws, Cc, 4 * below[1], 2)))
                 if pack_dy:

@@ -53,6 +53,9 @@ SYMBOLS = {
     "uda_conv_fwd": (_I, [C.POINTER(UdaConvArgs), _P]),
     "uda_conv_uses_x3": (_I, [C.POINTER(UdaConvArgs)]),
     "uda_conv_fwd_workspace_bytes": (_U, [C.POINTER(UdaConvArgs)]),
+    "uda_conv_route": (_I, [C.POINTER(UdaConvArgs), C.c_char_p, _I]),
+    "uda_conv_wgrad_route": (_I, [C.POINTER(UdaWgradArgs), C.c_char_p, _I]),
+    "uda_conv_route_list": (C.c_char_p, []),
     "uda_x3_packed_bytes": (_U, [_L, _I]),
     "uda_x3_pack": (_I, [C.POINTER(UdaSrc), _P, _P]),
     "uda_conv_wgrad_workspace_bytes": (_U, [_L, _I, _I, _I]),
@@ -288,27 +291,7 @@ class HipKernels:
                 r = slice(n0 * ppo, n1 * ppo)
                 self.conv(self._act_rows(src, n0, n1), w, ksize, dil, out[r], bias, None if addend is None else addend[r], stats, origin, stride)
             return
-        a = UdaConvArgs()
-        a.origin = origin
-        a.src = self._src(src)
-        Cout = out.shape[1]
-        assert w.is_contiguous() and tuple(w.shape) == conv_weight_shape(Cout, ksize, src.C), \
-            "weight layout %s does not match conv %dx%d %d->%d" % (tuple(w.shape), ksize, ksize, src.C, Cout)
-        assert out.shape[0] == Po and stride in (1, 2)
-        a.w, a.Cout, a.ksize, a.dil, a.stride = w.data_ptr(), Cout, ksize, dil, stride
-        a.bias = _ptr(bias)
-        if bias is not None:
-            assert bias.is_contiguous() and bias.numel() == Cout
-        if addend is not None:
-            assert addend.shape == out.shape
-            a.addend, a.ld_add = _mat(addend, "addend")
-        else:
-            a.addend, a.ld_add = None, 0
-        a.y, a.ldy = _mat(out, "out")
-        if stats is not None:
-            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, Cout)
-        a.stats = _ptr(stats)
-        a.mfma = self.mfma
+        a = self._conv_args_of(src, w, ksize, dil, out, bias, addend, stats, origin, stride)
         if self.mfma != self.MFMA_F32 and self.lib.uda_conv_uses_x3(C.byref(a)):
             # bf16x3: both operands as their three bf16 pieces.  The packed forms are kept on the descriptor / the relayouted
             # weight, so an activation read by several convolutions (the ASPP input) and a weight used by several passes of one
@@ -325,6 +308,48 @@ class HipKernels:
                 a.workspace, a.workspace_bytes = ws.data_ptr(), nws
             return self._conv_x3(a)
         self._ck(self.lib.uda_conv_fwd(C.byref(a), self._stream()))
+
+    def conv_args(self, usrc: UdaSrc, Cout, ksize, dil=1, origin=0, stride=1, w=None, bias=None, addend=None, ld_add=0, y=None, ldy=0,
+                  stats=None) -> UdaConvArgs:
+        """The argument block of uda_conv_fwd from raw addresses (None: absent).  The only place that fills one."""
+        a = UdaConvArgs()
+        a.src, a.origin = usrc, origin
+        a.w, a.Cout, a.ksize, a.dil, a.stride = w, Cout, ksize, dil, stride
+        a.bias, a.addend, a.ld_add = bias, addend, ld_add
+        a.y, a.ldy, a.stats = y, ldy, stats
+        a.mfma = self.mfma
+        return a
+
+    def _conv_args_of(self, src: Act, w, ksize, dil, out, bias, addend, stats, origin, stride) -> UdaConvArgs:
+        Cout = out.shape[1]
+        assert w.is_contiguous() and tuple(w.shape) == conv_weight_shape(Cout, ksize, src.C), \
+            "weight layout %s does not match conv %dx%d %d->%d" % (tuple(w.shape), ksize, ksize, src.C, Cout)
+        assert out.shape[0] == src.N * ((src.H - 1) // stride + 1) * ((src.W - 1) // stride + 1) and stride in (1, 2)
+        if bias is not None:
+            assert bias.is_contiguous() and bias.numel() == Cout
+        if addend is not None:
+            assert addend.shape == out.shape
+        if stats is not None:
+            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, Cout)
+        return self.conv_args(self._src(src), Cout, ksize, dil, origin, stride, w.data_ptr(), _ptr(bias),
+                              *((None, 0) if addend is None else _mat(addend, "addend")), *_mat(out, "out"), _ptr(stats))
+
+    def route(self, a) -> str:
+        """The launch the library plans for an argument block of ``conv`` / ``conv_wgrad`` (uda_conv_route, uda_conv_wgrad_route);
+        a conv that can split its last round of tiles is described with the workspace ``conv`` would bring."""
+        buf = C.create_string_buffer(96)
+        if isinstance(a, UdaWgradArgs):
+            self.lib.uda_conv_wgrad_route(C.byref(a), buf, len(buf))
+        else:
+            nws = int(self.lib.uda_conv_fwd_workspace_bytes(C.byref(a)))
+            if nws and not a.workspace:
+                a.workspace, a.workspace_bytes = 16, nws      # the plan tests the address, it reads nothing
+            self.lib.uda_conv_route(C.byref(a), buf, len(buf))
+        return buf.value.decode()
+
+    def conv_route(self, src: Act, w, ksize, dil, out, bias=None, addend=None, stats=None, origin=0, stride=1) -> str:
+        """``route`` of the ``conv`` call with these arguments (as one launch)"""
+        return self.route(self._conv_args_of(src, w, ksize, dil, out, bias, addend, stats, origin, stride))
 
     def _conv_x3(self, a):
         """the bf16x3 GEMM launch alone (bench.py times this)"""
@@ -380,17 +405,9 @@ class HipKernels:
                 if i:
                     dw.add_(tmp)
             return
-        a = UdaWgradArgs()
-        a.origin = origin
-        a.src = self._src(src)
-        Cout = dy.shape[1]
-        assert dy.shape[0] == Po and stride in (1, 2) and dw.is_contiguous() and tuple(dw.shape) == (Cout, src.C, ksize, ksize)
-        a.dy, a.lddy = _mat(dy, "dy")
-        a.Cout, a.ksize, a.dil, a.stride = Cout, ksize, dil, stride
-        a.dw = dw.data_ptr()
-        ws = self._ws(dy, self.lib.uda_conv_wgrad_workspace_bytes(Po, Cout, src.C, ksize))
+        a = self._wgrad_args_of(src, dy, ksize, dil, dw, origin, stride)
+        ws = self._ws(dy, self.lib.uda_conv_wgrad_workspace_bytes(Po, a.Cout, src.C, ksize))
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        a.mfma = self.mfma
         if self.mfma != self.MFMA_F32 and self.lib.uda_conv_wgrad_uses_x3(C.byref(a)):
             # bf16x3: the source's packed form usually exists already (the forward conv packed the same descriptor); dy is packed
             # once for its input-gradient conv and this weight gradient (the packed form rides on the tensor object)
@@ -399,6 +416,25 @@ class HipKernels:
             xd = self._packed(dsrc, self._src(dsrc), dy.device)
             a.x3_src, a.x3_dy = xs.data_ptr(), xd.data_ptr()
         self._ck(self.lib.uda_conv_wgrad(C.byref(a), self._stream()))
+
+    def wgrad_args(self, usrc: UdaSrc, Cout, ksize, dil=1, origin=0, stride=1, dy=None, lddy=0, dw=None) -> UdaWgradArgs:
+        """The argument block of uda_conv_wgrad from raw addresses, without workspace and packed operands.  The only place that fills one."""
+        a = UdaWgradArgs()
+        a.src, a.origin = usrc, origin
+        a.dy, a.lddy, a.dw = dy, lddy, dw
+        a.Cout, a.ksize, a.dil, a.stride = Cout, ksize, dil, stride
+        a.mfma = self.mfma
+        return a
+
+    def _wgrad_args_of(self, src: Act, dy, ksize, dil, dw, origin, stride) -> UdaWgradArgs:
+        Cout = dy.shape[1]
+        assert dy.shape[0] == src.N * ((src.H - 1) // stride + 1) * ((src.W - 1) // stride + 1) and stride in (1, 2)
+        assert dw.is_contiguous() and tuple(dw.shape) == (Cout, src.C, ksize, ksize)
+        return self.wgrad_args(self._src(src), Cout, ksize, dil, origin, stride, *_mat(dy, "dy"), dw.data_ptr())
+
+    def wgrad_route(self, src: Act, dy, ksize, dil, dw, origin=0, stride=1) -> str:
+        """``route`` of the ``conv_wgrad`` call with these arguments (as one launch)"""
+        return self.route(self._wgrad_args_of(src, dy, ksize, dil, dw, origin, stride))
 
     # ------------------------------------------------------------------ depthwise
     def dwconv_fwd(self, src: Act, w9c, stride, dil, border_mode, out, stats=None, family=""):
@@ -586,26 +622,24 @@ class HipKernels:
         self._ck(self.lib.uda_s2d_fwd(sp, lds_, int(nchw), N, Hs, Ws, Cc, vh, vw, float(slope), zp, ldz, Hz, Wz, self._stream()))
 
     # ---- bf16x3: space-to-depth operands in packed form only (no fp32 image); the engine asks the routing predicates first
+    @staticmethod
+    def _raw_src(N, H, W, Cc) -> UdaSrc:
+        """descriptor of a raw [N*H*W, Cc] operand by shape alone, for the routing predicates"""
+        s = UdaSrc()
+        s.N, s.H, s.W, s.C, s.ldx = N, H, W, Cc, round4(Cc)
+        return s
+
     def conv_route_x3(self, N, H, W, Cin, Cout, ksize):
         """True when ``conv`` of a RAW [N*H*W, Cin] operand to Cout outputs runs on the bf16x3 kernel in one launch."""
         if self.mfma != self.MFMA_BF16X3 or self._image_groups(N, H * W, max(round4(Cin), round4(Cout)), Cin) is not None:
             return False
-        a = UdaConvArgs()
-        a.src.N, a.src.H, a.src.W, a.src.C = N, H, W, Cin
-        a.src.scale = a.src.shift = a.src.mask = None
-        a.src.act, a.Cout, a.ksize, a.dil, a.mfma = 0, Cout, ksize, 1, self.mfma
-        a.stats = None
-        return bool(self.lib.uda_conv_uses_x3(C.byref(a)))
+        return bool(self.lib.uda_conv_uses_x3(C.byref(self.conv_args(self._raw_src(N, H, W, Cin), Cout, ksize))))
 
     def wgrad_route_x3(self, N, H, W, Cin, Cout, ksize):
         """True when ``conv_wgrad`` of a raw [N*H*W, Cin] source against a [N*H*W, Cout] gradient runs on the bf16x3 kernel."""
         if self.mfma != self.MFMA_BF16X3 or self._image_groups(N, H * W, max(round4(Cin), round4(Cout))) is not None:
             return False
-        a = UdaWgradArgs()
-        a.src.N, a.src.H, a.src.W, a.src.C = N, H, W, Cin
-        a.src.scale = a.src.shift = a.src.mask = None
-        a.src.act, a.Cout, a.ksize, a.dil, a.mfma = 0, Cout, ksize, 1, self.mfma
-        return bool(self.lib.uda_conv_wgrad_uses_x3(C.byref(a)))
+        return bool(self.lib.uda_conv_wgrad_uses_x3(C.byref(self.wgrad_args(self._raw_src(N, H, W, Cin), Cout, ksize))))
 
     def _packed_only(self, rows, Cc, device):
         """A [rows, Cc] fp32 matrix that exists ONLY in packed bf16x3 form: the returned tensor is an (uninitialised, never
