@@ -423,6 +423,19 @@ int uda_photometric_u8(uint8_t* image_hwc, int B, int H, int W, const int* sp_po
                        int sp_max, const uint8_t* lut, const int* erase_box, void* stream);
 int uda_elastic_warp(const uint8_t* image_hwc, const uint8_t* label, const double* dx, const double* dy, const uint8_t* apply,
                      int B, int H, int W, uint8_t* image_out, uint8_t* label_out, void* stream);
+/* custom_transforms.py:152-182,208-223,315-355 (RandomCrop, RandomFlip, RandomRotate, RandomScaleCrop): the PIL geometry at the
+ * head of the chain, for a whole batch, from a device-resident copy of the decoded dataset and the draws the workers recorded.
+ *   image_pool uint8: the sources' [H0,W0,3] images back to back; label_pool uint8: their [H0,W0] masks; offsets int64
+ *   [n_sources]: first PIXEL of each source (x1 in label_pool, x3 in image_pool); sizes int32 [n_sources,2] = (H0, W0);
+ *   src_index int64 [B]; records int32 [B,10] = (scale fired, scaled w, scaled h, pad width, crop x1, crop y1 in the padded
+ *   image, counter-clockwise quarter turns, flip left-right, flip top-bottom, crop size); S the crop size.
+ *   -> image_out uint8 [B,S,S,3], label_out uint8 [B,S,S]: byte for byte what Pillow gives (8-bit BILINEAR resample in its
+ *   integer arithmetic, NEAREST mask with its accumulated double index; fill 0 / 255 in the pad).  Scaled sizes must keep
+ *   in / out <= 2.5 per axis (the transform draws >= 0.5).  A source index outside [0, n_sources) yields the fill. */
+size_t uda_geometry_u8_workspace_bytes(int B, int S);
+int uda_geometry_u8(const uint8_t* image_pool, const uint8_t* label_pool, const int64_t* offsets, const int* sizes, int n_sources,
+                    const int64_t* src_index, const int* records, int B, int S, uint8_t* image_out, uint8_t* label_out,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* Trainer_prototype_full.py:335-355, 378-398 (EMA of the eight centroids, gradient through the current term only) + :428-444
  * (intra = sum_k MSE(src_k, tgt_k), inter = MSE(src_1, src_3) + MSE(src_0, src_2)) on two [4][C] centroid matrices in one

@@ -1,5 +1,6 @@
 """Sample transforms named as train_use_fix_initial.py:150-166 uses them.  Each takes and returns the
-dict {'image', 'label', 'img_name'}; the geometric ones work on PIL images, the photometric ones on
+dict {'image', 'label', 'img_name'}; the geometric ones work on PIL images (at UDA_CLR_DEVICE_INPUT=3 on their sizes only,
+see DEVICE_TAIL below), the photometric ones on
 HxWx3 uint8 arrays (after ``elastic_transform``), ``Normalize_tf`` + ``ToTensor`` end the chain with
 float tensors image [3,H,W] in [-1,1], map [2,H,W] (ch0 cup subset of ch1 disc), boundary [1,H,W].
 
@@ -26,8 +27,36 @@ from scipy import ndimage
 #      batch in the chain's order (uda_field_smooth + uda_elastic_warp, uda_photometric_u8) before decoding.  Given the same
 #      parameters the results equal the CPU chain's byte for byte; only the elastic displacement NOISE comes from the device
 #      generator instead of numpy's (the CPU chain seeds that RandomState from OS entropy, so it has no reproducible stream).
-# The PIL geometry (scale-crop, rotate, flip) stays on the workers.
+#   3  additionally the PIL geometry at the head of the chain (RandomScaleCrop / RandomCrop, RandomRotate, RandomFlip): a worker
+#      reads sizes only, makes the same draws from `random` in the same order and records them as one int32 record
+#      (GEOM_* below); the dataset hands over the sample's index instead of its pixels, and the Trainer gathers the batch from a
+#      device-resident copy of the decoded dataset with uda_geometry_u8 (Pillow's 8-bit BILINEAR resample and NEAREST resize
+#      restated in integers, crop / pad / quarter turns / flips as index maps), byte for byte what PIL produces.  A level-3
+#      sample holds no image: the transforms downstream see a stand-in that carries the crop's shape only.  The kernel
+#      applies scale -> pad + crop -> rotate -> flip in the script's order (train_use_fix_initial.py:150-153, 162-166); a chain
+#      composed in another order raises.
 DEVICE_TAIL = int(os.environ.get("UDA_CLR_DEVICE_INPUT", "0") or 0)
+
+# level-3 geometry record (int32 [GEOM_R]): scale fired, scaled (w, h), pad width, crop origin (x1, y1) in the padded image,
+# quarter turns (counter-clockwise), flip left-right, flip top-bottom, crop size
+GEOM_R = 10
+(GEOM_SCALED, GEOM_W, GEOM_H, GEOM_PAD, GEOM_X1, GEOM_Y1, GEOM_TURNS, GEOM_FLIP_LR, GEOM_FLIP_TB, GEOM_SIZE) = range(GEOM_R)
+
+
+class _PilShape(object):
+    """level 3, before elastic_transform: what the geometric transforms read of a PIL image - its size (w, h)"""
+    def __init__(self, w, h):
+        self.size = (int(w), int(h))
+
+
+class _ArrayShape(object):
+    """level 3, from elastic_transform on: what the recording transforms read of an HxWx3 array - shape, element count, copy()"""
+    def __init__(self, shape):
+        self.shape = tuple(int(v) for v in shape)
+        self.size = int(np.prod(self.shape))
+
+    def copy(self):
+        return self
 
 
 def _defer(sample, **rec):
@@ -38,6 +67,8 @@ def _defer(sample, **rec):
 
 def _out(sample, image, label, aug=None):
     out = {'image': image, 'label': label, 'img_name': sample['img_name']}
+    if 'src_index' in sample:
+        out['src_index'] = sample['src_index']
     if aug is not None or '_aug' in sample:
         out['_aug'] = aug if aug is not None else sample['_aug']
     return out
@@ -52,6 +83,8 @@ class RandomCrop(object):
         img, mask = sample['image'], sample['label']
         w, h = img.size
         th, tw = self.size
+        if DEVICE_TAIL >= 3:
+            return self._record(sample, w, h)
         if self.padding > 0 or w < tw or h < th:
             pad = int(max(self.padding, (tw - w) // 2 + 5, (th - h) // 2 + 5))
             img, mask = ImageOps.expand(img, border=pad, fill=0), ImageOps.expand(mask, border=pad, fill=255)
@@ -61,6 +94,18 @@ class RandomCrop(object):
         x1, y1 = random.randint(0, w - tw), random.randint(0, h - th)
         box = (x1, y1, x1 + tw, y1 + th)
         return _out(sample, img.crop(box), mask.crop(box))
+
+    def _record(self, sample, w, h):
+        th, tw = self.size
+        aug = sample.get('_aug') or {}
+        if th != tw or 'crop' in aug or 'turns' in aug or 'flip' in aug:
+            raise ValueError('UDA_CLR_DEVICE_INPUT=3 supports one square crop, before RandomRotate and RandomFlip')
+        pad = 0
+        if self.padding > 0 or w < tw or h < th:
+            pad = int(max(self.padding, (tw - w) // 2 + 5, (th - h) // 2 + 5))
+            w, h = w + 2 * pad, h + 2 * pad
+        x1, y1 = (0, 0) if (w, h) == (tw, th) else (random.randint(0, w - tw), random.randint(0, h - th))
+        return _out(sample, _PilShape(tw, th), _PilShape(tw, th), _defer(sample, pad=pad, crop=(x1, y1, tw)))
 
 
 class RandomScaleCrop(object):
@@ -72,8 +117,15 @@ class RandomScaleCrop(object):
         img, mask = sample['image'], sample['label']
         if random.random() > 0.5:
             w, h = int(random.uniform(0.5, 1.5) * img.size[0]), int(random.uniform(0.5, 1.5) * img.size[1])
+            if DEVICE_TAIL >= 3:
+                return self.crop(_out(sample, _PilShape(w, h), _PilShape(w, h), _defer(sample, scale=(w, h))))
             sample = _out(sample, img.resize((w, h), Image.BILINEAR), mask.resize((w, h), Image.NEAREST))
         return self.crop(sample)
+
+
+def _need_crop(sample, who):
+    if 'crop' not in (sample.get('_aug') or {}):
+        raise ValueError('UDA_CLR_DEVICE_INPUT=3: %s must follow RandomCrop / RandomScaleCrop' % who)
 
 
 class RandomRotate(object):
@@ -83,7 +135,11 @@ class RandomRotate(object):
         self.size = size
 
     def __call__(self, sample):
-        if random.random() > 0.5:
+        fire = random.random() > 0.5
+        if DEVICE_TAIL >= 3:
+            _need_crop(sample, 'RandomRotate')
+            return _out(sample, sample['image'], sample['label'], _defer(sample, turns=(self.degree // 90) % 4 if fire else 0))
+        if fire:
             return _out(sample, sample['image'].rotate(self.degree, Image.BILINEAR), sample['label'].rotate(self.degree, Image.NEAREST))
         return sample
 
@@ -91,6 +147,9 @@ class RandomRotate(object):
 class RandomFlip(object):
     def __call__(self, sample):
         img, mask = sample['image'], sample['label']
+        if DEVICE_TAIL >= 3:
+            _need_crop(sample, 'RandomFlip')
+            return _out(sample, img, mask, _defer(sample, flip=(random.random() < 0.5, random.random() < 0.5)))
         for op in (Image.FLIP_LEFT_RIGHT, Image.FLIP_TOP_BOTTOM):
             if random.random() < 0.5:
                 img, mask = img.transpose(op), mask.transpose(op)
@@ -101,6 +160,9 @@ class elastic_transform(object):
     """Simard-style elastic deformation with p = 0.5 (alpha = 2*side, sigma = 0.08*side); always leaves
     numpy arrays behind (image HxWx3 uint8, label HxW uint8)."""
     def __call__(self, sample):
+        if DEVICE_TAIL >= 3:            # no pixels: the shape of the crop stands in for both arrays
+            image = label = _ArrayShape(_shape_of(sample['image']))
+            return _out(sample, image, label, _defer(sample, elastic=random.random() > 0.5))
         image, label = np.array(sample['image']), np.array(sample['label'])
         fire = random.random() > 0.5
         if DEVICE_TAIL >= 2:
@@ -194,6 +256,22 @@ class GetBoundary(object):
         return ring.astype(np.uint8)
 
 
+def _shape_of(image):
+    """(H, W, 3) of a level-3 stand-in"""
+    return image.shape if hasattr(image, 'shape') else (image.size[1], image.size[0], 3)
+
+
+def _geom_record(aug):
+    rec = np.zeros(GEOM_R, np.int32)
+    if 'scale' in aug:
+        rec[GEOM_SCALED], rec[GEOM_W], rec[GEOM_H] = 1, aug['scale'][0], aug['scale'][1]
+    rec[GEOM_PAD] = aug['pad']
+    rec[GEOM_X1], rec[GEOM_Y1], rec[GEOM_SIZE] = aug['crop']
+    rec[GEOM_TURNS] = aug.get('turns', 0)
+    rec[GEOM_FLIP_LR], rec[GEOM_FLIP_TB] = aug.get('flip', (0, 0))
+    return rec
+
+
 class Normalize_tf(object):
     """image -> [-1, 1]; grey-coded mask -> 2-channel map + soft boundary"""
     def __init__(self, mean=(0., 0., 0.), std=(1., 1., 1.)):
@@ -202,11 +280,19 @@ class Normalize_tf(object):
 
     def __call__(self, sample):
         if DEVICE_TAIL:
-            out = {'image_u8': np.ascontiguousarray(np.array(sample['image']).astype(np.uint8)),
-                   'label_u8': np.ascontiguousarray(np.array(sample['label']).astype(np.uint8)), 'img_name': sample['img_name']}
             aug = sample.get('_aug') or {}                      # no record = no transform fired
+            if DEVICE_TAIL >= 3:                                # no pixels: the source's index and the geometry record
+                if 'src_index' not in sample or 'crop' not in aug:
+                    raise ValueError('UDA_CLR_DEVICE_INPUT=3 needs a dataset that hands over the sample index (FundusSegmentation) '
+                                     'and a chain with RandomCrop or RandomScaleCrop')
+                n_elem = int(np.prod(_shape_of(sample['image'])))
+                out = {'src_index': np.array([sample['src_index']], np.int64), 'geom': _geom_record(aug), 'img_name': sample['img_name']}
+            else:
+                out = {'image_u8': np.ascontiguousarray(np.array(sample['image']).astype(np.uint8)),
+                       'label_u8': np.ascontiguousarray(np.array(sample['label']).astype(np.uint8)), 'img_name': sample['img_name']}
+                n_elem = out['image_u8'].size
             if DEVICE_TAIL >= 2:                                # the recorded outcomes as fixed-size arrays (collate stacks them)
-                maxn = int(np.ceil(0.004 * out['image_u8'].size * 0.8))
+                maxn = int(np.ceil(0.004 * n_elem * 0.8))
                 pos = np.zeros((maxn, 2), np.int32)
                 val, ys, xs = aug.get('sp') or (0, (), ())
                 pos[:len(ys), 0], pos[:len(xs), 1] = ys, xs
@@ -228,7 +314,7 @@ class Normalize_tf(object):
 
 class ToTensor(object):
     def __call__(self, sample):
-        if 'image_u8' in sample:          # deferred tail: uint8 [H,W,3] + uint8 [H,W] (+ recorded augmentation outcomes)
+        if 'image_u8' in sample or 'src_index' in sample:     # deferred tail: uint8 [H,W,3] + uint8 [H,W], or at level 3 the source index + geometry record (+ recorded augmentation outcomes)
             return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in sample.items()}
         img = torch.from_numpy(np.ascontiguousarray(np.asarray(sample['image'], dtype=np.float32).transpose(2, 0, 1)))
         mp = torch.from_numpy(np.ascontiguousarray(np.asarray(sample['map']).astype(np.uint8).transpose(2, 0, 1))).float()

@@ -9,6 +9,7 @@ from glob import glob
 from PIL import Image
 from torch.utils.data import Dataset
 
+from . import custom_transforms
 from .mypath import Path
 
 
@@ -33,6 +34,8 @@ class FundusSegmentation(Dataset):
 
     def __getitem__(self, index):
         sample = {'image': self.image_pool[index], 'label': self.label_pool[index], 'img_name': self.img_name_pool[index]}
+        if custom_transforms.DEVICE_TAIL >= 3:       # the Trainer gathers the pixels from its device-resident copy of the pools
+            sample['src_index'] = int(index)
         return self.transform(sample) if self.transform is not None else sample
 
     def __str__(self):

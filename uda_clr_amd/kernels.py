@@ -141,6 +141,8 @@ SYMBOLS = {
     "uda_field_smooth": (_I, [_P, _I, _I, _I, _P, _I, _D, _P, _P, _P]),
     "uda_elastic_warp": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "uda_photometric_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "uda_geometry_u8_workspace_bytes": (_U, [_I, _I]),
+    "uda_geometry_u8": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _U, _P]),
 }
 
 
@@ -1148,6 +1150,27 @@ class HipKernels:
                                              sp_value.data_ptr(), sp_pos.shape[1], lut.data_ptr(), erase_box.data_ptr(),
                                              self._stream()))
         return image_u8
+
+    def geometry_u8(self, image_pool, label_pool, offsets, sizes, src_index, records, S):
+        """scale-crop, rotate and flip of a batch from the device-resident source pools and the recorded draws:
+        -> (uint8 [B,S,S,3], uint8 [B,S,S])."""
+        for t in (image_pool, label_pool):
+            self._dev(t)
+            assert t.dtype == torch.uint8 and t.is_contiguous()
+        for t in (offsets, sizes, src_index, records):
+            assert t.is_cuda and t.is_contiguous()
+        n = offsets.numel()
+        B = src_index.numel()
+        assert offsets.dtype == src_index.dtype == torch.int64 and sizes.dtype == records.dtype == torch.int32
+        assert tuple(sizes.shape) == (n, 2) and tuple(records.shape) == (B, 10)
+        assert label_pool.numel() * 3 == image_pool.numel()
+        io = torch.empty(B, S, S, 3, dtype=torch.uint8, device=image_pool.device)
+        lo = torch.empty(B, S, S, dtype=torch.uint8, device=image_pool.device)
+        ws = self._ws(image_pool, self.lib.uda_geometry_u8_workspace_bytes(B, S))
+        self._ck(self.lib.uda_geometry_u8(image_pool.data_ptr(), label_pool.data_ptr(), offsets.data_ptr(), sizes.data_ptr(), n,
+                                          src_index.data_ptr(), records.data_ptr(), B, S, io.data_ptr(), lo.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), self._stream()))
+        return io, lo
 
     def postprocess(self, pred, thr_cup, thr_disc, sweeps=None):
         """pred f32 [B,2,H,W] probabilities -> uint8 [B,2,H,W] masks after the reference's evaluation post-processing.

@@ -276,6 +276,59 @@ def photometric_u8(image_u8, sp_pos, sp_count, sp_value, lut, erase_box):
                                     lut.contiguous(), erase_box.contiguous())
 
 
+class SourcePool(object):
+    """A decoded dataset resident on the device for ``geometry_u8``: every image in one flat uint8 buffer, every mask in
+    another, an int64 table of first pixels and an int32 (H0, W0) table, so sources of different sizes share a batch.
+    4 B per source pixel (about 1 GB for 400 images of 800 x 800)."""
+    def __init__(self, images, labels, device):
+        import numpy as np
+        imgs = [np.ascontiguousarray(np.asarray(i, dtype=np.uint8)) for i in images]
+        labs = [np.ascontiguousarray(np.asarray(l, dtype=np.uint8)) for l in labels]
+        if not imgs or len(imgs) != len(labs):
+            raise ValueError("SourcePool needs as many masks as images, and at least one")
+        for i, l in zip(imgs, labs):
+            if i.ndim != 3 or i.shape[2] != 3 or l.shape != i.shape[:2]:
+                raise ValueError("SourcePool: sources are [H,W,3] images with [H,W] masks (got %s and %s)" % (i.shape, l.shape))
+        self.sizes_host = np.array([l.shape for l in labs], np.int32)
+        px = self.sizes_host[:, 0].astype(np.int64) * self.sizes_host[:, 1]
+        self.image_pool = torch.from_numpy(np.concatenate([i.reshape(-1) for i in imgs])).to(device)
+        self.label_pool = torch.from_numpy(np.concatenate([l.reshape(-1) for l in labs])).to(device)
+        self.offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(px)[:-1]]).astype(np.int64)).to(device)
+        self.sizes = torch.from_numpy(self.sizes_host).to(device)
+
+    def __len__(self):
+        return int(self.sizes_host.shape[0])
+
+
+def geometry_u8(pool, src_index, records, size=None):
+    """Device-side ``RandomScaleCrop`` / ``RandomCrop`` -> ``RandomRotate`` -> ``RandomFlip`` (custom_transforms.py:152-182,
+    208-223,315-355) of a batch: ``pool`` a SourcePool, ``src_index`` [B] the samples' dataset indices, ``records`` int32
+    [B,10] the draws the workers recorded (dataloaders.custom_transforms.GEOM_*).  -> uint8 [B,S,S,3], uint8 [B,S,S], byte for
+    byte what PIL gives.  Records that are still on the host (what the Trainer hands over) are checked here; the kernel only keeps a
+    bad one in bounds.  Records already on the device are not checked: pass ``size`` with them to avoid reading it back."""
+    from .dataloaders import custom_transforms as tr
+    records = records.reshape(-1, tr.GEOM_R)
+    src_index = src_index.reshape(-1)
+    if not records.is_cuda:
+        r, idx = records.numpy(), src_index.numpy()
+        if idx.min() < 0 or idx.max() >= len(pool):
+            raise ValueError("geometry_u8: source index outside the pool of %d" % len(pool))
+        if (r[:, tr.GEOM_SIZE] != r[0, tr.GEOM_SIZE]).any() or r[0, tr.GEOM_SIZE] <= 0:
+            raise ValueError("geometry_u8: one positive crop size per batch")
+        hw = pool.sizes_host[idx]
+        sc = r[:, tr.GEOM_SCALED] != 0
+        if (sc & ((r[:, tr.GEOM_W] * 5 < hw[:, 1] * 2) | (r[:, tr.GEOM_H] * 5 < hw[:, 0] * 2))).any():
+            raise ValueError("geometry_u8: a scaled size below 0.4 of its source")
+        S = int(r[0, tr.GEOM_SIZE])
+    elif size is not None:
+        S = int(size)                                   # device records: the caller names the crop size, nothing is read back
+    else:
+        S = int(records[0, tr.GEOM_SIZE].item())        # device records without `size`: one host synchronisation, and no range checks
+    dev = pool.image_pool.device
+    return kernels().geometry_u8(pool.image_pool, pool.label_pool, pool.offsets, pool.sizes,
+                                 src_index.to(dev).to(torch.int64).contiguous(), records.to(dev).to(torch.int32).contiguous(), S)
+
+
 def photometric_augment(images, generator=None):
     """Device-side photometric augmentation of a [-1,1] image batch in the spirit of utils/Utils.py:33-43
     (brightness/contrast + saturation jitter with p=0.8, grayscale with p=0.2, 5x5 Gaussian blur with

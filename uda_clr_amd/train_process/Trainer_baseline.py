@@ -100,7 +100,7 @@ class Trainer(TrainerBase):
             self.iteration = batch_idx + self.epoch * nS
             assert self.model_gen.training
             self.optim_gen.zero_grad()
-            sampleS = self._decode(sampleS)
+            sampleS = self._decode(sampleS, self.domain_loaderS)
             imageS = self._to(sampleS['image'])
             target_map = self._to(sampleS['map'])
             target_boundary = self._to(sampleS['boundary'])

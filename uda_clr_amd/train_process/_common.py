@@ -76,6 +76,8 @@ class HipOps:
         self.normalize_tf = ops.normalize_tf
         self.elastic_deform = ops.elastic_deform
         self.photometric_u8 = ops.photometric_u8
+        self.geometry_u8 = ops.geometry_u8
+        self.SourcePool = ops.SourcePool
         self.consistency_loss = ops.consistency_loss
         self.proto_align = ops.proto_align
         self.adv_loss = ops.adv_loss
@@ -246,13 +248,40 @@ class TrainerBase(object):
     def _to(self, t):
         return t.to(self._device(), non_blocking=True)
 
-    def _decode(self, sample):
+    def _source_pool(self, source):
+        """UDA_CLR_DEVICE_INPUT=3: the device-resident copy of the dataset a loader draws from (its decoded images and masks,
+        uploaded once and cached per dataset object).  ``source`` is the loader or the dataset; shard_loader's wrappers and
+        torch's Subset are looked through."""
+        ds = source
+        while not hasattr(ds, 'image_pool'):
+            inner = getattr(ds, 'loader', None)
+            if inner is None:
+                inner = getattr(ds, 'dataset', None)
+            if inner is None:
+                raise ValueError('UDA_CLR_DEVICE_INPUT=3: %r holds no decoded image_pool / label_pool to upload' % (source,))
+            ds = inner
+        pools = self.__dict__.setdefault('_source_pools', {})
+        if id(ds) not in pools:
+            pools[id(ds)] = (ds, self.ops.SourcePool(ds.image_pool, ds.label_pool, self._device()))      # keeps ds alive: ids are not reused
+        return pools[id(ds)][1]
+
+    def _decode(self, sample, dataset=None):
         """A batch whose Normalize_tf + ToTensor tail was deferred (dataloaders.custom_transforms.DEVICE_TAIL: uint8 image and
-        grey mask) is decoded here, on the device, for the whole batch; any other sample passes through."""
-        if 'image_u8' not in sample:
+        grey mask) is decoded here, on the device, for the whole batch; any other sample passes through.  At level 3 the batch
+        holds source indices and geometry records instead of pixels; ``dataset`` (the loader it came from, or its dataset) names
+        the pool they index.  Order: geometry, elastic, photometric, normalize_tf."""
+        if 'src_index' in sample:
+            if dataset is None:
+                raise ValueError("a batch of source indices (UDA_CLR_DEVICE_INPUT=3) cannot be decoded without its dataset: "
+                                 "call _decode(sample, dataset=loader)")
+            iu, lu = self.ops.geometry_u8(self._source_pool(dataset), sample['src_index'], sample['geom'])
+        elif 'image_u8' in sample:
+            iu, lu = self._to(sample['image_u8']), self._to(sample['label_u8'])
+        else:
             return sample
-        iu, lu = self._to(sample['image_u8']), self._to(sample['label_u8'])
         if 'aug_lut' in sample:          # UDA_CLR_DEVICE_INPUT=2: the recorded elastic / photometric outcomes, in the chain's order
+            # (a chain without those transforms - the validation chain - still carries identity records from level 2 on and pays these
+            # launches on them: same bytes out, left as it is)
             # 'aug_noise' ([B,2,H,W] float64): the uniform fields of the elastic transform when a caller supplies them (the parity
             # tests hand over numpy's draw); normally absent - the noise then comes from the device generator
             noise = self._to(sample['aug_noise']).transpose(0, 1).contiguous() if 'aug_noise' in sample else None
@@ -296,7 +325,7 @@ class TrainerBase(object):
         acc = [0.0] * 7
         with torch.no_grad():
             for sample in progress(self.val_loader, total=n, desc='Valid iteration=%d' % self.iteration, ncols=80, leave=False):
-                sample = self._decode(sample)
+                sample = self._decode(sample, self.val_loader)
                 data, target_map = self._to(sample['image']), self._to(sample['map'])
                 predictions = self.model_gen(data)[0]
                 loss = F.binary_cross_entropy_with_logits(predictions, target_map).item()
