@@ -398,7 +398,25 @@ size_t uda_postprocess_workspace_bytes(int B, int H, int W);
 int uda_postprocess(const float* pred, int B, int H, int W, float thr_cup, float thr_disc, int sweeps, uint8_t* out,
                     int* not_converged, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- device-side tail of the input pipeline.  The reference's dataloader workers run these per sample
+/* ---- exact surface distances of one (prediction, ground truth) mask pair per image and class: what the per-image ASD /
+ * ASSD / Hausdorff figures of an evaluation are closed forms of.  The reference keeps the 1-D scan of a squared distance
+ * transform (utils/metrics.py:62-68, `_upscan`) without its callers; the masks are those of utils/Utils.py:438-463.
+ * Conventions of medpy.metric.binary, distances in pixels:
+ *   border(M) = M & ~erosion(M, 4-connected cross), everything outside the image unset;
+ *   d2_X[y,x] = exact squared Euclidean distance (an integer) to the nearest pixel of border(X);
+ *   directed entry A -> G:  n = |border(A)|,  s = sum over border(A) of sqrt(d2_G),  m = max over border(A) of d2_G.
+ * pred, gt uint8 [B,2,H,W], nonzero = set.  1 <= H, W <= 1024 (and B <= 8192); anything else, or a workspace below
+ * uda_surface_distance_workspace_bytes, returns the error before any launch.
+ *   table  double [B][2 class][2 dir: 0 = pred -> gt, 1 = gt -> pred][3: n, s, m].  If either border set of an (image, class)
+ *          is empty, both its entries are (n as counted, NaN, -1).  s is summed in a fixed order: bit-identical from run to
+ *          run and independent of the batch an image sits in.
+ *   counts int64 [B][2][3] = |pred & gt|, |pred|, |gt| (the per-image Dice counts).
+ *   d2     null, or int32 [B][2][2: 0 = to the gt border, 1 = to the pred border][H][W]; -1 where that border set is empty. */
+size_t uda_surface_distance_workspace_bytes(int B, int H, int W);
+int uda_surface_distance(const uint8_t* pred, const uint8_t* gt, int B, int H, int W, double* table, int64_t* counts,
+                         int32_t* d2, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- device-side tail of the input pipeline. The reference's dataloader workers run these per sample
  * on the CPU with scipy.ndimage; here they run per uint8 BATCH on the GPU, bit-identical to the scipy calls.
  * uda_normalize_tf: dataloaders/custom_transforms.py:432-466 (Normalize_tf), :414-429 (GetBoundary), :504-507 (ToTensor).
  *   image_hwc uint8 [B,H,W,3], label uint8 [B,H,W] (grey code: > 200 background, 51..200 disc rim, <= 50 cup) ->

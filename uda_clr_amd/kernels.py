@@ -136,6 +136,8 @@ SYMBOLS = {
     "uda_upconv_bwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P]),
     "uda_postprocess_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_postprocess": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _U, _P]),
+    "uda_surface_distance_workspace_bytes": (_U, [_I, _I, _I]),
+    "uda_surface_distance": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _U, _P]),
     "uda_normalize_tf_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_normalize_tf": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _U, _P]),
     "uda_field_smooth": (_I, [_P, _I, _I, _I, _P, _I, _D, _P, _P, _P]),
@@ -1190,6 +1192,26 @@ class HipKernels:
                 return out
             n *= 2
         raise UdaError("uda_postprocess: label propagation did not converge after %d sweeps" % n)
+
+    def surface_distance(self, pred_u8, gt_u8, want_d2=False):
+        """uint8 [B,2,H,W] masks (nonzero = set) -> (table f64 [B,2,2,3], counts i64 [B,2,3][, d2 i32 [B,2,2,H,W]]) on the
+        device: per image and class the directed entries (n, sum of distances, max squared distance) pred -> gt and gt -> pred
+        between the masks' borders, and the Dice counts (include/uda_clr_hip.h, uda_surface_distance)."""
+        for t in (pred_u8, gt_u8):
+            self._dev(t)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != 2:
+                raise ValueError("surface_distance: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (t.dtype, tuple(t.shape)))
+        if pred_u8.shape != gt_u8.shape:
+            raise ValueError("surface_distance: shapes differ: %s and %s" % (tuple(pred_u8.shape), tuple(gt_u8.shape)))
+        B, _, H, W = pred_u8.shape
+        dev = pred_u8.device
+        table = torch.empty(B, 2, 2, 3, dtype=torch.float64, device=dev)
+        counts = torch.empty(B, 2, 3, dtype=torch.int64, device=dev)
+        d2 = torch.empty(B, 2, 2, H, W, dtype=torch.int32, device=dev) if want_d2 else None
+        ws = self._ws(pred_u8, self.lib.uda_surface_distance_workspace_bytes(B, H, W))
+        self._ck(self.lib.uda_surface_distance(pred_u8.data_ptr(), gt_u8.data_ptr(), B, H, W, table.data_ptr(), counts.data_ptr(),
+                                               _ptr(d2), ws.data_ptr(), ws.numel(), self._stream()))
+        return (table, counts, d2) if want_d2 else (table, counts)
 
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
         for t in (params, grads, exp_avg, exp_avg_sq):

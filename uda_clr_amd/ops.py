@@ -376,3 +376,27 @@ def consistency_loss(oT_aug, oT, mask_0, mask_1, epoch, aug_weight=1.0):
 def seg_counts(pred, target, thr=0.75):
     """int64 [C,3] on the host: (intersection, predicted, ground truth) for sigmoid(pred) > thr."""
     return kernels().seg_counts(pred.detach().contiguous().float(), target.detach().contiguous().float(), thr).cpu()
+
+
+def _mask_u8(m):
+    """[B,2,H,W] uint8 / bool / float mask -> uint8 0/1 (set means > 0.5, which for uint8 and bool is nonzero)."""
+    if m.dim() != 4 or m.shape[1] != 2:
+        raise ValueError("expected a [B, 2, H, W] mask, got %s" % (tuple(m.shape),))
+    return (m if m.dtype == torch.bool else m > 0.5).to(torch.uint8).contiguous()
+
+
+def surface_distances(pred_mask, gt_mask):
+    """Per image and class (cup, disc) the surface-distance table and the Dice counts of a [B,2,H,W] mask pair (uint8, bool or
+    float; set means > 0.5), on the host after one synchronising copy:
+        table  float64 [B,2,2,3]: direction 0 = pred -> gt, 1 = gt -> pred; (n border pixels, sum of their distances to the other
+               border, max squared distance); (n, NaN, -1) where either border set is empty
+        counts int64 [B,2,3]: |pred & gt|, |pred|, |gt|
+    as numpy arrays (``utils.metrics.surface_metrics_from_table`` / ``dice_per_image`` turn them into ASD, ASSD, HD and Dice).
+    Runs on the device (uda_surface_distance); CPU tensors are moved there."""
+    if not (pred_mask.is_cuda and gt_mask.is_cuda) and not torch.cuda.is_available():
+        raise RuntimeError("uda_clr_amd surface distances compute only on the MI355X HIP kernels (there is no CPU fallback)")
+    dev = pred_mask.device if pred_mask.is_cuda else (gt_mask.device if gt_mask.is_cuda else torch.device("cuda"))
+    table, counts = kernels().surface_distance(_mask_u8(pred_mask.detach().to(dev)), _mask_u8(gt_mask.detach().to(dev)))
+    B = table.shape[0]
+    packed = torch.cat([table.reshape(-1), counts.view(torch.float64).reshape(-1)]).cpu().numpy()      # the one copy (it synchronises)
+    return packed[:B * 12].reshape(B, 2, 2, 3), packed[B * 12:].view("int64").reshape(B, 2, 3)
