@@ -1249,24 +1249,10 @@ CASES += [
 def _scipy_postprocess(prob, thr_cup, thr_disc):
     """utils/Utils.py:427-463 with skimage's two calls replaced by their scipy.ndimage equivalents: binary_erosion(diamond(7))
     = ndimage.binary_erosion(structure=L1 ball, border_value=1) (skimage erodes with the outside set), measure.label =
-    ndimage.label with the full 3x3 structure (both number components in raster order of their first pixel)."""
-    import numpy as np
-    import scipy.signal
-    from scipy import ndimage
-    yy, xx = np.mgrid[-7:8, -7:8]
-    diamond = (np.abs(yy) + np.abs(xx)) <= 7
-    out = np.zeros(prob.shape, np.uint8)
-    for c, thr in ((0, thr_cup), (1, thr_disc)):
-        m = (prob[c] > thr).astype(np.uint8)
-        for _ in range(5):
-            m = scipy.signal.medfilt2d(m, 7)
-        m = ndimage.binary_erosion(m, structure=diamond, border_value=1).astype(np.uint8)
-        lab, n = ndimage.label(m, structure=np.ones((3, 3)))
-        if n:
-            areas = np.bincount(lab.ravel())[1:]
-            m[lab != int(np.argmax(areas)) + 1] = 0
-        out[c] = ndimage.binary_fill_holes(m.astype(int)).astype(np.uint8)
-    return out
+    ndimage.label with the full 3x3 structure (both number components in raster order of their first pixel).  The chain itself
+    is stated once, in tests/postproc_shapes.py (stages), which also keeps the masks after the erosion and after the keep."""
+    import postproc_shapes
+    return postproc_shapes.stages(prob, thr_cup, thr_disc)["filled"]
 
 
 def case_postprocess(B, H, W, seed=61):

@@ -99,7 +99,10 @@ __global__ __launch_bounds__(256) void pp_propagate_kernel(const int* __restrict
     }
     __syncthreads();
     bool any = false;
-    for (int sweep = 0; sweep < 4 * PP_T; ++sweep) {          // bounded: a tile's longest in-tile path is < 4 * PP_T steps for blob-like sets
+    // Bounded: a pass moves a label at least one step along its in-tile path.  4 * PP_T passes cover the sets the medians and the
+    // erosion leave (blobs, walls, corridors); a 1-pixel serpentine filling the tile would need about PP_T * PP_T / 2.  Leaving at
+    // the bound is still correct: `any` is set then, the launch counts as unfinished and the next one continues from its output.
+    for (int sweep = 0; sweep < 4 * PP_T; ++sweep) {
         if (threadIdx.x == 0) again = 0;
         __syncthreads();
         bool mine = false;

@@ -1176,8 +1176,11 @@ class HipKernels:
 
     def postprocess(self, pred, thr_cup, thr_disc, sweeps=None):
         """pred f32 [B,2,H,W] probabilities -> uint8 [B,2,H,W] masks after the reference's evaluation post-processing.
-        Runs the tile-wise propagations for ``sweeps`` launches (default: enough for any shape whose geodesic paths cross each
-        tile row / column at most twice) and repeats with twice as many while the device reports unfinished tiles."""
+        Runs the tile-wise propagations for ``sweeps`` launches and repeats with twice as many, up to six attempts, while the
+        device reports unfinished tiles; then raises.  A launch carries a label from one 32 x 32 tile into the next, so the
+        default, 2 * (tile rows + tile columns) + 4, is enough when the path inside a component to its first pixel (and inside
+        the background to the image border) crosses each line between two tile rows or tile columns at most twice: any convex
+        blob, a ring.  A spiral wall of three turns on 256 x 256 needs 50 launches against 36 and takes the second attempt."""
         self._dev(pred)
         assert pred.dtype == torch.float32 and pred.is_contiguous() and pred.dim() == 4 and pred.shape[1] == 2
         B, _, H, W = pred.shape
@@ -1191,7 +1194,7 @@ class HipKernels:
             if int(flags.sum()) == 0:            # host sync: evaluation path only
                 return out
             n *= 2
-        raise UdaError("uda_postprocess: label propagation did not converge after %d sweeps" % n)
+        raise UdaError("uda_postprocess: label propagation did not converge after %d sweeps" % (n // 2))   # the last attempt's
 
     def surface_distance(self, pred_u8, gt_u8, want_d2=False):
         """uint8 [B,2,H,W] masks (nonzero = set) -> (table f64 [B,2,2,3], counts i64 [B,2,3][, d2 i32 [B,2,2,H,W]]) on the
