@@ -137,35 +137,51 @@ int uda_conv_wgrad(const uda_wgrad_args_t* a, void* stream);
  * pixel range, red: the wgrad_reduce_kernel variant that sums them) */
 int uda_conv_wgrad_route(const uda_wgrad_args_t* a, char* buf, int len);
 
-/* ---- depthwise 3x3 (mobilenet.py:39,53): stride 1|2, dilation 1|2|4, "pad 0 on a padded input"; C <= 1024 on these
- * kernels, C <= 2048 routed to the channel-blocked ones below.
- * border_mode 0: out-of-image taps read 0; 1: they read act(shift[c]) (quirk Q1). */
+/* ---- depthwise 3x3 (mobilenet.py:39,53; Aligned Xception, networks/backbone/xception.py:17-31): stride 1|2, dilation >= 1
+ * (1|2|4 in the networks), "pad 0 on a padded input"; C a multiple of 4.
+ * border_mode 0: out-of-image taps read 0 (xception.py:8-14, fixed_padding after the activation); 1: they read act(shift[c]) (quirk Q1).
+ * Three kernel families serve it: UDA_DW_FLAT (all C/4 channel groups of a pixel in one workgroup; C <= 1024, the input gradient
+ * any C), UDA_DW_TILED (32 channels x a halo tile in LDS; forward and weight gradient, dilation <= 2, C <= 1024) and UDA_DW_CB
+ * (channel-blocked strips, C <= 2048).  `family` = UDA_DW_AUTO lets the library's launch plan choose by shape: channel-blocked
+ * for C > 1024 and for dilation > 2 at C >= 1024, else tiled where it exists (forward / weight gradient at dilation <= 2), else
+ * flat.  Any other value pins that family (kernel tests and measurements); a family that cannot serve the shape is an error.
+ * The plan is a function of the arguments alone (no pointer is dereferenced, no environment read) and the only place where a
+ * kernel, its grid or a template variant is chosen.  Workspace of the weight gradient: uda_dwconv_workspace_bytes, enough for
+ * whichever family serves C. */
+#define UDA_DW_AUTO 0
+#define UDA_DW_FLAT 1
+#define UDA_DW_TILED 2
+#define UDA_DW_CB 3
+#define UDA_DW_FWD 0
+#define UDA_DW_DGRAD 1
+#define UDA_DW_WGRAD 2
 uint64_t uda_dwconv_workspace_bytes(int64_t Pout, int C);
 int uda_dwconv_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
-                   float* y, int64_t ldy, double* stats /* [SLOTS][2][C] or NULL */, void* stream);
+                   float* y, int64_t ldy, double* stats /* [SLOTS][2][C] or NULL */, int family, void* stream);
 int uda_dwconv_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
-                     int N, int H, int W, float* dx, int64_t lddx, void* stream);
+                     int N, int H, int W, float* dx, int64_t lddx, int family, void* stream);
 int uda_dwconv_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
                      int border_mode, float* dw /* [C][9] */, float* workspace,
-                     uint64_t workspace_bytes, void* stream);
+                     uint64_t workspace_bytes, int family, void* stream);
+/* The launch planned for op (UDA_DW_FWD / _DGRAD / _WGRAD) on an N x H x W x C input grid, as uda_conv_route: a short stable
+ * text "<op> <kernel> ..." followed by the grid, the pixel lanes of a workgroup and lg (log2 of the float4 groups of a channel
+ * block): "fwd tiled-8x16 grid 12x30 lds 19584", "dgrad flat grid 8192", "wgrad cb grid 3x6 lanes 4 lg 6"; "none" for arguments
+ * the entry refuses.  Returns the text's length as snprintf does, -1 without a buffer. */
+int uda_dwconv_route(int op, int N, int H, int W, int C, int stride, int dil, int family, char* buf, int len);
+/* every "<op> <kernel>" uda_dwconv_route can begin with, one per line */
+const char* uda_dwconv_route_list(void);
 
-/* ---- channel-blocked depthwise 3x3 (Aligned Xception, networks/backbone/xception.py:17-31: 728 ... 2048 channels, stride
- * 1|2, dilation 1|2|4, zero border after the activation - fixed_padding, :8-14).  Same arguments and layouts as the three
- * entries above, C any multiple of 4 up to 2048; those entries route C > 1024 (and dilation 4 at C >= 1024) here.  Workspace: uda_dwconv_workspace_bytes. */
-int uda_dwconv_cb_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
-                      float* y, int64_t ldy, double* stats /* [SLOTS][2][C] or NULL */, void* stream);
-int uda_dwconv_cb_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
-                        int N, int H, int W, float* dx, int64_t lddx, void* stream);
-int uda_dwconv_cb_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
-                        int border_mode, float* dw /* [C][9] */, float* workspace,
-                        uint64_t workspace_bytes, void* stream);
-
-/* ---- stem conv 3x3 stride 2 pad 1, 3 -> 32, NCHW image in, NHWC out (mobilenet.py:10) */
+/* ---- stem conv 3x3 stride 2 pad 1, 3 -> 32, NCHW image in, NHWC out (mobilenet.py:10).  Output rows that are a multiple of 256
+ * pixels wide run on row-staged kernels (the weight gradient only with dy 16-byte aligned and lddy % 4 == 0), anything else on
+ * the per-pixel kernels: the stem's launch plan, what uda_stem_route reports. */
 uint64_t uda_stem_workspace_bytes(int64_t Pout);
 int uda_stem_fwd(const float* x, int N, int H, int W, const float* w, float* y, int64_t ldy,
                  double* stats /* [SLOTS][2][32] or NULL */, void* stream);
 int uda_stem_wgrad(const float* x, int N, int H, int W, const float* dy, int64_t lddy, float* dw,
                    float* workspace, uint64_t workspace_bytes, void* stream);
+/* op UDA_DW_FWD or UDA_DW_WGRAD (lddy, dy_aligned16: the weight gradient's dy): "fwd rows", "fwd pixels", "wgrad rows" or
+ * "wgrad pixels", then the grid; "none" for refused arguments.  Same contract as uda_dwconv_route. */
+int uda_stem_route(int op, int N, int H, int W, int64_t lddy, int dy_aligned16, char* buf, int len);
 
 /* ---- ResNet-101 variant (BASELINE.json configs[4]; networks/backbone/resnet.py)
  * conv1 7x7 stride 2 pad 3, 3 -> 64, NCHW image in, NHWC out (resnet.py:59,114); W % 8 == 0 */

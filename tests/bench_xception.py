@@ -6,8 +6,8 @@
 
 Workloads: ``source_only`` (Trainer_baseline's step, B images) and ``prototype_full`` (Trainer_prototype_full.train_step,
 B source + B target images), both on bench.py's synthetic batches, timed between device synchronisations after warm-up.
-``--kernels`` times the depthwise entry points at Xception's 512^2 / B = 16 shapes on both kernel families (routed
-uda_dwconv_* and channel-blocked uda_dwconv_cb_*) and reports achieved bytes/s from ALGORITHMIC bytes (input + output once).
+``--kernels`` times the depthwise entry points at Xception's 512^2 / B = 16 shapes with the kernel family the library's
+launch plan chooses (family "") and pinned to the channel-blocked one (family "cb"), and reports achieved bytes/s from ALGORITHMIC bytes (input + output once).
 """
 import argparse
 import json

@@ -202,7 +202,13 @@ def case_wgrad(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, seed=2, origin
     return run
 
 
-def case_dw(N, H, W, C, stride, dil, border, seed=3):
+def _entry(route):
+    return " ".join(route.split()[:2])          # "<family> <tile>" of a dense route, "<op> <kernel>" of a depthwise / stem one
+
+
+def case_dw(N, H, W, C, stride, dil, border, seed=3, *, route):
+    """route: the "<op> <kernel>" HipKernels.dw_route must begin with for the forward, input-gradient and weight-gradient call
+    (asserted before each call, and without a GPU by test_dw_plan_cpu.py)"""
     def run(dev):
         g = gen(seed)
         src = make_src(N, H, W, C, g, True, ACT_RELU6)
@@ -217,6 +223,9 @@ def case_dw(N, H, W, C, stride, dil, border, seed=3):
         SPEC.dwconv_fwd(src, w9, stride, dil, border, y_r, st_r)
         y_h, st_h = to_dev(padded(Po, C, g), dev), torch.zeros(16, 2, C, dtype=torch.float64, device=dev)
         sh = act_to(src, dev)
+        for op, want in zip(("fwd", "dgrad", "wgrad"), route):
+            got = _entry(K.dw_route(op, N, H, W, C, stride, dil))
+            assert got == want, "planned route %r, the case declares %r" % (got, want)
         K.dwconv_fwd(sh, w9h, stride, dil, border, y_h, st_h)
         errs += [rel(y_h, y_r), rel(st_h.sum(0), st_r.sum(0))]
         dy = padded(Po, C, g)
@@ -231,10 +240,20 @@ def case_dw(N, H, W, C, stride, dil, border, seed=3):
         K.dwconv_wgrad(sh, to_dev(dy, dev), stride, dil, border, dw_h)
         errs.append(rel(dw_h, dw_r))
         return max(errs), 3e-5
+    run.dw_query, run.route = dict(N=N, H=H, W=W, C=C, stride=stride, dil=dil), route
     return run
 
 
-def case_stem(N, H, W, seed=4):
+def _stem_dy(Po, g, dy_offset):
+    """the stem's output gradient, [Po, 32]: padded(), or with dy_offset = 1 columns 1..32 of a poisoned [Po, 33] matrix"""
+    if not dy_offset:
+        return padded(Po, 32, g)
+    return _poison(torch.empty(Po, 33))[:, 1:33].copy_(torch.randn(Po, 32, generator=g))
+
+
+def case_stem(N, H, W, seed=4, dy_offset=0, *, route):
+    """route: the "<op> <kernel>" HipKernels.stem_route must begin with for the forward and the weight-gradient call.
+    dy_offset = 1: dy is columns 1..32 of a [Po, 33] matrix - neither 16-byte aligned nor with a row stride that is a multiple of 4."""
     def run(dev):
         g = gen(seed)
         x = torch.randn(N, 3, H, W, generator=g)
@@ -244,12 +263,21 @@ def case_stem(N, H, W, seed=4):
         SPEC.stem_fwd(x, w, y_r, st_r)
         K = hip()
         y_h, st_h = to_dev(padded(Po, 32, g), dev), torch.zeros(16, 2, 32, dtype=torch.float64, device=dev)
-        K.stem_fwd(x.to(dev), w.to(dev), y_h, st_h)
-        dy = padded(Po, 32, g)
+        xh = x.to(dev)
+        assert _entry(K.stem_route("fwd", xh)) == route[0], (K.stem_route("fwd", xh), route)
+        K.stem_fwd(xh, w.to(dev), y_h, st_h)
+        dy = _stem_dy(Po, g, dy_offset)
         dw_r, dw_h = torch.empty(32, 3, 3, 3), torch.empty(32, 3, 3, 3, device=dev)
         SPEC.stem_wgrad(x, dy, dw_r)
-        K.stem_wgrad(x.to(dev), to_dev(dy, dev), dw_h)
+        dyh = _poison(torch.empty(Po, 33, device=dev))[:, 1:33].copy_(dy) if dy_offset else to_dev(dy, dev)
+        assert (dyh.stride(0), dyh.data_ptr() % 16 == 0) == (q["lddy"], q["aligned"]), "stem_query does not describe the dy of this call"
+        assert _entry(K.stem_route("wgrad", xh, dyh)) == route[1], (K.stem_route("wgrad", xh, dyh), route)
+        K.stem_wgrad(xh, dyh, dw_h)
         return max(rel(y_h, y_r), rel(st_h.sum(0), st_r.sum(0)), rel(dw_h, dw_r)), 3e-5
+    # what the weight gradient's route depends on besides the image: dy's row stride and 16-byte alignment, read off a one-row dy
+    d1 = _stem_dy(1, gen(seed), dy_offset)
+    q = dict(N=N, H=H, W=W, lddy=d1.stride(0), aligned=d1.storage_offset() % 4 == 0)
+    run.stem_query, run.route = q, route
     return run
 
 
@@ -587,15 +615,21 @@ CASES = [
     ("wgrad3x3 320->256 dil6", case_wgrad(2, 8, 8, 320, 256, 3, 6, lazy=False, route="wgrad-ws 128x128 xf0 S=1 red8")),
     ("wgrad3x3 64->40 dil2", case_wgrad(1, 11, 9, 64, 40, 3, 2, route="wgrad-ws 128x128 xf1 S=1 red8")),
     # depthwise
-    ("dw 32 s1 d1 border0", case_dw(2, 16, 16, 32, 1, 1, 0)),
-    ("dw 96 s2 d1 border1", case_dw(2, 16, 16, 96, 2, 1, 1)),
-    ("dw 144 s1 d1 border1 odd", case_dw(1, 13, 11, 144, 1, 1, 1)),
-    ("dw 960 s1 d2 border1", case_dw(2, 8, 8, 960, 1, 2, 1)),
-    ("dw 576 s1 d1 border1", case_dw(2, 8, 8, 576, 1, 1, 1)),
-    ("stem 2x3x32x32", case_stem(2, 32, 32)),
-    ("stem 1x3x48x80", case_stem(1, 48, 80)),
-    ("stem 2x3x20x512 (row-staged kernels: Wo = 256)", case_stem(2, 20, 512)),
-    ("stem 1x3x7x1024 (row-staged kernels: two segments per row)", case_stem(1, 7, 1024)),
+    ("dw 32 s1 d1 border0", case_dw(2, 16, 16, 32, 1, 1, 0, route=("fwd tiled-8x16", "dgrad flat", "wgrad tiled-8x16"))),
+    ("dw 96 s2 d1 border1", case_dw(2, 16, 16, 96, 2, 1, 1, route=("fwd tiled-8x8", "dgrad flat", "wgrad tiled-8x8"))),
+    ("dw 144 s1 d1 border1 odd", case_dw(1, 13, 11, 144, 1, 1, 1, route=("fwd tiled-8x16", "dgrad flat", "wgrad tiled-8x16"))),
+    ("dw 960 s1 d2 border1", case_dw(2, 8, 8, 960, 1, 2, 1, route=("fwd tiled-8x16", "dgrad flat", "wgrad tiled-8x16"))),
+    ("dw 576 s1 d1 border1", case_dw(2, 8, 8, 576, 1, 1, 1, route=("fwd tiled-8x16", "dgrad flat", "wgrad tiled-8x16"))),
+    # the flat forward / weight-gradient kernels with the quirk-Q1 border: MobileNetV2's dilation-4 blocks at output stride 8
+    ("dw 960 s1 d4 border1 (flat: one pixel lane, 16 idle threads)", case_dw(2, 8, 8, 960, 1, 4, 1, route=("fwd flat", "dgrad flat", "wgrad flat"))),
+    ("dw 64 s1 d4 border1 odd (flat: 16 pixel lanes, extents below the dilated window)",
+     case_dw(1, 9, 7, 64, 1, 4, 1, route=("fwd flat", "dgrad flat", "wgrad flat"))),
+    ("stem 2x3x32x32", case_stem(2, 32, 32, route=("fwd pixels", "wgrad pixels"))),
+    ("stem 1x3x48x80", case_stem(1, 48, 80, route=("fwd pixels", "wgrad pixels"))),
+    ("stem 2x3x20x512 (row-staged kernels: Wo = 256)", case_stem(2, 20, 512, route=("fwd rows", "wgrad rows"))),
+    ("stem 1x3x7x1024 (row-staged kernels: two segments per row)", case_stem(1, 7, 1024, route=("fwd rows", "wgrad rows"))),
+    ("stem 2x3x20x512 dy off 16-byte alignment (row-staged forward, per-pixel weight gradient)",
+     case_stem(2, 20, 512, dy_offset=1, route=("fwd rows", "wgrad pixels"))),
     # batch norm pieces
     ("bn C=32 P=3000", case_bn(3000, 32)),
     ("bn C=96 q1", case_bn(1500, 96, q1=True)),

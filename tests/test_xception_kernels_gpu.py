@@ -1,23 +1,18 @@
-"""-m gpu: the depthwise entry points at the Xception widths against fp64 torch.  Every case runs twice: through the
-routed entries (uda_dwconv_*: C > 1024 on the channel-blocked kernels, narrower widths on their own kernels) and
-straight on the channel-blocked family (uda_dwconv_cb_*), so both families are pinned at every width they may serve.
+"""-m gpu: the depthwise entry points at the Xception widths against fp64 torch.  Every case runs twice: with the kernel
+family the library's launch plan chooses (C > 1024 and dilation 4 at 1024 channels on the channel-blocked kernels, narrower
+widths on the tiled / flat ones) and pinned to the channel-blocked family, which may serve every width.  Each variant asserts
+through dw_route which kernel serves its three calls.
 Inputs are [P, C] views with ld > C whose padding columns hold NaN / Inf (kernel_cases.padded): nothing may leak."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+from dw_shapes import SHAPES, declared
 from kernel_cases import act_to, gen, hip, make_src, padded, to_dev
 from uda_clr_amd.acts import ACT_NONE, ACT_RELU
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-# (N, H, W, C, stride, dilation, BN + ReLU prologue)
-SHAPES = [(3, 9, 13, 4, 1, 1, True), (1, 7, 5, 64, 2, 1, True), (3, 6, 10, 64, 1, 4, False),
-          (1, 12, 9, 728, 1, 1, True), (3, 11, 8, 728, 2, 1, True), (1, 10, 14, 728, 1, 2, False),
-          (1, 9, 9, 1024, 1, 2, True), (3, 8, 11, 1024, 1, 4, True), (1, 5, 12, 1024, 2, 1, False),
-          (1, 13, 10, 1536, 1, 2, True), (3, 7, 9, 1536, 1, 4, True), (1, 8, 6, 1536, 2, 1, False),
-          (1, 9, 12, 2048, 1, 4, True), (3, 5, 7, 2048, 1, 1, False), (1, 6, 6, 2048, 2, 2, True)]
 
 
 def _rel(a, b):
@@ -58,6 +53,9 @@ def test_depthwise_matches_fp64(family, N, H, W, C, stride, dil, lazy):
     yr = _rows(y)
 
     K = hip()
+    for op, want in zip(("fwd", "dgrad", "wgrad"), declared(family, (N, H, W, C, stride, dil, lazy))):
+        route = K.dw_route(op, N, H, W, C, stride, dil, family)
+        assert " ".join(route.split()[:2]) == want, route
     w9 = K.relayout_dw(w.to(DEV))
     sh = act_to(src, DEV)
     yh = to_dev(padded(Po, C, g), DEV)

@@ -11,8 +11,6 @@
 // Thread mapping: cg = tid % G float4 channel groups, pl = tid / G pixel lanes (coalesced rows).
 #include "common.h"
 
-int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hipStream_t st);
-
 #define RED_ITER 32
 #define RED_CBLK 1024
 // channel block of the column REDUCTIONS: 128 channels per workgroup (8 pixel lanes x RED_ITER pixels): every

@@ -26,6 +26,23 @@ int uda_set_error(const char* fmt, ...);
 static inline bool uda_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int uda_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// ------------------------------------------------------------------------------------ weight gradients from partials (host)
+// out[col] += sum over rows of part[row][col], in double (igemm_conv.hip)
+int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hipStream_t st);
+
+// Workspace of a weight gradient of nel elements that up to nwg_max workgroups write one partial row each for:
+// [nel doubles: the sums][nwg_max x nel floats: the partials].  On the stream, in this order: uda_wgp_zero, the kernel that writes
+// nwg rows at uda_wgp_part, then uda_wgp_finish (or uda_wgp_reduce and a store kernel of the caller's own).
+static inline uint64_t uda_wgp_bytes(int64_t nwg_max, int64_t nel) { return (uint64_t)nwg_max * nel * sizeof(float) + (uint64_t)nel * sizeof(double); }
+static inline double* uda_wgp_sums(float* ws) { return reinterpret_cast<double*>(ws); }
+static inline float* uda_wgp_part(float* ws, int nel) { return ws + 2 * (size_t)nel; }
+static inline void uda_wgp_zero(float* ws, int nel, hipStream_t st) { (void)hipMemsetAsync(ws, 0, (size_t)nel * sizeof(double), st); }
+static inline int uda_wgp_reduce(float* ws, int nwg, int nel, hipStream_t st) {
+    return uda_reduce_partials(uda_wgp_part(ws, nel), nwg, nel, uda_wgp_sums(ws), st);
+}
+// uda_wgp_reduce, then dw[e] = (float)sums[e] for the nel elements; `who` names the store launch in an error (dwconv.hip)
+int uda_wgp_finish(float* ws, int nwg, int nel, float* dw, const char* who, hipStream_t st);
+
 // ------------------------------------------------------------------------------------ device
 #define ACT_NONE 0
 #define ACT_RELU 1

@@ -11,8 +11,6 @@
 // they arrive through the scalar cache as SGPR operands of v_fmac and cost no LDS or vector-memory traffic.
 #include "common.h"
 
-int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hipStream_t st);
-
 typedef const __attribute__((address_space(4))) float cfloat;      // uniform-index loads from here are scalar loads
 
 __device__ __forceinline__ cfloat* as_const(const float* p) { return (cfloat*)(uintptr_t)p; }
@@ -42,11 +40,6 @@ __device__ __forceinline__ void block_stats(const float* s1, const float* s2, fl
         const float t = red[tid] + red[2 * NC + tid] + red[4 * NC + tid] + red[6 * NC + tid];
         atomicAdd(&stats[(int64_t)(blockIdx.x % UDA_STAT_SLOTS) * 2 * NC + tid], (double)t);
     }
-}
-
-__global__ void dh_cast_d2f_kernel(const double* __restrict__ in, int n, float* __restrict__ out) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n) out[e] = (float)in[e];
 }
 
 // ------------------------------------------------------------------------------------------ 7x7 stride 1, 3 -> 16
@@ -211,7 +204,7 @@ __global__ __launch_bounds__(256) void stem7s1_wgrad_kernel(Stem7s1Args a) {
 
 extern "C" uint64_t uda_stem7s1_workspace_bytes(int64_t P) {
     (void)P;
-    return (uint64_t)H7W_MAX_WG * 2352 * sizeof(float) + 2352 * sizeof(double);
+    return uda_wgp_bytes(H7W_MAX_WG, 2352);
 }
 
 extern "C" int uda_stem7s1_fwd(const float* x, int N, int H, int W, const float* w_hwio, float* y, int64_t ldy, double* stats,
@@ -245,15 +238,11 @@ extern "C" int uda_stem7s1_wgrad(const float* x, int N, int H, int W, const floa
     UDA_REQUIRE(nt < ((int64_t)1 << 31), "uda_stem7s1_wgrad: too many tiles");
     a.ntiles = (int)nt;
     const int nwg = a.ntiles < H7W_MAX_WG ? a.ntiles : H7W_MAX_WG, nel = 2352;
-    double* sums = reinterpret_cast<double*>(workspace);
-    a.part = workspace + 2 * nel;
-    (void)hipMemsetAsync(sums, 0, nel * sizeof(double), st);
+    a.part = uda_wgp_part(workspace, nel);
+    uda_wgp_zero(workspace, nel, st);
     hipLaunchKernelGGL(stem7s1_wgrad_kernel, dim3(nwg), dim3(256), 0, st, a);
     UDA_LAUNCH_CHECK("stem7s1_wgrad");
-    if (int e = uda_reduce_partials(a.part, nwg, nel, sums, st)) return e;
-    hipLaunchKernelGGL(dh_cast_d2f_kernel, dim3(uda_cdiv(nel, 256)), dim3(256), 0, st, sums, nel, dw);
-    UDA_LAUNCH_CHECK("stem7s1_wgrad_store");
-    return 0;
+    return uda_wgp_finish(workspace, nwg, nel, dw, "stem7s1_wgrad_store", st);
 }
 
 // ------------------------------------------------------------------------------------------ narrow dense 3x3
@@ -496,8 +485,7 @@ extern "C" int uda_conv3n_fwd(const uda_src_t* src, const float* w_hwio, int Cou
 }
 
 extern "C" uint64_t uda_conv3n_workspace_bytes(int Cin, int Cout) {
-    const uint64_t nel = (uint64_t)Cin * Cout * 9;
-    return nel * sizeof(double) + (uint64_t)n3_max_wg(Cin, Cout) * nel * sizeof(float);
+    return uda_wgp_bytes(n3_max_wg(Cin, Cout), (int64_t)Cin * Cout * 9);
 }
 
 extern "C" int uda_conv3n_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int Cout, int stride, float* dw,
@@ -519,13 +507,9 @@ extern "C" int uda_conv3n_wgrad(const uda_src_t* src, const float* dy, int64_t l
     a.dy = dy; a.lddy = lddy;
     const int nel = Cin * Cout * 9, cap = n3_max_wg(Cin, Cout);
     const int nwg = a.ntiles < cap ? a.ntiles : cap;
-    double* sums = reinterpret_cast<double*>(workspace);
-    a.part = workspace + 2 * nel;
-    (void)hipMemsetAsync(sums, 0, nel * sizeof(double), st);
+    a.part = uda_wgp_part(workspace, nel);
+    uda_wgp_zero(workspace, nel, st);
     N3_DISPATCH(N3_LAUNCH_WGRAD, Cin, Cout, stride, dim3(nwg, Cin / 16), st, a);
     UDA_LAUNCH_CHECK("conv3n_wgrad");
-    if (int e = uda_reduce_partials(a.part, nwg, nel, sums, st)) return e;
-    hipLaunchKernelGGL(dh_cast_d2f_kernel, dim3(uda_cdiv(nel, 256)), dim3(256), 0, st, sums, nel, dw);
-    UDA_LAUNCH_CHECK("conv3n_wgrad_store");
-    return 0;
+    return uda_wgp_finish(workspace, nwg, nel, dw, "conv3n_wgrad_store", st);
 }

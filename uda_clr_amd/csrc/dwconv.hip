@@ -7,12 +7,8 @@
 // Thread mapping (shared by the depthwise kernels): channel group cg = tid % G (G = C/4 float4
 // groups), pixel lane pl = tid / G; a workgroup walks ITER strips of PP = 256/G consecutive
 // output pixels, so the 64 lanes of a wave read G*16 contiguous bytes per pixel.
-#include "common.h"
-
-int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hipStream_t st);
-
-#define DW_ITER_FWD 8
-#define DW_ITER_RED 32
+// Which kernel serves a call, and on which grid, is decided in dw_plan.h and nowhere else.
+#include "dw_plan.h"
 
 struct DwArgs {
     uda_src_t src;
@@ -100,7 +96,6 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(DwArgs a) {
 // quirk-Q1 border value) is applied ONCE per element on the way into LDS, and the 9 taps are read
 // back with ds_read_b128.  (The first version re-read and re-transformed every input 9 times from
 // L1/L2: 1.3-2.1 TB/s of algorithmic bytes; this one is bounded by the 1.3-1.6x halo over-read.)
-#define DWT_CB 32
 // Halo tile into LDS: every thread's loads are issued back to back with clamped coordinates (the value of an out-of-image position is
 // replaced afterwards) - with the bounds test AROUND the load a thread had one load in flight at a time and a workgroup spent six to
 // twelve load latencies on staging (the tiled kernels streamed at 2.4-3.7 TB/s).
@@ -272,45 +267,32 @@ __global__ void dw_wgrad_store_slots_kernel(const double* __restrict__ sums, int
     }
 }
 
+// The tiled launches: raise the kernel's dynamic-LDS limit where the plan's tile needs it, then launch on the plan's grid.
 template <int S, int TH, int TW>
-static int launch_dw_wgrad_tiled(DwArgs& a, double* sums, float* dw, hipStream_t st) {
-    const int d = a.dil;
-    const int IH = (TH - 1) * S + 2 * d + 1, IW = (TW - 1) * S + 2 * d + 1;
-    size_t lds = (size_t)IH * IW * DWT_CB * sizeof(float);
-    if (lds < 32 * 9 * DWT_CB * sizeof(float)) lds = 32 * 9 * DWT_CB * sizeof(float);
-    auto fn = dwconv_wgrad_tiled_kernel<S, TH, TW>;
+static int launch_dw_tiled(const DwArgs& a, const DwPlan& p, hipStream_t st) {
+    auto fn = dwconv_fwd_tiled_kernel<S, TH, TW>;
     static size_t reserved = 0;
-    if (lds > reserved && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return uda_set_error("dwconv_wgrad: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-        reserved = lds;
+    if (p.lds > reserved && p.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        if (e != hipSuccess) return uda_set_error("dwconv_fwd: cannot reserve %zu B of LDS: %s", p.lds, hipGetErrorString(e));
+        reserved = p.lds;
     }
-    const int C = a.src.C;
-    (void)hipMemsetAsync(sums, 0, (size_t)UDA_STAT_SLOTS * 9 * C * sizeof(double), st);
-    const int tilesX = uda_cdiv(a.Wo, TW), tilesY = uda_cdiv(a.Ho, TH);
-    hipLaunchKernelGGL(fn, dim3(tilesX * tilesY * a.src.N, uda_cdiv(C, DWT_CB)), dim3(256), lds, st, a, tilesX, tilesY, sums);
-    UDA_LAUNCH_CHECK("dwconv_wgrad_tiled");
-    hipLaunchKernelGGL(dw_wgrad_store_slots_kernel, dim3(uda_cdiv(9 * C, 256)), dim3(256), 0, st, sums, C, dw);
-    UDA_LAUNCH_CHECK("dw_wgrad_store");
+    hipLaunchKernelGGL(fn, dim3(p.gx, p.gy), dim3(256), p.lds, st, a, p.tilesX, p.tilesY);
+    UDA_LAUNCH_CHECK("dwconv_fwd_tiled");
     return 0;
 }
 
 template <int S, int TH, int TW>
-static int launch_dw_tiled(DwArgs& a, hipStream_t st) {
-    const int d = a.dil;
-    const int IH = (TH - 1) * S + 2 * d + 1, IW = (TW - 1) * S + 2 * d + 1;
-    size_t lds = (size_t)IH * IW * DWT_CB * sizeof(float);
-    if (lds < 32 * 2 * DWT_CB * sizeof(float)) lds = 32 * 2 * DWT_CB * sizeof(float);
-    auto fn = dwconv_fwd_tiled_kernel<S, TH, TW>;
+static int launch_dw_wgrad_tiled(const DwArgs& a, const DwPlan& p, double* sums, hipStream_t st) {
+    auto fn = dwconv_wgrad_tiled_kernel<S, TH, TW>;
     static size_t reserved = 0;
-    if (lds > reserved && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return uda_set_error("dwconv_fwd: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-        reserved = lds;
+    if (p.lds > reserved && p.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        if (e != hipSuccess) return uda_set_error("dwconv_wgrad: cannot reserve %zu B of LDS: %s", p.lds, hipGetErrorString(e));
+        reserved = p.lds;
     }
-    const int tilesX = uda_cdiv(a.Wo, TW), tilesY = uda_cdiv(a.Ho, TH);
-    hipLaunchKernelGGL(fn, dim3(tilesX * tilesY * a.src.N, uda_cdiv(a.src.C, DWT_CB)), dim3(256), lds, st, a, tilesX, tilesY);
-    UDA_LAUNCH_CHECK("dwconv_fwd_tiled");
+    hipLaunchKernelGGL(fn, dim3(p.gx, p.gy), dim3(256), p.lds, st, a, p.tilesX, p.tilesY, sums);
+    UDA_LAUNCH_CHECK("dwconv_wgrad_tiled");
     return 0;
 }
 
@@ -439,16 +421,6 @@ __global__ void dw_wgrad_store_kernel(const double* __restrict__ sums, int C, fl
 // and the 9x re-read of each input row is served by L1 / L2 (the strip walks the image row-major).  Statistics / weight
 // gradients: fp32 per thread and through one LDS reduction per workgroup, fp64 atomics across workgroups into
 // UDA_STAT_SLOTS replicas.
-#define DWB_ITER_FWD 8
-#define DWB_ITER_RED 32
-#define DWB_CMAX 2048
-
-static inline int dwb_lg_groups(int C) {          // log2(CG)
-    int lg = 0;
-    while ((1 << lg) < C / 4 && lg < 6) ++lg;
-    return lg;
-}
-
 __device__ __forceinline__ void dwb_pixel(int64_t po, int Wo, int Ho, int& n, int& oh, int& ow) {
     ow = (int)(po % Wo);
     const int64_t r = po / Wo;
@@ -635,169 +607,143 @@ __global__ __launch_bounds__(256) void dwconv_cb_dgrad_kernel(const float* __res
     }
 }
 
-static int dwb_fwd(DwArgs& a, hipStream_t st) {
-    const int lg = dwb_lg_groups(a.src.C);
-    const int64_t Pout = (int64_t)a.src.N * a.Ho * a.Wo;
-    const dim3 grid(uda_cdiv(Pout, (int64_t)(256 >> lg) * DWB_ITER_FWD), uda_cdiv(a.src.C / 4, 1 << lg));
-    hipLaunchKernelGGL(dwconv_cb_fwd_kernel, grid, dim3(256), 0, st, a, lg);
-    UDA_LAUNCH_CHECK("dwconv_cb_fwd");
-    return 0;
-}
+static_assert(DWF_AUTO == UDA_DW_AUTO && DWF_FLAT == UDA_DW_FLAT && DWF_TILED == UDA_DW_TILED && DWF_CB == UDA_DW_CB, "DwFamily is the ABI's UDA_DW_*");
+static_assert(DW_FWD == UDA_DW_FWD && DW_DGRAD == UDA_DW_DGRAD && DW_WGRAD == UDA_DW_WGRAD, "DwOp is the ABI's UDA_DW_FWD ...");
 
-static int dwb_wgrad(DwArgs& a, double* sums, float* dw, hipStream_t st) {
-    const int C = a.src.C, lg = dwb_lg_groups(C);
-    const int64_t Pout = (int64_t)a.src.N * a.Ho * a.Wo;
-    (void)hipMemsetAsync(sums, 0, (size_t)UDA_STAT_SLOTS * 9 * C * sizeof(double), st);
-    const dim3 grid(uda_cdiv(Pout, (int64_t)(256 >> lg) * DWB_ITER_RED), uda_cdiv(C / 4, 1 << lg));
-    hipLaunchKernelGGL(dwconv_cb_wgrad_kernel, grid, dim3(256), 0, st, a, lg, sums);
-    UDA_LAUNCH_CHECK("dwconv_cb_wgrad");
-    hipLaunchKernelGGL(dw_wgrad_store_slots_kernel, dim3(uda_cdiv(9 * C, 256)), dim3(256), 0, st, sums, C, dw);
-    UDA_LAUNCH_CHECK("dw_wgrad_store");
-    return 0;
-}
-
-static int dwb_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil, int N, int H, int W,
-                     float* dx, int64_t lddx, hipStream_t st) {
-    const int lg = dwb_lg_groups(C);
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    const int64_t P = (int64_t)N * H * W;
-    const dim3 grid(uda_cdiv(P, (int64_t)(256 >> lg) * DWB_ITER_FWD), uda_cdiv(C / 4, 1 << lg));
-    hipLaunchKernelGGL(dwconv_cb_dgrad_kernel, grid, dim3(256), 0, st, dy, lddy, w9c, C, stride, dil, N, H, W, Ho, Wo, dx, lddx, lg);
-    UDA_LAUNCH_CHECK("dwconv_cb_dgrad");
-    return 0;
-}
-
-// Shape rule of the C entries (measured on MI355X at Xception's 512^2, B = 16 shapes, profiles/xception_dw_kernels.md): the
-// channel-blocked kernels take the widths the other families reject (C > 1024) and the dilation-4 convs of 1024 channels
-// (fwd 343 -> 235 us, wgrad 346 -> 258 us against the flat kernel).  At 728 / 1024 channels with dilation <= 2 the LDS-tiled
-// kernels stay (fwd 25 / 31 us against 44 / 52 us).  Every MobileNetV2 launch (C <= 960) keeps its kernel; ResNet-101 has
-// no depthwise conv.
-static inline bool dw_use_cb(int C, int dil) { return C > 1024 || (dil > 2 && C >= 1024); }
-
-static int dw_check(const uda_src_t* s, const char* who, int cmax = 1024) {
+// what a plan cannot see: the pointers and row strides of the source
+static int dw_check(const uda_src_t* s, const char* who) {
     UDA_REQUIRE(s && s->x && uda_aligned16(s->x) && s->ldx % 4 == 0 && s->ldx >= s->C, "%s: bad src", who);
-    UDA_REQUIRE(s->C % 4 == 0 && s->C >= 4 && s->C <= cmax, "%s: C=%d must be a multiple of 4 in [4,%d]", who, s->C, cmax);
     UDA_REQUIRE((s->scale == nullptr) == (s->shift == nullptr), "%s: scale/shift must come together", who);
     UDA_REQUIRE(s->mask == nullptr, "%s: dropout masks are not supported on depthwise inputs", who);
     return 0;
 }
 
-static inline int dw_pixels_per_wg(int C, int iter) { return (256 / (C / 4)) * iter; }
+#define DW_REQUIRE_PLAN(p, who, C, stride, dil) UDA_REQUIRE(!(p).error, "%s: C=%d, stride %d, dilation %d: %s", who, C, stride, dil, (p).error)
+
+// the kernel argument block of the forward conv and the weight gradient (the caller adds its own operands)
+static DwArgs dw_args(const uda_src_t* src, const DwPlan& p, int stride, int dil, int border_mode) {
+    DwArgs a = {};
+    a.src = *src;
+    a.stride = stride; a.dil = dil; a.border_mode = border_mode;
+    a.Ho = p.Ho; a.Wo = p.Wo;
+    return a;
+}
+
+// the instantiation the plan names
+static int dw_fwd_tiled(const DwArgs& a, const DwPlan& p, hipStream_t st) {
+#define DW_LAUNCH(S_, TH_, TW_) if (p.S == S_ && p.TH == TH_ && p.TW == TW_) return launch_dw_tiled<S_, TH_, TW_>(a, p, st);
+    DW_TILED_VARIANTS(DW_LAUNCH)
+#undef DW_LAUNCH
+    return uda_set_error("dwconv_fwd: no tiled kernel <%d, %d, %d>", p.S, p.TH, p.TW);
+}
+
+static int dw_wgrad_tiled(const DwArgs& a, const DwPlan& p, double* sums, hipStream_t st) {
+#define DW_LAUNCH(S_, TH_, TW_) if (p.S == S_ && p.TH == TH_ && p.TW == TW_) return launch_dw_wgrad_tiled<S_, TH_, TW_>(a, p, sums, st);
+    DW_TILED_VARIANTS(DW_LAUNCH)
+#undef DW_LAUNCH
+    return uda_set_error("dwconv_wgrad: no tiled kernel <%d, %d, %d>", p.S, p.TH, p.TW);
+}
 
 extern "C" uint64_t uda_dwconv_workspace_bytes(int64_t Pout, int C) {
     if (C < 4) return 0;
-    const uint64_t tiled = (uint64_t)UDA_STAT_SLOTS * 9 * C * sizeof(double);     // (the channel-blocked kernels' too)
-    if (C > 1024) return tiled;
-    const uint64_t flat = (uint64_t)uda_cdiv(Pout, dw_pixels_per_wg(C, DW_ITER_RED)) * 9 * C * sizeof(float) + 9 * C * sizeof(double);
-    return flat > tiled ? flat : tiled;
-}
-
-static int dw_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
-                  float* y, int64_t ldy, double* stats, void* stream, bool cb) {
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = dw_check(src, "uda_dwconv_fwd", cb ? DWB_CMAX : 1024)) return e;
-    UDA_REQUIRE(w9c && uda_aligned16(w9c) && y && uda_aligned16(y) && ldy % 4 == 0 && ldy >= src->C, "uda_dwconv_fwd: bad pointers");
-    UDA_REQUIRE((stride == 1 || stride == 2) && dil >= 1, "uda_dwconv_fwd: stride must be 1 or 2");
-    UDA_REQUIRE(border_mode == 0 || (border_mode == 1 && src->shift), "uda_dwconv_fwd: border_mode 1 needs shift");
-    DwArgs a;
-    a.src = *src;
-    a.w9c = w9c;
-    a.stride = stride; a.dil = dil; a.border_mode = border_mode;
-    a.Ho = (src->H - 1) / stride + 1;
-    a.Wo = (src->W - 1) / stride + 1;
-    a.y = y; a.ldy = ldy; a.dy = nullptr; a.lddy = 0;
-    a.part = nullptr;
-    a.stats = stats;
-    if (cb) return dwb_fwd(a, st);
-    const int64_t Pout = (int64_t)src->N * a.Ho * a.Wo;
-    const int nwg = uda_cdiv(Pout, dw_pixels_per_wg(src->C, DW_ITER_FWD));     // (C <= 1024 here: at least one pixel per workgroup)
-    if (dil <= 2) return stride == 1 ? launch_dw_tiled<1, 8, 16>(a, st) : launch_dw_tiled<2, 8, 8>(a, st);
-    hipLaunchKernelGGL(dwconv_fwd_kernel, dim3(nwg), dim3(256), 0, st, a);
-    UDA_LAUNCH_CHECK("dwconv_fwd");
-    return 0;
+    uint64_t most = 0;
+    for (int f = DWF_FLAT; f <= DWF_CB; ++f)
+        if (C <= dw_cmax(DW_WGRAD, f)) {
+            const uint64_t b = dw_wgrad_ws_bytes(f, Pout, C);
+            if (b > most) most = b;
+        }
+    return most;
 }
 
 extern "C" int uda_dwconv_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
-                              float* y, int64_t ldy, double* stats, void* stream) {
-    return dw_fwd(src, w9c, stride, dil, border_mode, y, ldy, stats, stream, src && dw_use_cb(src->C, dil));
-}
-
-extern "C" int uda_dwconv_cb_fwd(const uda_src_t* src, const float* w9c, int stride, int dil, int border_mode,
-                                 float* y, int64_t ldy, double* stats, void* stream) {
-    return dw_fwd(src, w9c, stride, dil, border_mode, y, ldy, stats, stream, true);
-}
-
-static int dw_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
-                    int N, int H, int W, float* dx, int64_t lddx, void* stream, bool cb) {
-    UDA_REQUIRE(dy && w9c && dx && uda_aligned16(dy) && uda_aligned16(dx) && uda_aligned16(w9c), "uda_dwconv_dgrad: pointers must be 16-byte aligned");
-    UDA_REQUIRE(C % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && lddy >= C && lddx >= C, "uda_dwconv_dgrad: C and lds must be multiples of 4");
-    UDA_REQUIRE((stride == 1 || stride == 2) && dil >= 1 && N > 0 && H > 0 && W > 0, "uda_dwconv_dgrad: bad geometry");
-    if (cb) {
-        UDA_REQUIRE(C >= 4 && C <= DWB_CMAX, "uda_dwconv_dgrad: C=%d must be in [4,%d]", C, DWB_CMAX);
-        return dwb_dgrad(dy, lddy, w9c, C, stride, dil, N, H, W, dx, lddx, (hipStream_t)stream);
-    }
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    const int64_t total = (int64_t)N * H * W * (C / 4);
-    int grid = uda_cdiv(total, 256);
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(dwconv_dgrad_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, lddy, w9c, C, stride, dil,
-                       N, H, W, Ho, Wo, dx, lddx);
-    UDA_LAUNCH_CHECK("dwconv_dgrad");
+                              float* y, int64_t ldy, double* stats, int family, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = dw_check(src, "uda_dwconv_fwd")) return e;
+    const DwPlan p = dw_plan(DW_FWD, src->N, src->H, src->W, src->C, stride, dil, family);
+    DW_REQUIRE_PLAN(p, "uda_dwconv_fwd", src->C, stride, dil);
+    UDA_REQUIRE(w9c && uda_aligned16(w9c) && y && uda_aligned16(y) && ldy % 4 == 0 && ldy >= src->C, "uda_dwconv_fwd: bad pointers");
+    UDA_REQUIRE(border_mode == 0 || (border_mode == 1 && src->shift), "uda_dwconv_fwd: border_mode 1 needs shift");
+    DwArgs a = dw_args(src, p, stride, dil, border_mode);
+    a.w9c = w9c; a.y = y; a.ldy = ldy; a.stats = stats;
+    if (p.family == DWF_TILED) return dw_fwd_tiled(a, p, st);
+    if (p.family == DWF_CB) hipLaunchKernelGGL(dwconv_cb_fwd_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, a, p.lg);
+    else hipLaunchKernelGGL(dwconv_fwd_kernel, dim3(p.gx), dim3(256), 0, st, a);
+    UDA_LAUNCH_CHECK(p.family == DWF_CB ? "dwconv_cb_fwd" : "dwconv_fwd");
     return 0;
 }
 
 extern "C" int uda_dwconv_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
-                                int N, int H, int W, float* dx, int64_t lddx, void* stream) {
-    return dw_dgrad(dy, lddy, w9c, C, stride, dil, N, H, W, dx, lddx, stream, dw_use_cb(C, dil));
-}
-
-extern "C" int uda_dwconv_cb_dgrad(const float* dy, int64_t lddy, const float* w9c, int C, int stride, int dil,
-                                   int N, int H, int W, float* dx, int64_t lddx, void* stream) {
-    return dw_dgrad(dy, lddy, w9c, C, stride, dil, N, H, W, dx, lddx, stream, true);
-}
-
-static int dw_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
-                    int border_mode, float* dw, float* workspace, uint64_t workspace_bytes, void* stream, bool cb) {
+                                int N, int H, int W, float* dx, int64_t lddx, int family, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (int e = dw_check(src, "uda_dwconv_wgrad", cb ? DWB_CMAX : 1024)) return e;
-    UDA_REQUIRE(dy && uda_aligned16(dy) && lddy % 4 == 0 && lddy >= src->C && dw, "uda_dwconv_wgrad: bad pointers");
-    UDA_REQUIRE((stride == 1 || stride == 2) && dil >= 1, "uda_dwconv_wgrad: stride must be 1 or 2");
-    UDA_REQUIRE(border_mode == 0 || (border_mode == 1 && src->shift), "uda_dwconv_wgrad: border_mode 1 needs shift");
-    DwArgs a;
-    a.src = *src;
-    a.w9c = nullptr;
-    a.stride = stride; a.dil = dil; a.border_mode = border_mode;
-    a.Ho = (src->H - 1) / stride + 1;
-    a.Wo = (src->W - 1) / stride + 1;
-    a.y = nullptr; a.ldy = 0; a.dy = dy; a.lddy = lddy; a.stats = nullptr;
-    const int C = src->C;
-    const int64_t Pout = (int64_t)src->N * a.Ho * a.Wo;
-    UDA_REQUIRE(workspace && workspace_bytes >= uda_dwconv_workspace_bytes(Pout, C), "uda_dwconv_wgrad: workspace too small");
-    if (cb) return dwb_wgrad(a, reinterpret_cast<double*>(workspace), dw, st);
-    const int nwg = uda_cdiv(Pout, dw_pixels_per_wg(C, DW_ITER_RED));
-    if (dil <= 2) {
-        double* slot_sums = reinterpret_cast<double*>(workspace);
-        return stride == 1 ? launch_dw_wgrad_tiled<1, 8, 16>(a, slot_sums, dw, st) : launch_dw_wgrad_tiled<2, 8, 8>(a, slot_sums, dw, st);
-    }
-    double* sums = reinterpret_cast<double*>(workspace);          // [9][C] first (8-byte aligned)
-    a.part = workspace + 2 * 9 * C;
-    (void)hipMemsetAsync(sums, 0, 9 * C * sizeof(double), st);
-    hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3(nwg), dim3(256), 0, st, a);
-    UDA_LAUNCH_CHECK("dwconv_wgrad");
-    if (int e = uda_reduce_partials(a.part, nwg, 9 * C, sums, st)) return e;
-    hipLaunchKernelGGL(dw_wgrad_store_kernel, dim3(uda_cdiv(9 * C, 256)), dim3(256), 0, st, sums, C, dw);
-    UDA_LAUNCH_CHECK("dw_wgrad_store");
+    UDA_REQUIRE(dy && w9c && dx && uda_aligned16(dy) && uda_aligned16(dx) && uda_aligned16(w9c), "uda_dwconv_dgrad: pointers must be 16-byte aligned");
+    const DwPlan p = dw_plan(DW_DGRAD, N, H, W, C, stride, dil, family);
+    DW_REQUIRE_PLAN(p, "uda_dwconv_dgrad", C, stride, dil);
+    UDA_REQUIRE(lddy % 4 == 0 && lddx % 4 == 0 && lddy >= C && lddx >= C, "uda_dwconv_dgrad: lds must be multiples of 4, at least C");
+    if (p.family == DWF_CB)
+        hipLaunchKernelGGL(dwconv_cb_dgrad_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, dy, lddy, w9c, C, stride, dil, N, H, W, p.Ho, p.Wo, dx, lddx, p.lg);
+    else
+        hipLaunchKernelGGL(dwconv_dgrad_kernel, dim3(p.gx), dim3(256), 0, st, dy, lddy, w9c, C, stride, dil, N, H, W, p.Ho, p.Wo, dx, lddx);
+    UDA_LAUNCH_CHECK(p.family == DWF_CB ? "dwconv_cb_dgrad" : "dwconv_dgrad");
     return 0;
 }
 
 extern "C" int uda_dwconv_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
-                                int border_mode, float* dw, float* workspace, uint64_t workspace_bytes, void* stream) {
-    return dw_wgrad(src, dy, lddy, stride, dil, border_mode, dw, workspace, workspace_bytes, stream, src && dw_use_cb(src->C, dil));
+                                int border_mode, float* dw, float* workspace, uint64_t workspace_bytes, int family, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = dw_check(src, "uda_dwconv_wgrad")) return e;
+    const int C = src->C;
+    const DwPlan p = dw_plan(DW_WGRAD, src->N, src->H, src->W, C, stride, dil, family);
+    DW_REQUIRE_PLAN(p, "uda_dwconv_wgrad", C, stride, dil);
+    UDA_REQUIRE(dy && uda_aligned16(dy) && lddy % 4 == 0 && lddy >= C && dw, "uda_dwconv_wgrad: bad pointers");
+    UDA_REQUIRE(border_mode == 0 || (border_mode == 1 && src->shift), "uda_dwconv_wgrad: border_mode 1 needs shift");
+    UDA_REQUIRE(workspace && workspace_bytes >= uda_dwconv_workspace_bytes(p.Pout, C), "uda_dwconv_wgrad: workspace too small");
+    DwArgs a = dw_args(src, p, stride, dil, border_mode);
+    a.dy = dy; a.lddy = lddy;
+    const dim3 store_grid(uda_cdiv(9 * C, 256));
+    if (p.family == DWF_FLAT) {      // one partial row per workgroup, summed in double, then the [9][C] -> [C][9] store
+        a.part = uda_wgp_part(workspace, 9 * C);
+        uda_wgp_zero(workspace, 9 * C, st);
+        hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3(p.gx), dim3(256), 0, st, a);
+        UDA_LAUNCH_CHECK("dwconv_wgrad");
+        if (int e = uda_wgp_reduce(workspace, p.part_rows, 9 * C, st)) return e;
+        hipLaunchKernelGGL(dw_wgrad_store_kernel, store_grid, dim3(256), 0, st, uda_wgp_sums(workspace), C, dw);
+        UDA_LAUNCH_CHECK("dw_wgrad_store");
+        return 0;
+    }
+    // tiled / channel-blocked: fp64 atomics into slot replicas, summed by the store
+    double* sums = reinterpret_cast<double*>(workspace);
+    (void)hipMemsetAsync(sums, 0, (size_t)p.sum_slots * 9 * C * sizeof(double), st);
+    if (p.family == DWF_CB) {
+        hipLaunchKernelGGL(dwconv_cb_wgrad_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, a, p.lg, sums);
+        UDA_LAUNCH_CHECK("dwconv_cb_wgrad");
+    } else if (int e = dw_wgrad_tiled(a, p, sums, st)) return e;
+    hipLaunchKernelGGL(dw_wgrad_store_slots_kernel, store_grid, dim3(256), 0, st, sums, C, dw);
+    UDA_LAUNCH_CHECK("dw_wgrad_store");
+    return 0;
 }
 
-extern "C" int uda_dwconv_cb_wgrad(const uda_src_t* src, const float* dy, int64_t lddy, int stride, int dil,
-                                   int border_mode, float* dw, float* workspace, uint64_t workspace_bytes, void* stream) {
-    return dw_wgrad(src, dy, lddy, stride, dil, border_mode, dw, workspace, workspace_bytes, stream, true);
+// ---- routes: the plan as a short stable text, for tests and tools
+static const char* const DW_OP_NAME[3] = {"fwd", "dgrad", "wgrad"};
+
+/* "<op> <kernel>" + the grid, the pixel lanes of a workgroup and lg, e.g. "fwd tiled-8x16 grid 12x30 lds 19584", "dgrad flat grid 8192",
+ * "wgrad cb grid 3x6 lanes 4 lg 6"; "none" for refused arguments.  Returns the text's length (as snprintf), -1 without a buffer. */
+extern "C" int uda_dwconv_route(int op, int N, int H, int W, int C, int stride, int dil, int family, char* buf, int len) {
+    if (!buf || len < 1) return -1;
+    const DwPlan p = dw_plan(op, N, H, W, C, stride, dil, family);
+    if (p.error) return snprintf(buf, len, "none");
+    if (p.family == DWF_TILED) return snprintf(buf, len, "%s tiled-%dx%d grid %ux%u lds %zu", DW_OP_NAME[op], p.TH, p.TW, p.gx, p.gy, p.lds);
+    if (p.family == DWF_CB) return snprintf(buf, len, "%s cb grid %ux%u lanes %d lg %d", DW_OP_NAME[op], p.gx, p.gy, p.lanes, p.lg);
+    if (op == DW_DGRAD) return snprintf(buf, len, "%s flat grid %u", DW_OP_NAME[op], p.gx);
+    return snprintf(buf, len, "%s flat grid %u lanes %d", DW_OP_NAME[op], p.gx, p.lanes);
+}
+
+/* every "<op> <kernel>" uda_dwconv_route can begin with, one per line */
+extern "C" const char* uda_dwconv_route_list(void) {
+#define DW_FWD_ENTRY(S_, TH_, TW_) "fwd tiled-" #TH_ "x" #TW_ "\n"
+#define DW_WGRAD_ENTRY(S_, TH_, TW_) "wgrad tiled-" #TH_ "x" #TW_ "\n"
+    return DW_TILED_VARIANTS(DW_FWD_ENTRY) "fwd flat\nfwd cb\ndgrad flat\ndgrad cb\n" DW_TILED_VARIANTS(DW_WGRAD_ENTRY) "wgrad flat\nwgrad cb";
+#undef DW_FWD_ENTRY
+#undef DW_WGRAD_ENTRY
 }
 
 // ==========================================================================================
@@ -814,8 +760,6 @@ struct StemArgs {
     const float* dy;
     int64_t lddy;
 };
-
-#define STEM_PIX_PER_WG 256   // 32 pixels per pass x 8 passes
 
 __global__ __launch_bounds__(256) void stem_fwd_kernel(StemArgs a) {
     __shared__ float wsm[27 * 32];     // [tap][co]
@@ -1000,24 +944,32 @@ __global__ void cast_d2f_kernel(const double* __restrict__ in, int n, float* __r
     if (e < n) out[e] = (float)in[e];
 }
 
-extern "C" uint64_t uda_stem_workspace_bytes(int64_t Pout) {
-    return (uint64_t)uda_cdiv(Pout, STEM_PIX_PER_WG) * 864 * sizeof(float) + 864 * sizeof(double);
+// the finish of every partial-sum weight gradient of the library (declared in common.h)
+int uda_wgp_finish(float* ws, int nwg, int nel, float* dw, const char* who, hipStream_t st) {
+    if (int e = uda_wgp_reduce(ws, nwg, nel, st)) return e;
+    hipLaunchKernelGGL(cast_d2f_kernel, dim3(uda_cdiv(nel, 256)), dim3(256), 0, st, uda_wgp_sums(ws), nel, dw);
+    UDA_LAUNCH_CHECK(who);
+    return 0;
+}
+
+extern "C" uint64_t uda_stem_workspace_bytes(int64_t Pout) { return uda_wgp_bytes(uda_cdiv(Pout, STEM_PIX_PER_WG), 864); }
+
+static StemArgs stem_args(const float* x, int N, int H, int W, const StemPlan& p) {
+    StemArgs a = {};
+    a.x = x; a.N = N; a.H = H; a.W = W;
+    a.Ho = p.Ho; a.Wo = p.Wo;
+    return a;
 }
 
 extern "C" int uda_stem_fwd(const float* x, int N, int H, int W, const float* w, float* y, int64_t ldy,
                             double* stats, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    UDA_REQUIRE(x && w && y && uda_aligned16(y) && ldy % 4 == 0 && ldy >= 32 && N > 0 && H > 1 && W > 1, "uda_stem_fwd: bad args");
-    StemArgs a;
-    a.x = x; a.N = N; a.H = H; a.W = W;
-    a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
-    a.w = w; a.y = y; a.ldy = ldy; a.dy = nullptr; a.lddy = 0;
-    const int64_t Pout = (int64_t)N * a.Ho * a.Wo;
-    const int nwg = uda_cdiv(Pout, STEM_PIX_PER_WG);
-    a.part = nullptr;
-    a.stats = stats;
-    if (a.Wo % 256 == 0) hipLaunchKernelGGL(stem_fwd_rows_kernel, dim3(nwg), dim3(256), 0, st, a);       // nwg = N * Ho * (Wo / 256)
-    else hipLaunchKernelGGL(stem_fwd_kernel, dim3(nwg), dim3(256), 0, st, a);
+    const StemPlan p = stem_plan(DW_FWD, N, H, W, 0, 0);
+    UDA_REQUIRE(!p.error && x && w && y && uda_aligned16(y) && ldy % 4 == 0 && ldy >= 32, "uda_stem_fwd: bad args");
+    StemArgs a = stem_args(x, N, H, W, p);
+    a.w = w; a.y = y; a.ldy = ldy; a.stats = stats;
+    if (p.kernel == STEM_ROWS) hipLaunchKernelGGL(stem_fwd_rows_kernel, dim3(p.grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(stem_fwd_kernel, dim3(p.grid), dim3(256), 0, st, a);
     UDA_LAUNCH_CHECK("stem_fwd");
     return 0;
 }
@@ -1025,22 +977,23 @@ extern "C" int uda_stem_fwd(const float* x, int N, int H, int W, const float* w,
 extern "C" int uda_stem_wgrad(const float* x, int N, int H, int W, const float* dy, int64_t lddy, float* dw,
                               float* workspace, uint64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    UDA_REQUIRE(x && dy && dw && lddy >= 32 && N > 0 && H > 1 && W > 1, "uda_stem_wgrad: bad args");
-    StemArgs a;
-    a.x = x; a.N = N; a.H = H; a.W = W;
-    a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
-    a.w = nullptr; a.y = nullptr; a.ldy = 0; a.dy = dy; a.lddy = lddy; a.stats = nullptr;
-    const int64_t Pout = (int64_t)N * a.Ho * a.Wo;
-    const int nwg = uda_cdiv(Pout, STEM_PIX_PER_WG);
-    UDA_REQUIRE(workspace && workspace_bytes >= uda_stem_workspace_bytes(Pout), "uda_stem_wgrad: workspace too small");
-    double* sums = reinterpret_cast<double*>(workspace);
-    a.part = workspace + 2 * 864;
-    (void)hipMemsetAsync(sums, 0, 864 * sizeof(double), st);
-    if (a.Wo % 256 == 0 && uda_aligned16(dy) && lddy % 4 == 0) hipLaunchKernelGGL(stem_wgrad_rows_kernel, dim3(nwg), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(stem_wgrad_kernel, dim3(nwg), dim3(256), 0, st, a);
+    const StemPlan p = stem_plan(DW_WGRAD, N, H, W, lddy, uda_aligned16(dy));
+    UDA_REQUIRE(!p.error && x && dy && dw, "uda_stem_wgrad: bad args");
+    UDA_REQUIRE(workspace && workspace_bytes >= uda_stem_workspace_bytes(p.Pout), "uda_stem_wgrad: workspace too small");
+    StemArgs a = stem_args(x, N, H, W, p);
+    a.dy = dy; a.lddy = lddy;
+    a.part = uda_wgp_part(workspace, 864);
+    uda_wgp_zero(workspace, 864, st);
+    if (p.kernel == STEM_ROWS) hipLaunchKernelGGL(stem_wgrad_rows_kernel, dim3(p.grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(stem_wgrad_kernel, dim3(p.grid), dim3(256), 0, st, a);
     UDA_LAUNCH_CHECK("stem_wgrad");
-    if (int e = uda_reduce_partials(a.part, nwg, 864, sums, st)) return e;
-    hipLaunchKernelGGL(cast_d2f_kernel, dim3(uda_cdiv(864, 256)), dim3(256), 0, st, sums, 864, dw);
-    UDA_LAUNCH_CHECK("stem_wgrad_store");
-    return 0;
+    return uda_wgp_finish(workspace, p.grid, 864, dw, "stem_wgrad_store", st);
+}
+
+/* "fwd rows", "fwd pixels", "wgrad rows" or "wgrad pixels" (+ the grid); "none" for refused arguments.  As uda_dwconv_route. */
+extern "C" int uda_stem_route(int op, int N, int H, int W, int64_t lddy, int dy_aligned16, char* buf, int len) {
+    if (!buf || len < 1) return -1;
+    const StemPlan p = stem_plan(op, N, H, W, lddy, dy_aligned16);
+    if (p.error) return snprintf(buf, len, "none");
+    return snprintf(buf, len, "%s %s grid %d", DW_OP_NAME[op], p.kernel == STEM_ROWS ? "rows" : "pixels", p.grid);
 }

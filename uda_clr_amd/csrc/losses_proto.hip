@@ -294,8 +294,6 @@ __global__ __launch_bounds__(256) void proto_reduce_kernel(const float* __restri
     }
 }
 
-int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hipStream_t st);
-
 static inline int proto_nwg(int64_t P, int C) { return uda_cdiv(P, (int64_t)(256 / ((C + 3) / 4)) * PR_ITER); }
 
 extern "C" uint64_t uda_proto_workspace_bytes(int64_t P, int C) { return (uint64_t)proto_nwg(P, C) * 4 * (C + 1) * sizeof(float); }

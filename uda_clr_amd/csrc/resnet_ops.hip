@@ -6,8 +6,6 @@
 // All HBM / VALU bound and < 3 % of the ResNet step; the bottleneck convs run on igemm_*.hip.
 #include "common.h"
 
-int uda_reduce_partials(const float* part, int nrows, int ncols, double* out, hipStream_t st);
-
 // ------------------------------------------------------------------------------------------
 struct Stem7Args {
     const float* x;   // [N][3][H][W]
@@ -141,13 +139,8 @@ __global__ __launch_bounds__(256) void stem7_wgrad_kernel(Stem7Args a) {
     }
 }
 
-__global__ void s7_cast_d2f_kernel(const double* __restrict__ in, int n, float* __restrict__ out) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n) out[e] = (float)in[e];
-}
-
 extern "C" uint64_t uda_stem7_workspace_bytes(int64_t Pout) {
-    return (uint64_t)uda_cdiv(Pout, S7W_PIX_PER_WG) * 64 * S7_TAPS * sizeof(float) + 64 * S7_TAPS * sizeof(double);
+    return uda_wgp_bytes(uda_cdiv(Pout, S7W_PIX_PER_WG), 64 * S7_TAPS);
 }
 
 extern "C" int uda_stem7_fwd(const float* x, int N, int H, int W, const float* w, float* y, int64_t ldy, double* stats,
@@ -175,15 +168,11 @@ extern "C" int uda_stem7_wgrad(const float* x, int N, int H, int W, const float*
     const int64_t Pout = (int64_t)N * a.Ho * a.Wo;
     const int nwg = uda_cdiv(Pout, S7W_PIX_PER_WG), nel = 64 * S7_TAPS;
     UDA_REQUIRE(workspace && workspace_bytes >= uda_stem7_workspace_bytes(Pout), "uda_stem7_wgrad: workspace too small");
-    double* sums = reinterpret_cast<double*>(workspace);
-    a.part = workspace + 2 * nel;
-    (void)hipMemsetAsync(sums, 0, nel * sizeof(double), st);
+    a.part = uda_wgp_part(workspace, nel);
+    uda_wgp_zero(workspace, nel, st);
     hipLaunchKernelGGL(stem7_wgrad_kernel, dim3(nwg), dim3(256), 0, st, a);
     UDA_LAUNCH_CHECK("stem7_wgrad");
-    if (int e = uda_reduce_partials(a.part, nwg, nel, sums, st)) return e;
-    hipLaunchKernelGGL(s7_cast_d2f_kernel, dim3(uda_cdiv(nel, 256)), dim3(256), 0, st, sums, nel, dw);
-    UDA_LAUNCH_CHECK("stem7_wgrad_store");
-    return 0;
+    return uda_wgp_finish(workspace, nwg, nel, dw, "stem7_wgrad_store", st);
 }
 
 // ------------------------------------------------------------------------------------------

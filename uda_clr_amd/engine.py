@@ -561,6 +561,22 @@ class GeneratorEngine:
         self.K.conv(Act(dy, N, H, W), self._w(ctx, key, "dgrad"), ksize, dil, out, addend=addend)
         return out
 
+    def _dw_backward(self, ctx, G, key, src: Act, dy, stride, dil, border):
+        """Backward of the depthwise 3x3 conv ``key`` on ``src``: its weight gradient into G[key]; returns the gradient w.r.t.
+        the transformed ``src`` (a fresh [P, C] matrix)."""
+        K = self.K
+        dw = torch.empty_like(ctx.params[key])
+        K.dwconv_wgrad(src, dy, stride, dil, border, dw)
+        G[key] = dw
+        dx = self._buf(ctx.x, src.P, src.C)
+        if stride == 1:
+            # the input gradient of a stride-1 depthwise conv IS a depthwise conv of dy with the taps reversed: it runs on the
+            # forward kernels (the gather kernels stay for the stride-2 convs)
+            K.dwconv_fwd(Act(dy, src.N, src.H, src.W), self._w(ctx, key, "dwflip"), 1, dil, 0, dx, None)
+        else:
+            K.dwconv_dgrad(dy, self._w(ctx, key, "dw"), stride, dil, src.N, src.H, src.W, dx)
+        return dx
+
     def _bias_grad(self, G, key, dy):
         g = torch.empty(dy.shape[1], dtype=torch.float32, device=dy.device)
         self.K.colsum(dy, g)

@@ -62,15 +62,15 @@ SYMBOLS = {
     "uda_conv_wgrad": (_I, [C.POINTER(UdaWgradArgs), _P]),
     "uda_conv_wgrad_uses_x3": (_I, [C.POINTER(UdaWgradArgs)]),
     "uda_dwconv_workspace_bytes": (_U, [_L, _I]),
-    "uda_dwconv_fwd": (_I, [C.POINTER(UdaSrc), _P, _I, _I, _I, _P, _L, _P, _P]),
-    "uda_dwconv_dgrad": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
-    "uda_dwconv_wgrad": (_I, [C.POINTER(UdaSrc), _P, _L, _I, _I, _I, _P, _P, _U, _P]),
-    "uda_dwconv_cb_fwd": (_I, [C.POINTER(UdaSrc), _P, _I, _I, _I, _P, _L, _P, _P]),
-    "uda_dwconv_cb_dgrad": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
-    "uda_dwconv_cb_wgrad": (_I, [C.POINTER(UdaSrc), _P, _L, _I, _I, _I, _P, _P, _U, _P]),
+    "uda_dwconv_fwd": (_I, [C.POINTER(UdaSrc), _P, _I, _I, _I, _P, _L, _P, _I, _P]),
+    "uda_dwconv_dgrad": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _I, _P]),
+    "uda_dwconv_wgrad": (_I, [C.POINTER(UdaSrc), _P, _L, _I, _I, _I, _P, _P, _U, _I, _P]),
+    "uda_dwconv_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
+    "uda_dwconv_route_list": (C.c_char_p, []),
     "uda_stem_workspace_bytes": (_U, [_L]),
     "uda_stem_fwd": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
     "uda_stem_wgrad": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _U, _P]),
+    "uda_stem_route": (_I, [_I, _I, _I, _I, _L, _I, C.c_char_p, _I]),
     "uda_stem7_workspace_bytes": (_U, [_L]),
     "uda_stem7_fwd": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
     "uda_stem7_wgrad": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _U, _P]),
@@ -162,6 +162,8 @@ def load_library(path: Optional[str] = None):
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)          # AttributeError -> symbol missing
         fn.restype, fn.argtypes = res, args
+    if lib.uda_version() < 2:            # version 1 has no `family` argument in uda_dwconv_*: it would read the stream there
+        raise RuntimeError("%s is ABI version %d, these bindings need 2 - rebuild it" % (path, lib.uda_version()))
     _lib = lib
     return lib
 
@@ -170,11 +172,16 @@ class UdaError(RuntimeError):
     pass
 
 
-def _family(family: str) -> str:
-    """Depthwise kernel family of a binding call: "" (the library routes by shape) or "cb" (channel-blocked, uda_dwconv_cb_*)."""
-    if family not in ("", "cb"):
+_DW_FAMILY = {"": 0, "flat": 1, "tiled": 2, "cb": 3}      # UDA_DW_AUTO, _FLAT, _TILED, _CB
+_DW_OP = {"fwd": 0, "dgrad": 1, "wgrad": 2}                # UDA_DW_FWD, _DGRAD, _WGRAD
+
+
+def _family(family: str) -> int:
+    """Depthwise kernel family of a binding call: "" (the library's launch plan chooses by shape) or "flat" / "tiled" / "cb"
+    (that family, or an error where it cannot serve the shape)."""
+    if family not in _DW_FAMILY:
         raise ValueError("depthwise kernel family %r" % (family,))
-    return family + "_" if family else ""
+    return _DW_FAMILY[family]
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -235,6 +242,12 @@ class HipKernels:
             s.mask, s.ldm = None, 0
         s.mask_scale = a.mask_scale
         return s
+
+    @staticmethod
+    def _ck_stats(stats, Cc):
+        """a statistics accumulator of Cc channels: double [STAT_SLOTS][2][Cc], or None"""
+        if stats is not None:
+            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, Cc)
 
     @staticmethod
     def _ws(like, nbytes):
@@ -333,8 +346,7 @@ class HipKernels:
             assert bias.is_contiguous() and bias.numel() == Cout
         if addend is not None:
             assert addend.shape == out.shape
-        if stats is not None:
-            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, Cout)
+        self._ck_stats(stats, Cout)
         return self.conv_args(self._src(src), Cout, ksize, dil, origin, stride, w.data_ptr(), _ptr(bias),
                               *((None, 0) if addend is None else _mat(addend, "addend")), *_mat(out, "out"), _ptr(stats))
 
@@ -442,16 +454,15 @@ class HipKernels:
 
     # ------------------------------------------------------------------ depthwise
     def dwconv_fwd(self, src: Act, w9c, stride, dil, border_mode, out, stats=None, family=""):
-        """``family``: "" routes by shape inside the library (uda_dwconv_*), "cb" calls the channel-blocked kernels directly
-        (uda_dwconv_cb_*: kernel tests and measurements; the engine always routes)."""
+        """``family``: "" lets the library's launch plan choose by shape (the engine always does), "flat" / "tiled" / "cb" pin a
+        kernel family (kernel tests and measurements); ``dw_route`` tells which kernel a call takes."""
         s = self._src(src)
         Ho, Wo = (src.H - 1) // stride + 1, (src.W - 1) // stride + 1
         assert out.shape == (src.N * Ho * Wo, src.C) and w9c.is_contiguous() and tuple(w9c.shape) == (9, src.C)
         y, ldy = _mat(out, "out")
-        if stats is not None:
-            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, src.C)
-        self._ck(getattr(self.lib, "uda_dwconv_%sfwd" % _family(family))(C.byref(s), w9c.data_ptr(), stride, dil, border_mode, y, ldy,
-                                                                        _ptr(stats), self._stream()))
+        self._ck_stats(stats, src.C)
+        self._ck(self.lib.uda_dwconv_fwd(C.byref(s), w9c.data_ptr(), stride, dil, border_mode, y, ldy, _ptr(stats), _family(family),
+                                         self._stream()))
 
     def dwconv_dgrad(self, dy, w9c, stride, dil, N, H, W, out, family=""):
         Cc = dy.shape[1]
@@ -459,8 +470,7 @@ class HipKernels:
         assert dy.shape[0] == N * Ho * Wo and out.shape == (N * H * W, Cc)
         g, ldg = _mat(dy, "dy")
         o, ldo = _mat(out, "out")
-        self._ck(getattr(self.lib, "uda_dwconv_%sdgrad" % _family(family))(g, ldg, w9c.data_ptr(), Cc, stride, dil, N, H, W, o, ldo,
-                                                                          self._stream()))
+        self._ck(self.lib.uda_dwconv_dgrad(g, ldg, w9c.data_ptr(), Cc, stride, dil, N, H, W, o, ldo, _family(family), self._stream()))
 
     def dwconv_wgrad(self, src: Act, dy, stride, dil, border_mode, dw, family=""):
         s = self._src(src)
@@ -468,8 +478,15 @@ class HipKernels:
         assert dy.shape == (src.N * Ho * Wo, src.C) and dw.is_contiguous() and dw.numel() == 9 * src.C
         g, ldg = _mat(dy, "dy")
         ws = self._ws(dy, self.lib.uda_dwconv_workspace_bytes(dy.shape[0], src.C))
-        self._ck(getattr(self.lib, "uda_dwconv_%swgrad" % _family(family))(C.byref(s), g, ldg, stride, dil, border_mode, dw.data_ptr(),
-                                                                          ws.data_ptr(), ws.numel(), self._stream()))
+        self._ck(self.lib.uda_dwconv_wgrad(C.byref(s), g, ldg, stride, dil, border_mode, dw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _family(family), self._stream()))
+
+    def dw_route(self, op, N, H, W, Cc, stride, dil, family="") -> str:
+        """The launch the library plans for ``dwconv_fwd`` / ``dwconv_dgrad`` / ``dwconv_wgrad`` (op "fwd" / "dgrad" / "wgrad") on
+        an N x H x W x Cc input grid: "<op> <kernel> ...", "none" for a shape the entry refuses (uda_dwconv_route)."""
+        buf = C.create_string_buffer(96)
+        self.lib.uda_dwconv_route(_DW_OP[op], N, H, W, Cc, stride, dil, _family(family), buf, len(buf))
+        return buf.value.decode()
 
     # ------------------------------------------------------------------ stem
     def stem_fwd(self, x, w, out, stats=None):
@@ -479,8 +496,7 @@ class HipKernels:
         Po = N * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1)
         assert out.shape == (Po, 32)
         y, ldy = _mat(out, "out")
-        if stats is not None:
-            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, 32)
+        self._ck_stats(stats, 32)
         self._ck(self.lib.uda_stem_fwd(x.data_ptr(), N, H, W, w.data_ptr(), y, ldy, _ptr(stats), self._stream()))
 
     def stem_wgrad(self, x, dy, dw):
@@ -492,6 +508,15 @@ class HipKernels:
         self._ck(self.lib.uda_stem_wgrad(x.data_ptr(), N, H, W, g, ldg, dw.data_ptr(), ws.data_ptr(), ws.numel(),
                                          self._stream()))
 
+    def stem_route(self, op, x, dy=None) -> str:
+        """The kernel ``stem_fwd`` (op "fwd") / ``stem_wgrad`` (op "wgrad", with its ``dy``) runs on the image batch ``x``:
+        "fwd rows", "fwd pixels", "wgrad rows" or "wgrad pixels", then the grid (uda_stem_route)."""
+        N, _, H, W = x.shape
+        g, ldg = (0, 0) if dy is None else _mat(dy, "dy")
+        buf = C.create_string_buffer(96)
+        self.lib.uda_stem_route(_DW_OP[op], N, H, W, ldg, int(g % 16 == 0), buf, len(buf))
+        return buf.value.decode()
+
     # ------------------------------------------------------------------ ResNet-101 pieces
     def stem7_fwd(self, x, w, out, stats=None):
         self._dev(x)
@@ -500,8 +525,7 @@ class HipKernels:
         Po = N * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1)
         assert out.shape == (Po, 64)
         y, ldy = _mat(out, "out")
-        if stats is not None:
-            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, 64)
+        self._ck_stats(stats, 64)
         self._ck(self.lib.uda_stem7_fwd(x.data_ptr(), N, H, W, w.data_ptr(), y, ldy, _ptr(stats), self._stream()))
 
     def stem7_wgrad(self, x, dy, dw):
@@ -529,8 +553,7 @@ class HipKernels:
         assert c3 == 3 and x.is_contiguous() and w_hwio.is_contiguous() and tuple(w_hwio.shape) == (7, 7, 3, 16)
         assert out.shape == (N * H * W, 16)
         y, ldy = _mat(out, "out")
-        if stats is not None:
-            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, 16)
+        self._ck_stats(stats, 16)
         self._ck(self.lib.uda_stem7s1_fwd(x.data_ptr(), N, H, W, w_hwio.data_ptr(), y, ldy, _ptr(stats), self._stream()))
 
     def stem7s1_wgrad(self, x, dy, dw):
@@ -548,8 +571,7 @@ class HipKernels:
         Ho, Wo = (src.H - 1) // stride + 1, (src.W - 1) // stride + 1
         assert out.shape[0] == src.N * Ho * Wo and w_hwio.is_contiguous() and tuple(w_hwio.shape) == (3, 3, src.C, Cout)
         y, ldy = _mat(out, "out")
-        if stats is not None:
-            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, Cout)
+        self._ck_stats(stats, Cout)
         self._ck(self.lib.uda_conv3n_fwd(C.byref(s), w_hwio.data_ptr(), Cout, stride, y, ldy, _ptr(stats), self._stream()))
 
     def conv3n_wgrad(self, src: Act, dy, stride, dw):
@@ -890,8 +912,7 @@ class HipKernels:
         if addend is not None:
             assert addend.shape[1] == Cc and (N * H * W) % addend.shape[0] == 0
         fused = stats is not None and bool(self.lib.uda_upconv_fused_stats(h, w, H, W, Cc, dil))
-        if stats is not None:
-            assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (STAT_SLOTS, 2, Cc)
+        self._ck_stats(stats, Cc)
         self._ck(self.lib.uda_upconv_fwd(gp, ldg, N, h, w, Cc, dil, ad, lda, rows, o, ldo, H, W, _ptr(stats) if fused else None,
                                          self._stream()))
         if stats is not None and not fused:

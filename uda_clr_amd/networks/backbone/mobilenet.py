@@ -147,16 +147,7 @@ class MobileNetV2Exec:
             dUd = E._buf(x, d.P, d.C)
             E._dgrad(ctx, pre + kp + ".weight", dyp, No, Ho, Wo, 1, 1, dUd)
             dyd = E._bn_backward(ctx, G, d, dUd)
-            dwg = torch.empty_like(ctx.params[pre + kd + ".weight"])
-            K.dwconv_wgrad(e, dyd, stride, dil, r["border"], dwg)
-            G[pre + kd + ".weight"] = dwg
-            dUe = E._buf(x, zin.P, d.C)
-            if stride == 1:
-                # the input gradient of a stride-1 depthwise conv IS a depthwise conv of dy with the taps reversed:
-                # runs on the LDS-tiled forward kernel (the flat gather kernel stays for the four stride-2 blocks)
-                K.dwconv_fwd(Act(dyd, N, Hi, Wi), E._w(ctx, pre + kd + ".weight", "dwflip"), 1, dil, 0, dUe, None)
-            else:
-                K.dwconv_dgrad(dyd, E._w(ctx, pre + kd + ".weight", "dw"), stride, dil, N, Hi, Wi, dUe)
+            dUe = E._dw_backward(ctx, G, pre + kd + ".weight", e, dyd, stride, dil, r["border"])
             del dUd, dyd, dyp
             if t != 1:
                 q1_total = None

@@ -189,7 +189,7 @@ class XceptionExec:
         """Reverse of ``_sep_forward``: dP is the gradient w.r.t. the activated outer-BN output.  Returns the gradient
         w.r.t. the rectified input ``v`` (a fresh [P, Cin] matrix)."""
         E = self.E
-        K, x, N = E.K, ctx.x, ctx.N
+        x, N = ctx.x, ctx.N
         pre, v, d, p, stride, dil = r["pre"], r["v"], r["d"], r["p"], r["stride"], r["dil"]
         dyp = E._buf(x, p.P, p.C)
         E._bn_backward(ctx, G, p, dP, out=dyp)
@@ -198,16 +198,7 @@ class XceptionExec:
         E._dgrad(ctx, pre + ".pointwise.weight", dyp, N, d.H, d.W, 1, 1, dUd)
         del dyp
         dyd = E._bn_backward(ctx, G, d, dUd)
-        key = pre + ".conv1.weight"
-        dwg = torch.empty_like(ctx.params[key])
-        K.dwconv_wgrad(v, dyd, stride, dil, 0, dwg)
-        G[key] = dwg
-        dV = E._buf(x, v.P, v.C)
-        if stride == 1:          # a stride-1 depthwise conv's input gradient is the depthwise conv of dy with the taps reversed
-            K.dwconv_fwd(Act(dyd, N, v.H, v.W), E._w(ctx, key, "dwflip"), 1, dil, 0, dV, None)
-        else:
-            K.dwconv_dgrad(dyd, E._w(ctx, key, "dw"), stride, dil, N, v.H, v.W, dV)
-        return dV
+        return E._dw_backward(ctx, G, pre + ".conv1.weight", v, dyd, stride, dil, 0)
 
     def backward(self, ctx, G, d_a, d_low):
         """d_a: gradient w.r.t. the activated [P16, 2048] backbone output, d_low: w.r.t. relu(block1 output)."""
