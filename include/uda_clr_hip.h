@@ -432,6 +432,24 @@ size_t uda_surface_distance_workspace_bytes(int B, int H, int W);
 int uda_surface_distance(const uint8_t* pred, const uint8_t* gt, int B, int H, int W, double* table, int64_t* counts,
                          int32_t* d2, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same four passes (table, counts and d2 bit-identical to uda_surface_distance on the same masks) and a fifth over
+ * the border sets and distance maps they leave: what hd95 (any percentile of the distances), the surface Dice at a tolerance
+ * and the vertical cup-to-disc ratio are closed forms of.  Integers only, bit-identical from run to run, an image's rows the
+ * same alone and inside any batch.
+ *   quantiles HOST double[Q], 0 <= q <= 1, 0 <= Q <= 8;  tol2 HOST int32[T], squared tolerances >= 0, 0 <= T <= 8.
+ *   order  int64 [B][2 class][3 set: 0 = pred -> gt, 1 = gt -> pred, 2 = both pooled][Q][2]: for a set of n squared distances,
+ *          v = (double)(n - 1) * q (one IEEE multiply), lo = floor(v), hi = min(lo + 1, n - 1): the lo-th and the hi-th smallest
+ *          squared distance (0-based).  (-1, -1) where either border set of the (image, class) is empty.
+ *   within int64 [B][2][2 dir][T]: border pixels of that direction with d2 <= tol2[t]; -1 where either border set is empty.
+ *   extent int64 [B][2][2 slot: 0 = ground truth, 1 = prediction][2]: smallest and largest row that holds a set pixel of that
+ *          mask; (-1, -1) for an empty mask, whatever the other mask holds.
+ * Limits and workspace as uda_surface_distance; Q or T out of range, a quantile outside [0, 1] or NaN, a negative tol2: the
+ * error is returned before any launch and nothing is written.  order may be null at Q = 0, within at T = 0. */
+size_t uda_surface_profile_workspace_bytes(int B, int H, int W);
+int uda_surface_profile(const uint8_t* pred, const uint8_t* gt, int B, int H, int W, const double* quantiles, int Q,
+                        const int32_t* tol2, int T, double* table, int64_t* counts, int64_t* order, int64_t* within,
+                        int64_t* extent, int32_t* d2, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- device-side tail of the input pipeline. The reference's dataloader workers run these per sample
  * on the CPU with scipy.ndimage; here they run per uint8 BATCH on the GPU, bit-identical to the scipy calls.
  * uda_normalize_tf: dataloaders/custom_transforms.py:432-466 (Normalize_tf), :414-429 (GetBoundary), :504-507 (ToTensor).

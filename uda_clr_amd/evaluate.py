@@ -3,7 +3,19 @@
 
 The forward, ``postprocessing_batch`` and ``ops.surface_distances`` run per batch on the device; the metrics are closed forms
 (utils/metrics.py) of the small table that one copy per batch brings to the host.  No per-image device call is made.
+
+On request (``hd95``, ``tolerances``, ``cdr``) the batch goes through ``ops.surface_profile`` instead - the same table and counts plus
+the order statistics, tolerance counts and row extents that the 95th-percentile Hausdorff distance, the surface Dice at a tolerance
+and the vertical cup-to-disc ratio are closed forms of - still one copy per batch.
+
+    python -m uda_clr_amd.evaluate --data-dir DIR --dataset Drishti-GS --checkpoint FILE [--hd95] [--tolerance 2 ...] [--cdr]
+                                   [--csv per_image.csv] [--json result.json]
 """
+import argparse
+import csv
+import json
+import sys
+
 import numpy as np
 import torch
 
@@ -20,7 +32,15 @@ def _names(sample, B, seen):
     return [str(n) for n in ([names] if isinstance(names, str) else list(names))]
 
 
-def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True):
+def extra_fields(hd95=False, tolerances=(), cdr=False):
+    """names of the per-image figures that ``evaluate`` adds for these arguments, in the order of its tables"""
+    names = ["cup_hd95", "disc_hd95"] if hd95 else []
+    for tau in tolerances:
+        names += ["cup_nsd_%g" % tau, "disc_nsd_%g" % tau]
+    return tuple(names + (["vcdr_pred", "vcdr_gt", "cdr_error"] if cdr else []))
+
+
+def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=False, tolerances=(), cdr=False):
     """Score ``model`` on every image of ``loader``.
 
     model       callable whose first output (or only output) is the [B,2,H,W] logits (cup, disc), e.g. ``DeepLab``
@@ -30,7 +50,15 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True):
 
     -> {'per_image': [{'img_name', 'cup_dice', 'disc_dice', 'cup_assd', 'disc_assd', 'cup_hd', 'disc_hd'}, ...],
         'mean': nanmean of each field, 'n_images', 'n_undefined': {'cup', 'disc'}}; distances in pixels.  An (image, class) whose
-    predicted or true mask is empty has NaN distances and is counted in ``n_undefined``."""
+    predicted or true mask is empty has NaN distances and is counted in ``n_undefined``.
+
+    hd95        True: also 'cup_hd95', 'disc_hd95', the 95th percentile of the distances of both directions pooled (medpy's hd95)
+    tolerances  pixel distances tau: also 'cup_nsd_<tau>', 'disc_nsd_<tau>' (tau as %g), the share of both borders' pixels within tau
+                of the other border (d2 <= floor(tau^2))
+    cdr         True: also 'vcdr_pred', 'vcdr_gt' (cup height / disc height in rows, NaN without a disc) and 'cdr_error' = |pred - gt|
+    With any of the three set, per-image dicts and 'mean' carry the added names and the result lists them as 'extra_fields'."""
+    tolerances = tuple(float(t) for t in tolerances)
+    extra = extra_fields(hd95, tolerances, cdr)
     dev = torch.device("cuda") if torch.cuda.is_available() else None
     was_training = getattr(model, "training", False)
     if hasattr(model, "eval"):
@@ -52,18 +80,128 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True):
                 else:
                     thr_cup, thr_disc = (0.1, 0.5) if dataset[0] == 'D' else (threshold, threshold)
                     pred = torch.stack([prob[:, 0] > thr_cup, prob[:, 1] > thr_disc], 1)
-                table, counts = ops.surface_distances(pred, target > 0.5)           # the batch's one copy to the host
+                if extra:                                                            # the batch's one copy to the host, either way
+                    table, counts, profile = ops.surface_profile(pred, target > 0.5, percentiles=(95,) if hd95 else (), tolerances=tolerances)
+                else:
+                    table, counts = ops.surface_distances(pred, target > 0.5)
                 dice = metrics.dice_per_image(counts)
                 sm = metrics.surface_metrics_from_table(table)
+                more = {}
+                if hd95:
+                    h = metrics.percentile_distance_from_profile(table, profile)["hd_p"][..., 0]
+                    more["cup_hd95"], more["disc_hd95"] = h[:, 0], h[:, 1]
+                if tolerances:
+                    nsd = metrics.surface_dice_from_profile(table, profile)
+                    for t, tau in enumerate(tolerances):
+                        more["cup_nsd_%g" % tau], more["disc_nsd_%g" % tau] = nsd[:, 0, t], nsd[:, 1, t]
+                if cdr:
+                    more.update(metrics.vertical_cdr_from_profile(profile))
                 for i, name in enumerate(_names(sample, dice.shape[0], len(per_image))):
                     per_image.append({"img_name": name,
                                       "cup_dice": float(dice[i, 0]), "disc_dice": float(dice[i, 1]),
                                       "cup_assd": float(sm["assd"][i, 0]), "disc_assd": float(sm["assd"][i, 1]),
                                       "cup_hd": float(sm["hd"][i, 0]), "disc_hd": float(sm["hd"][i, 1])})
+                    per_image[-1].update({k: float(more[k][i]) for k in extra})
     finally:
         if was_training and hasattr(model, "train"):
             model.train()
-    cols = {k: np.array([r[k] for r in per_image], np.float64) for k in FIELDS}
+    cols = {k: np.array([r[k] for r in per_image], np.float64) for k in FIELDS + extra}
     mean = {k: (float(np.nanmean(v)) if np.isfinite(v).any() else float("nan")) for k, v in cols.items()}
-    return {"per_image": per_image, "mean": mean, "n_images": len(per_image),
-            "n_undefined": {"cup": int(np.isnan(cols["cup_assd"]).sum()), "disc": int(np.isnan(cols["disc_assd"]).sum())}}
+    res = {"per_image": per_image, "mean": mean, "n_images": len(per_image),
+           "n_undefined": {"cup": int(np.isnan(cols["cup_assd"]).sum()), "disc": int(np.isnan(cols["disc_assd"]).sum())}}
+    if extra:
+        res["extra_fields"] = extra
+    return res
+
+
+# ------------------------------------------------------------------------------------------------------------ command line
+class _Compose(object):
+    def __init__(self, transforms):
+        self.transforms = transforms
+
+    def __call__(self, sample):
+        for t in self.transforms:
+            sample = t(sample)
+        return sample
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="python -m uda_clr_amd.evaluate", description="Per-image evaluation of a DeepLab checkpoint on a fundus test split.")
+    ap.add_argument("--data-dir", required=True, help="root that holds <dataset>/<split>/ROIs/{image,mask}")
+    ap.add_argument("--dataset", default="Drishti-GS")
+    ap.add_argument("--split", default="test")
+    ap.add_argument("--checkpoint", required=True, help="file with a 'model_state_dict'")
+    ap.add_argument("--backbone", default="mobilenet")
+    ap.add_argument("--out-stride", type=int, default=16)
+    ap.add_argument("--use_TN", action="store_true", help="TransNorm in place of BatchNorm, as the trainers' switch")
+    ap.add_argument("--batch-size", type=int, default=8)
+    ap.add_argument("--threshold", type=float, default=0.75)
+    ap.add_argument("--no-postprocess", action="store_true", help="the plain thresholds only")
+    ap.add_argument("--hd95", action="store_true")
+    ap.add_argument("--tolerance", type=float, nargs="+", default=[], metavar="TAU", help="surface Dice at these pixel tolerances")
+    ap.add_argument("--cdr", action="store_true", help="vertical cup-to-disc ratio and its error")
+    ap.add_argument("--csv", default=None, metavar="PATH", help="one row per image")
+    ap.add_argument("--json", default=None, metavar="PATH", help="the whole result")
+    return ap
+
+
+def write_csv(path, res):
+    """img_name and the fields of ``res`` (the six of FIELDS, then its 'extra_fields'), one row per image; NaN is written as nan"""
+    fields = FIELDS + tuple(res.get("extra_fields", ()))
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(("img_name",) + fields)
+        for r in res["per_image"]:
+            w.writerow([r["img_name"]] + [repr(float(r[k])) for k in fields])
+
+
+def write_json(path, res):
+    """the whole result; NaN as the JSON extension ``NaN`` that ``json.load`` reads back"""
+    with open(path, "w") as f:
+        json.dump(dict(res, extra_fields=list(res.get("extra_fields", ()))), f, indent=1)
+        f.write("\n")
+
+
+def format_mean(res):
+    fields = FIELDS + tuple(res.get("extra_fields", ()))
+    return "mean over %d images: " % res["n_images"] + "  ".join("%s %.4f" % (k, res["mean"][k]) for k in fields)
+
+
+def load_generator(checkpoint, backbone="mobilenet", out_stride=16, use_TN=False, device=None):
+    """A DeepLab with the checkpoint's 'model_state_dict' loaded by the trainers' key filter (train_use_fix_initial.py:231-238):
+    keys the model does not have are dropped, keys the file does not have keep their initial value."""
+    from .networks.deeplabv3 import DeepLab
+    model = DeepLab(num_classes=2, backbone=backbone, output_stride=out_stride, sync_bn=not use_TN)
+    pretrained = torch.load(checkpoint, map_location="cpu", weights_only=True)["model_state_dict"]
+    model_dict = model.state_dict()
+    model_dict.update({k: v for k, v in pretrained.items() if k in model_dict})
+    model.load_state_dict(model_dict)
+    return model.to(device) if device is not None else model
+
+
+def main(argv=None, model=None):
+    """The command line.  ``model``: a callable to score instead of the checkpoint's DeepLab (tests)."""
+    args = build_parser().parse_args(argv)
+    from torch.utils.data import DataLoader
+    from .dataloaders import custom_transforms as tr
+    from .dataloaders.fundus_dataloader import FundusSegmentation
+    data = FundusSegmentation(base_dir=args.data_dir, dataset=args.dataset, split=args.split,
+                              transform=_Compose([tr.Normalize_tf(), tr.ToTensor()]))
+    if len(data) == 0:
+        raise SystemExit("no images under %s/%s/%s/ROIs/image" % (args.data_dir, args.dataset, args.split))
+    loader = DataLoader(data, batch_size=args.batch_size, shuffle=False, num_workers=0)
+    if model is None:
+        model = load_generator(args.checkpoint, args.backbone, args.out_stride, args.use_TN,
+                               torch.device("cuda") if torch.cuda.is_available() else None)
+    res = evaluate(model, loader, dataset=args.dataset, threshold=args.threshold, postprocess=not args.no_postprocess,
+                   hd95=args.hd95, tolerances=tuple(args.tolerance), cdr=args.cdr)
+    print(format_mean(res))
+    if args.csv:
+        write_csv(args.csv, res)
+    if args.json:
+        write_json(args.json, res)
+    return res
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

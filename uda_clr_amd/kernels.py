@@ -138,6 +138,8 @@ SYMBOLS = {
     "uda_postprocess": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _U, _P]),
     "uda_surface_distance_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_surface_distance": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _U, _P]),
+    "uda_surface_profile_workspace_bytes": (_U, [_I, _I, _I]),
+    "uda_surface_profile": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _U, _P]),
     "uda_normalize_tf_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_normalize_tf": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _U, _P]),
     "uda_field_smooth": (_I, [_P, _I, _I, _I, _P, _I, _D, _P, _P, _P]),
@@ -1236,6 +1238,39 @@ class HipKernels:
         self._ck(self.lib.uda_surface_distance(pred_u8.data_ptr(), gt_u8.data_ptr(), B, H, W, table.data_ptr(), counts.data_ptr(),
                                                _ptr(d2), ws.data_ptr(), ws.numel(), self._stream()))
         return (table, counts, d2) if want_d2 else (table, counts)
+
+    def surface_profile(self, pred_u8, gt_u8, quantiles, tol2, want_packed=False):
+        """uint8 [B,2,H,W] masks -> (table f64 [B,2,2,3], counts i64 [B,2,3], order i64 [B,2,3,Q,2], within i64 [B,2,2,T],
+        extent i64 [B,2,2,2]) on the device (include/uda_clr_hip.h, uda_surface_profile): table and counts as
+        ``surface_distance``; per set (pred -> gt, gt -> pred, both pooled) and quantile the two squared distances a percentile
+        interpolates between; per direction the border pixels within each squared tolerance; per mask its first and last row.
+        The five are views of one buffer of 8-byte words, handed back as a sixth value with ``want_packed`` (one copy moves all)."""
+        for t in (pred_u8, gt_u8):
+            self._dev(t)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != 2:
+                raise ValueError("surface_profile: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (t.dtype, tuple(t.shape)))
+        if pred_u8.shape != gt_u8.shape:
+            raise ValueError("surface_profile: shapes differ: %s and %s" % (tuple(pred_u8.shape), tuple(gt_u8.shape)))
+        q = [float(v) for v in quantiles]
+        t2 = [int(v) for v in tol2]
+        if any(not 0.0 <= v <= 1.0 for v in q):                   # also true for NaN
+            raise ValueError("surface_profile: quantiles must lie in [0, 1], got %r" % (q,))
+        if any(v < 0 or v > 2 ** 31 - 1 for v in t2):
+            raise ValueError("surface_profile: squared tolerances must lie in 0..2^31-1, got %r" % (t2,))
+        Q, T = len(q), len(t2)
+        B, _, H, W = pred_u8.shape
+        sizes = (B * 12, B * 6, B * 12 * Q, B * 4 * T, B * 8)
+        packed = torch.empty(sum(sizes), dtype=torch.int64, device=pred_u8.device)
+        table, counts, order, within, extent = torch.split(packed, sizes)
+        table = table.view(torch.float64).view(B, 2, 2, 3)
+        counts, order, within, extent = counts.view(B, 2, 3), order.view(B, 2, 3, Q, 2), within.view(B, 2, 2, T), extent.view(B, 2, 2, 2)
+        cq, ct = (C.c_double * max(Q, 1))(*q), (C.c_int32 * max(T, 1))(*t2)
+        ws = self._ws(pred_u8, self.lib.uda_surface_profile_workspace_bytes(B, H, W))
+        self._ck(self.lib.uda_surface_profile(pred_u8.data_ptr(), gt_u8.data_ptr(), B, H, W, C.addressof(cq), Q, C.addressof(ct), T,
+                                              table.data_ptr(), counts.data_ptr(), order.data_ptr(), within.data_ptr(), extent.data_ptr(),
+                                              None, ws.data_ptr(), ws.numel(), self._stream()))
+        out = (table, counts, order, within, extent)
+        return out + (packed,) if want_packed else out
 
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
         for t in (params, grads, exp_avg, exp_avg_sq):

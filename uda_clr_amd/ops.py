@@ -400,3 +400,38 @@ def surface_distances(pred_mask, gt_mask):
     B = table.shape[0]
     packed = torch.cat([table.reshape(-1), counts.view(torch.float64).reshape(-1)]).cpu().numpy()      # the one copy (it synchronises)
     return packed[:B * 12].reshape(B, 2, 2, 3), packed[B * 12:].view("int64").reshape(B, 2, 3)
+
+
+def surface_profile(pred_mask, gt_mask, percentiles=(95,), tolerances=()):
+    """``surface_distances`` plus what a percentile of the surface distances (hd95), the surface Dice at a tolerance and the vertical
+    cup-to-disc ratio are closed forms of, on the host after ONE synchronising copy.  Masks as ``surface_distances``.
+        percentiles  in [0, 100]; the kernel takes quantiles = np.true_divide(percentiles, 100)
+        tolerances   tau >= 0 in pixels; a border pixel is within tau when its squared distance d2 <= floor(tau * tau) (float64):
+                     d2 is an integer, so that is d2 <= tau^2
+    -> table, counts as ``surface_distances``, and profile = {
+        'order'   int64 [B,2,3,Q,2]: set 0 = pred -> gt, 1 = gt -> pred, 2 = both pooled; the lo-th and hi-th smallest squared distance
+                  around the virtual index (n - 1) * q; -1 where either border set is empty
+        'within'  int64 [B,2,2,T]: per direction the border pixels within each tolerance; -1 where either border set is empty
+        'extent'  int64 [B,2,2,2]: per mask (0 ground truth, 1 prediction) the first and last row with a set pixel; -1 if empty
+        'quantiles' float64 [Q], 'tolerances' float64 [T], 'tol2' int64 [T]: what was used}
+    (``utils.metrics.percentile_distance_from_profile`` / ``surface_dice_from_profile`` / ``vertical_cdr_from_profile``).
+    Runs on the device (uda_surface_profile); CPU tensors are moved there."""
+    import numpy as np
+    quantiles = np.true_divide(np.asarray(list(percentiles), np.float64), 100)
+    tol = np.asarray(list(tolerances), np.float64)
+    if not np.all((quantiles >= 0) & (quantiles <= 1)):
+        raise ValueError("surface_profile: percentiles must lie in [0, 100], got %r" % (tuple(percentiles),))
+    if not np.all((tol >= 0) & (tol * tol < 2.0 ** 31)):
+        raise ValueError("surface_profile: tolerances must be non-negative pixel distances, got %r" % (tuple(tolerances),))
+    tol2 = np.floor(tol * tol).astype(np.int64)
+    if not (pred_mask.is_cuda and gt_mask.is_cuda) and not torch.cuda.is_available():
+        raise RuntimeError("uda_clr_amd surface distances compute only on the MI355X HIP kernels (there is no CPU fallback)")
+    dev = pred_mask.device if pred_mask.is_cuda else (gt_mask.device if gt_mask.is_cuda else torch.device("cuda"))
+    packed = kernels().surface_profile(_mask_u8(pred_mask.detach().to(dev)), _mask_u8(gt_mask.detach().to(dev)), quantiles.tolist(),
+                                       tol2.tolist(), want_packed=True)[-1]
+    host = packed.cpu().numpy()                                                                          # the one copy (it synchronises)
+    B, Q, T = pred_mask.shape[0], len(quantiles), len(tol)
+    table, counts, order, within, extent = np.split(host, np.cumsum([B * 12, B * 6, B * 12 * Q, B * 4 * T]))
+    profile = {"order": order.reshape(B, 2, 3, Q, 2), "within": within.reshape(B, 2, 2, T), "extent": extent.reshape(B, 2, 2, 2),
+               "quantiles": quantiles, "tolerances": tol, "tol2": tol2}
+    return table.view(np.float64).reshape(B, 2, 2, 3), counts.reshape(B, 2, 3), profile

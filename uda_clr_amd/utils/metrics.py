@@ -84,3 +84,54 @@ def hd_2label(pred_mask, gt_mask):
     """(cup, disc) Hausdorff distance in pixels per image (arrays of length B) of [B,2,H,W] masks."""
     h = surface_metrics_from_table(ops.surface_distances(pred_mask, gt_mask)[0])["hd"]
     return h[:, 0], h[:, 1]
+
+
+# ---- closed forms of the profile of ops.surface_profile: percentiles of the surface distances (hd95 is medpy's
+# np.percentile(np.hstack((d_pred_gt, d_gt_pred)), 95)), the surface Dice at a tolerance, the vertical cup-to-disc ratio
+def _lerp(a, b, t):
+    """numpy's percentile interpolation between a <= b at weight t"""
+    d = b - a
+    return np.where(t >= 0.5, b - d * (1.0 - t), a + d * t)
+
+
+def percentile_distance_from_profile(table, profile):
+    """table [B,2,2,3], profile of ``ops.surface_profile`` -> {'hd_p' [B,2,Q]: the percentiles of the distances of both directions
+    pooled, 'hd_p_directed' [B,2,2,Q]: of pred -> gt and gt -> pred alone}, float64 pixels, NaN where either border set is empty.
+    With n distances in a set and quantile q the virtual index is v = (n - 1) * q (the kernel's own single multiply), and the value
+    lerp(sqrt(d2_lo), sqrt(d2_hi), v - floor(v)) of the lo-th and hi-th smallest squared distances the kernel selected."""
+    n = np.asarray(table, dtype=np.float64)[..., 0]                                  # [B,2,2]
+    order = np.asarray(profile["order"])                                                 # [B,2,3,Q,2]
+    q = np.asarray(profile["quantiles"], dtype=np.float64)
+    n3 = np.concatenate([n, n.sum(-1, keepdims=True)], -1)                               # [B,2,3]: pred -> gt, gt -> pred, pooled
+    undefined = (order < 0).any(-1)
+    v = np.maximum(n3 - 1.0, 0.0)[..., None] * q
+    root = np.sqrt(np.maximum(order, 0).astype(np.float64))
+    val = np.where(undefined, np.nan, _lerp(root[..., 0], root[..., 1], v - np.floor(v)))
+    return {"hd_p": val[:, :, 2], "hd_p_directed": val[:, :, :2]}
+
+
+def surface_dice_from_profile(table, profile):
+    """Surface Dice (NSD) per tolerance [B,2,T]: the share of the border pixels of both masks that lie within the tolerance of the
+    other mask's border, (within_0 + within_1) / (n_0 + n_1); NaN where either border set is empty."""
+    n = np.asarray(table, dtype=np.float64)[..., 0].sum(-1)                          # [B,2]
+    w = np.asarray(profile["within"])                                                    # [B,2,2,T]
+    undefined = (w < 0).any(2) | (n == 0)[..., None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(undefined, np.nan, w.sum(2).astype(np.float64) / n[..., None])
+
+
+def vertical_cdr_from_profile(profile):
+    """Vertical cup-to-disc ratio per image from the masks' row extents: diameter = last row - first row + 1 (0 for an empty mask),
+    vCDR = cup diameter / disc diameter, NaN where that disc is empty -> {'vcdr_pred', 'vcdr_gt', 'cdr_error' = |pred - gt|}, [B]."""
+    e = np.asarray(profile["extent"])                                                    # [B, class, slot, 2]
+    diam = np.where(e[..., 0] < 0, 0, e[..., 1] - e[..., 0] + 1).astype(np.float64)      # [B, class, slot]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vcdr = np.where(diam[:, 1] > 0, diam[:, 0] / diam[:, 1], np.nan)                 # [B, slot]
+    return {"vcdr_pred": vcdr[:, 1], "vcdr_gt": vcdr[:, 0], "cdr_error": np.abs(vcdr[:, 1] - vcdr[:, 0])}
+
+
+def hd95_2label(pred_mask, gt_mask):
+    """(cup, disc) 95th-percentile Hausdorff distance in pixels per image (arrays of length B) of [B,2,H,W] masks."""
+    table, _, profile = ops.surface_profile(pred_mask, gt_mask, percentiles=(95,))
+    h = percentile_distance_from_profile(table, profile)["hd_p"][..., 0]
+    return h[:, 0], h[:, 1]
