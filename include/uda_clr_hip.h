@@ -16,6 +16,9 @@
  *     16-byte aligned, at least round4(C) readable floats per row).  uda_src_t adds the pending
  *     per-channel transform the consumer applies on load:
  *         u[p,c] = act(x[p,c]*scale[c] + shift[c]) * (mask[p,c] * mask_scale)
+ *   - write footprint: an output matrix is written in rows [0, P) x columns [0, C) only (never the lanes [C, ld) of a row, so a
+ *     column window of a wider matrix is a valid output), a contiguous output within its stated shape, a workspace within the
+ *     queried bytes, an input never.  The one entry that writes lanes [C, round4(C)) says so (uda_dropout_mask).
  */
 #ifndef UDA_CLR_HIP_H
 #define UDA_CLR_HIP_H
@@ -341,7 +344,9 @@ int uda_gap_fwd(const float* x, int64_t ldx, int N, int HW, int C, float scale, 
 int uda_broadcast_rows(const float* g, int64_t ldg, int N, int HW, int C, float scale,
                        const float* addend, int64_t ld_add, float* out, int64_t ldo, void* stream);
 
-/* ---- dropout keep-mask, Philox4x32-10 counter stream (nn.Dropout at aspp.py:62, decoder.py:31,36,40) */
+/* ---- dropout keep-mask, Philox4x32-10 counter stream (nn.Dropout at aspp.py:62, decoder.py:31,36,40).
+ * Written in 4-byte words: round4(C) bytes of every row, i.e. also the lanes [C, round4(C)) - the mask must be a matrix of its
+ * own (ldm >= round4(C), 4-byte aligned), not a column window with live bytes beside it. */
 int uda_dropout_mask(uint8_t* mask, int64_t ldm, int64_t P, int C, float p, uint64_t seed,
                      uint64_t offset, void* stream);
 

@@ -35,11 +35,14 @@ def main():
             try:
                 err, tol = fn(dev)
                 torch.cuda.synchronize()
-                ok = err <= tol
+                import kernel_cases
+                spills = kernel_cases.footprint_violations()      # (the case itself began with a cleared registry)
+                ok = err <= tol and not spills
                 emit("%-48s err %.3e tol %.1e %s (%.2fs)" % (name, err, tol, "ok" if ok else "FAIL", time.time() - t0))
                 if not ok:
-                    import kernel_cases
                     emit("      detail: %s" % kernel_cases.DETAIL)
+                    if spills:
+                        emit("      writes outside the outputs (buffer, first position): %s" % spills)
                 nfail += (not ok)
             except Exception as e:  # noqa: BLE001
                 nfail += 1

@@ -4,6 +4,8 @@ worst relative error (max |a-b| / max |b|) over the outputs of that case and the
 Used by tests/test_kernels_gpu.py (asserting) and tests/gpu_report.py (printing everything)."""
 from __future__ import annotations
 
+import functools
+
 import torch
 
 from kernel_spec import SpecKernels
@@ -51,28 +53,216 @@ def padded(P, C, g, dev=None, scale=1.0, dtype=torch.float32):
     return buf[:, :C]
 
 
-def to_dev(t, dev):
-    """Move a [P, C] view keeping its row stride (so padding / alignment are preserved)."""
+# ------------------------------------------------------------------------------------- write footprints
+# Every device buffer a case hands to a kernel is a registered frame: the tensor the kernel sees, inside an allocation that the
+# test owns on both sides of it.  After the case, footprint_violations() compares the bits of every frame with a snapshot and
+# reports what changed outside the windows the kernels may write:
+#   strided [P, C] matrices (to_dev): GUARD_ROWS poisoned rows before and after the P rows; the window is rows [0, P) x columns
+#       [0, C) - the lanes [C, ld) of a row are "never written" (Padding lanes);
+#   contiguous outputs (out_dev) and workspaces (HipKernels._ws, patched while a case runs): GUARD_BYTES of 0xA5 on both sides;
+#   read-only operands (ro_dev, act_to): no window, every bit must survive.
+# Known limit: a spill that writes the identical bit pattern back is invisible - with the by-row poison, a NaN written onto a NaN
+# row.  The four fills alternate by row, so any spill that touches two consecutive rows is visible.
+#
+# GUARD_ROWS: the furthest a ragged last tile can reach behind row P - 1 (or before row 0) if its row guard were missing.
+#   dense convs (conv_plan.h): tiles of 64 / 128 / 256 pixel rows, the last one starts at a row < P: at most 255 rows behind;
+#   stem (dw_plan.h STEM_PIX_PER_WG): 256 pixels per workgroup: 255 rows;
+#   flat / channel-blocked depthwise (dw_plan.h): lanes x DW_ITER_FWD pixels per workgroup, 256 / (C / 4) lanes: 512 pixels at
+#       C = 4, 128 at the narrowest width any case uses (C = 64): 127 rows;
+#   spatial TH x TW tiles - depthwise 8 x 16 / 8 x 8 (DW_TILED_VARIANTS), upconv 16 x 16 (UPT_TH x UPT_TW), the narrow dense 3x3
+#       family 8 x 32 (N3_TW) and the 7x7 stride-1 stem 16 x 64 (H7_TH x H7_TW), resample one pixel per wave: the last tile of the
+#       last image ends at linear row (tiles_y * TH - 1) * W + tiles_x * TW - 1 of that image.  The largest over-hang in the suite
+#       is the stem's 1 x 33 x 80 shape (test_drn_kernels_gpu.py): tile rows 32..47 and columns 64..127 reach row 47 * 80 + 127 =
+#       3887 of P = 2640 rows, 1247 behind; the depthwise shapes stay below 8 * 16 + 16, upconv's tile kernel below 15 * 16 + 16.
+#   1280 is the next multiple of 256 above all of them.
+GUARD_ROWS = 1280          # multiple of 4: row 0 of the window keeps the poison phase and the 16-byte alignment of the allocation
+GUARD_BYTES = 4096
+_FRAMES = []
+
+
+class _Frame:
+    """bits: the whole allocation as a flat integer view; wins: [(offset, rows, pitch, width)] in elements of ``bits``;
+    origin / pitch / unit describe how a flat position is reported: (row, column) of a matrix, or a byte offset"""
+    __slots__ = ("name", "keep", "bits", "snap", "wins", "origin", "pitch", "unit")
+
+    def __init__(self, name, keep, bits, wins, origin, pitch, unit):
+        self.name, self.keep, self.bits, self.wins, self.origin, self.pitch, self.unit = name, keep, bits, wins, origin, pitch, unit
+        self.snap = bits.clone()
+
+    def where(self, i):
+        rel = i - self.origin
+        if self.pitch:
+            return (rel // self.pitch, rel % self.pitch)       # (row, column); row -1 / row P: the guard rows
+        return rel * self.unit                                  # byte offset from the first byte of the tensor
+
+
+_BITS = {4: torch.int32, 8: torch.int64, 1: torch.uint8, 2: torch.int16}
+
+
+def _flat_bits(t):
+    """a contiguous tensor's memory as a flat integer tensor of the same element size (bits are compared, not float values)"""
+    return t.view(-1).view(_BITS[t.element_size()])
+
+
+def _register(name, keep, bits, wins, origin, pitch, unit):
+    f = _Frame(name or "buffer %d" % len(_FRAMES), keep, bits, wins, origin, pitch, unit)
+    _FRAMES.append(f)
+    return f
+
+
+def _frame_of(t):
+    p = t.untyped_storage().data_ptr()
+    for f in _FRAMES:
+        if f.keep.untyped_storage().data_ptr() == p:
+            return f
+    raise KeyError("tensor is not part of a registered frame")
+
+
+def _window(f, v):
+    """the window of frame f that the view v covers (a [P, C] row-strided view, or any contiguous view)"""
+    isz = f.bits.element_size()
+    scale = v.element_size() // isz
+    off = v.storage_offset() * v.element_size() // isz
+    if v.dim() == 2 and not v.is_contiguous():
+        assert v.stride(1) == 1
+        return (off, v.shape[0], v.stride(0) * scale, v.shape[1] * scale)
+    assert v.is_contiguous()
+    return (off, 1, v.numel() * scale, v.numel() * scale)
+
+
+def footprint_begin():
+    del _FRAMES[:]
+
+
+def to_dev(t, dev, name=None):
+    """Move a [P, C] view keeping its row stride (so padding / alignment are preserved).  A strided view becomes rows
+    [GUARD_ROWS, GUARD_ROWS + P) of a registered frame of GUARD_ROWS + P + GUARD_ROWS rows with the same row stride; padding
+    lanes and guard rows hold the by-row poison, so a read out of range still leaks NaN / Inf into the compared values."""
     if t is None:
         return None
     if t.dim() == 2 and t.stride(0) != t.shape[1]:
-        base = torch.empty(t.shape[0], t.stride(0), dtype=t.dtype, device=dev)
+        P, ld, G = t.shape[0], t.stride(0), GUARD_ROWS
+        base = torch.empty(P + 2 * G, ld, dtype=t.dtype, device=dev)
         if t.dtype.is_floating_point:
             _poison(base)
         elif t.dtype == torch.uint8:
             base.copy_((torch.arange(base.numel(), device=dev) % 251).to(torch.uint8).view_as(base))      # keep-mask padding: arbitrary bytes
-        v = base[:, :t.shape[1]]
+        v = base[G:G + P, :t.shape[1]]
         v.copy_(t)
+        assert v.data_ptr() % 16 == 0 or ld * t.element_size() % 16
+        _register(name or "matrix %d [%d, %d]" % (len(_FRAMES), P, t.shape[1]), base, _flat_bits(base), [(G * ld, P, ld, t.shape[1])], G * ld, ld, t.element_size())
         return v
     return t.to(dev)
+
+
+def out_dev(shape, dtype, dev, fill=None, name=None, cols=None):
+    """A contiguous output (weight gradient, NCHW head, coefficient vector, statistics accumulator, byte mask): a 16-byte aligned
+    slice of a registered flat buffer with GUARD_BYTES of 0xA5 on both sides.  fill = None leaves the 0xA5 bytes in the tensor
+    (torch.empty), a number fills it.  cols: of a 2-D tensor only columns [0, cols) of each row are a kernel's to write."""
+    shape = (shape,) if isinstance(shape, int) else tuple(shape)
+    n = torch.empty(0, dtype=dtype).element_size()
+    for d in shape:
+        n *= d
+    buf = torch.full((2 * GUARD_BYTES + (n + 15) // 16 * 16,), 0xA5, dtype=torch.uint8, device=dev)
+    t = buf[GUARD_BYTES:GUARD_BYTES + n].view(dtype).view(shape)
+    assert t.data_ptr() % 16 == 0
+    if fill is not None:
+        t.fill_(fill)
+    win = (GUARD_BYTES, 1, n, n)
+    if cols is not None:
+        win = (GUARD_BYTES, shape[0], shape[1] * t.element_size(), cols * t.element_size())
+    _register(name or "output %d %s" % (len(_FRAMES), list(shape)), buf, buf, [win], GUARD_BYTES, 0, 1)
+    return t
+
+
+def out_like(t, dev, name=None):
+    """a contiguous operand that a kernel updates in place: out_dev holding t's values"""
+    return out_dev(t.shape, t.dtype, dev, name=name).copy_(t)
+
+
+def ro_dev(t, dev, name=None):
+    """an operand no kernel may write (weights, coefficient vectors, gradients read by a pass): checked whole"""
+    if t is None:
+        return None
+    if t.dim() == 2 and t.stride(0) != t.shape[1]:
+        return read_only(to_dev(t, dev, name))
+    x = t.to(dev) if t.device != torch.device(dev) else t.clone()
+    _register(name or "operand %d %s" % (len(_FRAMES), list(x.shape)), x, _flat_bits(x), [], 0, 0, x.element_size())
+    return x
+
+
+def read_only(t):
+    """from here on no bit of the frame behind t may change (its snapshot is taken now)"""
+    if t is not None:
+        f = _frame_of(t)
+        f.wins = []
+        f.snap.copy_(f.bits)
+    return t
+
+
+def only_writes(*views):
+    """Window cases: snapshot every frame now; until the next call of this function only the given views may change (all other
+    columns of their matrices, the guard rows, every other frame and the neighbouring slices of a shared arena may not)."""
+    for f in _FRAMES:
+        f.wins = []
+        f.snap.copy_(f.bits)
+    for v in views:
+        if v is not None:
+            f = _frame_of(v)
+            f.wins.append(_window(f, v))
+
+
+def guarded_ws(like, nbytes):
+    """stands in for HipKernels._ws while a case runs: exactly the queried bytes (16 where nothing is asked for, as the original),
+    16-byte aligned, inside a registered buffer with GUARD_BYTES of 0xA5 on both sides"""
+    n = int(nbytes) if int(nbytes) > 0 else 16
+    buf = torch.full((2 * GUARD_BYTES + (n + 15) // 16 * 16,), 0xA5, dtype=torch.uint8, device=like.device)
+    _register("workspace %d (%d bytes)" % (len(_FRAMES), n), buf, buf, [(GUARD_BYTES, 1, n, n)], GUARD_BYTES, 0, 1)
+    return buf[GUARD_BYTES:GUARD_BYTES + n]
+
+
+def footprint_violations():
+    """[(frame name, position)] of every registered frame with a changed bit outside its windows: position is (row, column) of
+    the first one in a strided matrix (row -1 / row P and beyond: guard rows; column >= C: padding lanes), else the byte offset
+    from the tensor's first byte (negative: before it; >= its size: behind it)."""
+    out = []
+    for f in _FRAMES:
+        d = f.bits != f.snap
+        for off, rows, pitch, width in f.wins:
+            d[off:off + rows * pitch].view(rows, pitch)[:, :width] = False
+        if bool(d.any()):
+            out.append((f.name, f.where(int(d.nonzero()[0]))))
+    return out
+
+
+class footprint:
+    """``with footprint():`` - an empty registry, and HipKernels._ws handing out guarded workspaces inside"""
+    def __enter__(self):
+        from uda_clr_amd.kernels import HipKernels
+        footprint_begin()
+        self.cls, self.keep = HipKernels, HipKernels.__dict__["_ws"]
+        HipKernels._ws = staticmethod(guarded_ws)
+        return self
+
+    def __exit__(self, *exc):
+        self.cls._ws = self.keep
+        return False
+
+
+def footprinted(fn):
+    """a case that begins with a cleared registry and runs under ``footprint``; the frames stay for footprint_violations()"""
+    @functools.wraps(fn)
+    def run(dev):
+        with footprint():
+            return fn(dev)
+    return run
 
 
 def act_to(a: Act, dev) -> Act:
     bn = None
     if a.bn is not None:
-        bn = BNRec(a.bn.key, a.bn.mean.to(dev), a.bn.invstd.to(dev), a.bn.count, a.bn.q1_border)
-    return Act(to_dev(a.x, dev), a.N, a.H, a.W, None if a.scale is None else a.scale.to(dev),
-               None if a.shift is None else a.shift.to(dev), a.act, to_dev(a.mask, dev), a.mask_scale, bn)
+        bn = BNRec(a.bn.key, ro_dev(a.bn.mean, dev), ro_dev(a.bn.invstd, dev), a.bn.count, a.bn.q1_border)
+    return Act(ro_dev(a.x, dev), a.N, a.H, a.W, ro_dev(a.scale, dev), ro_dev(a.shift, dev), a.act, ro_dev(a.mask, dev), a.mask_scale, bn)
 
 
 def make_src(N, H, W, C, g, lazy=True, act=ACT_RELU, mask=False, bn=False, q1=False):
@@ -108,23 +298,25 @@ def _check_route(got, route, mfma):
 
 def plan_route(K, q):
     """The route of a dense case's call from its recorded shape (``run.plan_query``) alone, without a GPU: stand-in addresses,
-    the row strides of ``padded``."""
+    the row strides of ``padded`` unless the query overrides them (ldx / ldy / ld_add: column windows of a wider matrix)."""
     s = UdaSrc()
-    s.x, s.ldx, s.N, s.H, s.W, s.C = 0x10000, round4(q["C"]) + 4, q["N"], q["H"], q["W"], q["C"]
+    s.x, s.ldx, s.N, s.H, s.W, s.C = 0x10000, q.get("ldx") or round4(q["C"]) + 4, q["N"], q["H"], q["W"], q["C"]
     if q["lazy"]:
         s.scale, s.shift, s.act = 0x20000, 0x30000, ACT_RELU
     if q["mask"]:
         s.mask, s.ldm = 0x40000, round4(q["C"])
-    ld = round4(q["Cout"]) + 4
+    ld = q.get("ldy") or round4(q["Cout"]) + 4
+    ld_add = q.get("ld_add") or ld
     if q["kind"] == "wgrad":
         return K.route(K.wgrad_args(s, q["Cout"], q["k"], q["dil"], q["origin"], q["stride"], 0x50000, ld, 0x60000))
     return K.route(K.conv_args(s, q["Cout"], q["k"], q["dil"], q["origin"], q["stride"], 0x50000, 0x70000 if q["bias"] else None,
-                               0x80000 if q["addend"] else None, ld if q["addend"] else 0, 0x90000, ld, 0xa0000 if q["stats"] else None))
+                               0x80000 if q["addend"] else None, ld_add if q["addend"] else 0, 0x90000, ld, 0xa0000 if q["stats"] else None))
 
 
-def _query(kind, N, H, W, C, Cout, k, dil, lazy=False, mask=False, bias=False, addend=False, stats=False, origin=0, stride=1):
+def _query(kind, N, H, W, C, Cout, k, dil, lazy=False, mask=False, bias=False, addend=False, stats=False, origin=0, stride=1,
+           ldx=None, ldy=None, ld_add=None):
     return dict(kind=kind, N=N, H=H, W=W, C=C, Cout=Cout, k=k, dil=dil, lazy=lazy, mask=mask, bias=bias, addend=addend, stats=stats,
-                origin=origin, stride=stride)
+                origin=origin, stride=stride, ldx=ldx, ldy=ldy, ld_add=ld_add)
 
 
 def case_conv(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, bias=False, addend=False, stats=True, seed=0, origin=0, stride=1, *, route):
@@ -142,10 +334,10 @@ def case_conv(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, bias=False, add
         SPEC.conv(src, SPEC.relayout_ohwi(w), k, dil, out_r, b, ad, st_r, origin=origin, **kw)
         K = hip()
         out_h = to_dev(padded(P, Cout, g), dev)
-        st_h = torch.zeros(16, 2, Cout, dtype=torch.float64, device=dev) if stats else None
-        wl = K.relayout_ohwi(w.to(dev))
+        st_h = out_dev((16, 2, Cout), torch.float64, dev, fill=0) if stats else None
+        wl = ro_dev(K.relayout_ohwi(w.to(dev)), dev)
         errs = [rel(wl, SPEC.relayout_ohwi(w))]
-        args = (act_to(src, dev), wl, k, dil, out_h, None if b is None else b.to(dev), to_dev(ad, dev), st_h)
+        args = (act_to(src, dev), wl, k, dil, out_h, ro_dev(b, dev), ro_dev(ad, dev), st_h)
         _check_route(K.conv_route(*args, origin=origin, **kw), route, K.mfma)
         K.conv(*args, origin=origin, **kw)
         errs.append(rel(out_h, out_r))
@@ -169,14 +361,14 @@ def case_dgrad(N, H, W, Cin, Cout, k, dil, accumulate=False, seed=1, *, route):
         if ad is not None:
             ref = ref + ad
         K = hip()
-        wd = K.relayout_dgrad(w.to(dev))
+        wd = ro_dev(K.relayout_dgrad(w.to(dev)), dev)
         e0 = rel(wd, SPEC.relayout_dgrad(w))
         out = to_dev(padded(P, Cin, g), dev)
         adh = to_dev(ad, dev)
         if accumulate:      # in-place accumulate, as the engine uses it
             out.copy_(adh)
             adh = out
-        args = (Act(to_dev(dy, dev), N, H, W), wd, k, dil, out)
+        args = (Act(ro_dev(dy, dev), N, H, W), wd, k, dil, out)
         _check_route(K.conv_route(*args, addend=adh), route, K.mfma)
         K.conv(*args, addend=adh)
         return max(e0, rel(out, ref)), 2e-5
@@ -192,9 +384,9 @@ def case_wgrad(N, H, W, Cin, Cout, k, dil, lazy=True, mask=False, seed=2, origin
         ref = torch.empty(Cout, Cin, k, k)
         kw = {"stride": stride} if stride != 1 else {}
         SPEC.conv_wgrad(src, dy, k, dil, ref, origin=origin, **kw)
-        out = torch.empty(Cout, Cin, k, k, device=dev)
+        out = out_dev((Cout, Cin, k, k), torch.float32, dev)
         K = hip()
-        args = (act_to(src, dev), to_dev(dy, dev), k, dil, out)
+        args = (act_to(src, dev), ro_dev(dy, dev), k, dil, out)
         _check_route(K.wgrad_route(*args, origin=origin, **kw), route, K.mfma)
         K.conv_wgrad(*args, origin=origin, **kw)
         return rel(out, ref), 3e-5
@@ -217,11 +409,11 @@ def case_dw(N, H, W, C, stride, dil, border, seed=3, *, route):
         Po = N * Ho * Wo
         K = hip()
         w9 = SPEC.relayout_dw(w)
-        w9h = K.relayout_dw(w.to(dev))
+        w9h = ro_dev(K.relayout_dw(w.to(dev)), dev)
         errs = [rel(w9h, w9)]
         y_r, st_r = padded(Po, C, g), torch.zeros(16, 2, C, dtype=torch.float64)
         SPEC.dwconv_fwd(src, w9, stride, dil, border, y_r, st_r)
-        y_h, st_h = to_dev(padded(Po, C, g), dev), torch.zeros(16, 2, C, dtype=torch.float64, device=dev)
+        y_h, st_h = to_dev(padded(Po, C, g), dev), out_dev((16, 2, C), torch.float64, dev, fill=0)
         sh = act_to(src, dev)
         for op, want in zip(("fwd", "dgrad", "wgrad"), route):
             got = _entry(K.dw_route(op, N, H, W, C, stride, dil))
@@ -232,12 +424,12 @@ def case_dw(N, H, W, C, stride, dil, border, seed=3, *, route):
         dx_r = padded(N * H * W, C, g)
         SPEC.dwconv_dgrad(dy, w9, stride, dil, N, H, W, dx_r)
         dx_h = to_dev(padded(N * H * W, C, g), dev)
-        K.dwconv_dgrad(to_dev(dy, dev), w9h, stride, dil, N, H, W, dx_h)
+        K.dwconv_dgrad(ro_dev(dy, dev), w9h, stride, dil, N, H, W, dx_h)
         errs.append(rel(dx_h, dx_r))
         dw_r = torch.empty(C, 1, 3, 3)
         SPEC.dwconv_wgrad(src, dy, stride, dil, border, dw_r)
-        dw_h = torch.empty(C, 1, 3, 3, device=dev)
-        K.dwconv_wgrad(sh, to_dev(dy, dev), stride, dil, border, dw_h)
+        dw_h = out_dev((C, 1, 3, 3), torch.float32, dev)
+        K.dwconv_wgrad(sh, ro_dev(dy, dev), stride, dil, border, dw_h)
         errs.append(rel(dw_h, dw_r))
         return max(errs), 3e-5
     run.dw_query, run.route = dict(N=N, H=H, W=W, C=C, stride=stride, dil=dil), route
@@ -262,14 +454,14 @@ def case_stem(N, H, W, seed=4, dy_offset=0, *, route):
         y_r, st_r = padded(Po, 32, g), torch.zeros(16, 2, 32, dtype=torch.float64)
         SPEC.stem_fwd(x, w, y_r, st_r)
         K = hip()
-        y_h, st_h = to_dev(padded(Po, 32, g), dev), torch.zeros(16, 2, 32, dtype=torch.float64, device=dev)
-        xh = x.to(dev)
+        y_h, st_h = to_dev(padded(Po, 32, g), dev), out_dev((16, 2, 32), torch.float64, dev, fill=0)
+        xh = ro_dev(x, dev)
         assert _entry(K.stem_route("fwd", xh)) == route[0], (K.stem_route("fwd", xh), route)
-        K.stem_fwd(xh, w.to(dev), y_h, st_h)
+        K.stem_fwd(xh, ro_dev(w, dev), y_h, st_h)
         dy = _stem_dy(Po, g, dy_offset)
-        dw_r, dw_h = torch.empty(32, 3, 3, 3), torch.empty(32, 3, 3, 3, device=dev)
+        dw_r, dw_h = torch.empty(32, 3, 3, 3), out_dev((32, 3, 3, 3), torch.float32, dev)
         SPEC.stem_wgrad(x, dy, dw_r)
-        dyh = _poison(torch.empty(Po, 33, device=dev))[:, 1:33].copy_(dy) if dy_offset else to_dev(dy, dev)
+        dyh = _poison(torch.empty(Po, 33, device=dev))[:, 1:33].copy_(dy) if dy_offset else ro_dev(dy, dev)
         assert (dyh.stride(0), dyh.data_ptr() % 16 == 0) == (q["lddy"], q["aligned"]), "stem_query does not describe the dy of this call"
         assert _entry(K.stem_route("wgrad", xh, dyh)) == route[1], (K.stem_route("wgrad", xh, dyh), route)
         K.stem_wgrad(xh, dyh, dw_h)
@@ -293,15 +485,15 @@ def case_transnorm(C, n0=300, n1=500, seed=9):
         st = st[:, torch.randperm(16, generator=g)]                  # any slot may hold the sums
         gamma, beta = 0.5 + torch.rand(C, generator=g), torch.randn(C, generator=g)
         cr = torch.randn(2, 2, C, generator=g)                        # [scale | shift][half][C], pre-filled as after bn_finalize
-        ch = cr.to(dev)
-        gr, gh = torch.empty(C), torch.empty(C, device=dev)
+        ch = out_like(cr, dev)
+        gr, gh = torch.empty(C), out_dev((C,), torch.float32, dev)
         SPEC.tn_gain(st[0], st[1], float(n0), float(n1), 1e-5, cr[0, 0], cr[1, 0], cr[0, 1], cr[1, 1], gr)
         sth = st.to(dev)
         K.tn_gain(sth[0], sth[1], float(n0), float(n1), 1e-5, ch[0, 0], ch[1, 0], ch[0, 1], ch[1, 1], gh)
         errs = [rel(gh, gr), rel(ch, cr)]
         rms, rmt = torch.randn(C, generator=g), torch.randn(C, generator=g)
         rvs, rvt = 0.5 + torch.rand(C, generator=g), 0.5 + torch.rand(C, generator=g)
-        er, eh = torch.empty(2, C), torch.empty(2, C, device=dev)
+        er, eh = torch.empty(2, C), out_dev((2, C), torch.float32, dev)
         SPEC.tn_eval_coeffs(gamma, beta, rms, rvs, rmt, rvt, 1e-5, er[0], er[1])
         K.tn_eval_coeffs(gamma.to(dev), beta.to(dev), rms.to(dev), rvs.to(dev), rmt.to(dev), rvt.to(dev), 1e-5, eh[0], eh[1])
         errs.append(rel(eh, er))
@@ -317,22 +509,22 @@ def case_bn(P, C, q1=False, mask=False, training=True, seed=5, frozen=False):
         x = padded(P, C, g, scale=2.0)
         st_r = torch.zeros(16, 2, C, dtype=torch.float64)
         SPEC.colstats(x, st_r)
-        st_h = torch.zeros(16, 2, C, dtype=torch.float64, device=dev)
-        K.colstats(to_dev(x, dev), st_h)
+        st_h = out_dev((16, 2, C), torch.float64, dev, fill=0)
+        K.colstats(ro_dev(x, dev), st_h)
         errs.append(rel(st_h.sum(0), st_r.sum(0)))
         gamma, beta = 0.5 + torch.rand(C, generator=g), torch.randn(C, generator=g)
         rm, rv = torch.randn(C, generator=g), 0.5 + torch.rand(C, generator=g)
         cr = torch.empty(4, C)
-        ch = torch.empty(4, C, device=dev)
-        rmh, rvh = rm.to(dev), rv.to(dev)
+        ch = out_dev((4, C), torch.float32, dev)
+        rmh, rvh = out_like(rm, dev), out_like(rv, dev)
         cnt = float(P * (1.25 if q1 else 1.0))
         if training:
             SPEC.bn_finalize(st_r, cnt, gamma, beta, rm, rv, 0.1, 1e-5, cr[0], cr[1], cr[2], cr[3])
-            K.bn_finalize(st_h, cnt, gamma.to(dev), beta.to(dev), rmh, rvh, 0.1, 1e-5, ch[0], ch[1], ch[2], ch[3])
+            K.bn_finalize(st_h, cnt, ro_dev(gamma, dev), ro_dev(beta, dev), rmh, rvh, 0.1, 1e-5, ch[0], ch[1], ch[2], ch[3])
             errs += [rel(ch, cr), rel(rmh, rm), rel(rvh, rv)]
         else:
             SPEC.bn_eval_coeffs(gamma, beta, rm, rv, 1e-5, cr[0], cr[1])
-            K.bn_eval_coeffs(gamma.to(dev), beta.to(dev), rmh, rvh, 1e-5, ch[0], ch[1])
+            K.bn_eval_coeffs(ro_dev(gamma, dev), ro_dev(beta, dev), ro_dev(rm, dev), ro_dev(rv, dev), 1e-5, ch[0], ch[1])
             cr[2:], ch[2:] = 0.0, 0.0
             errs.append(rel(ch[:2], cr[:2]))
         # keep pre-activations away from the ReLU/ReLU6 kinks: there the gate legitimately depends
@@ -348,7 +540,7 @@ def case_bn(P, C, q1=False, mask=False, training=True, seed=5, frozen=False):
             o_r = padded(P, C, g)
             SPEC.bn_apply(src, o_r, res)
             o_h = to_dev(padded(P, C, g), dev)
-            K.bn_apply(act_to(src, dev), o_h, to_dev(res, dev))
+            K.bn_apply(act_to(src, dev), o_h, ro_dev(res, dev))
             errs.append(rel(o_h, o_r))
         if training or frozen:
             q1t = None
@@ -367,11 +559,11 @@ def case_bn(P, C, q1=False, mask=False, training=True, seed=5, frozen=False):
             s_r = torch.zeros(16, 3, C, dtype=torch.float64)
             SPEC.bnbwd_reduce(dU, y, s_r)
             yh = act_to(y, dev)
-            dUh = to_dev(dU, dev)
-            s_h = torch.zeros(16, 3, C, dtype=torch.float64, device=dev)
+            dUh = ro_dev(dU, dev)
+            s_h = out_dev((16, 3, C), torch.float64, dev, fill=0)
             K.bnbwd_reduce(dUh, yh, s_h)
             errs.append(rel(s_h.sum(0), s_r.sum(0)))
-            gr, gh = torch.empty(4, C), torch.empty(4, C, device=dev)
+            gr, gh = torch.empty(4, C), out_dev((4, C), torch.float32, dev)
             SPEC.bnbwd_finalize(s_r, y, gr[0], gr[1], gr[2], gr[3], q1_total=q1t)
             K.bnbwd_finalize(s_h, yh, gh[0], gh[1], gh[2], gh[3], q1_total=None if q1t is None else q1t.to(dev))
             errs.append(rel(gh[2:], gr[2:]))
@@ -411,10 +603,10 @@ def case_bnbwd_lowrank(P, C, k, mask, seed=9):
         w = torch.randn(k, C, generator=g) / C ** 0.5
         s_r = torch.zeros(16, 3, C, dtype=torch.float64)
         SPEC.bnbwd_reduce(None, y, s_r, lowrank=(d, w))
-        yh, dh, wh = act_to(y, dev), to_dev(wide, dev)[:, 4:4 + k], w.to(dev)
-        s_h = torch.zeros(16, 3, C, dtype=torch.float64, device=dev)
+        yh, dh, wh = act_to(y, dev), ro_dev(wide, dev)[:, 4:4 + k], ro_dev(w, dev)
+        s_h = out_dev((16, 3, C), torch.float64, dev, fill=0)
         K.bnbwd_reduce(None, yh, s_h, lowrank=(dh, wh))
-        s_m = torch.zeros(16, 3, C, dtype=torch.float64, device=dev)
+        s_m = out_dev((16, 3, C), torch.float64, dev, fill=0)
         dU = to_dev(padded(P, C, g), dev)
         dU.copy_(dh @ wh)
         K.bnbwd_reduce(dU, yh, s_m)
@@ -455,12 +647,12 @@ def case_mc_seg_head(N, h, w, H, W, Cf, Cl, reps, mask, seed=10):
         bias = torch.randn(2, generator=g)
         o_r, o_h = padded(P, 2, g), to_dev(padded(P, 2, g), dev)
         SPEC.mc_seg_head(feat, N, h, w, low, bnd, H, W, sc, sh, ACT_RELU, mk, 1.0 / 0.9, SPEC.relayout_ohwi(w4), bias, o_r)
-        K.mc_seg_head(to_dev(feat, dev), N, h, w, to_dev(low, dev), to_dev(bnd, dev), H, W, sc.to(dev), sh.to(dev), ACT_RELU,
-                      None if mk is None else to_dev(mbuf, dev)[:, :Cc], 1.0 / 0.9, K.relayout_ohwi(w4.to(dev)), bias.to(dev), o_h)
+        K.mc_seg_head(ro_dev(feat, dev), N, h, w, ro_dev(low, dev), ro_dev(bnd, dev), H, W, ro_dev(sc, dev), ro_dev(sh, dev), ACT_RELU,
+                      None if mk is None else ro_dev(mbuf, dev)[:, :Cc], 1.0 / 0.9, ro_dev(K.relayout_ohwi(w4.to(dev)), dev), ro_dev(bias, dev), o_h)
         st_r = torch.zeros(16, 2, Cc, dtype=torch.float64)
-        st_h = torch.zeros(16, 2, Cc, dtype=torch.float64, device=dev)
+        st_h = out_dev((16, 2, Cc), torch.float64, dev, fill=0)
         SPEC.upsample_stats(feat, N, h, w, H, W, st_r)
-        K.upsample_stats(to_dev(feat, dev), N, h, w, H, W, st_h)
+        K.upsample_stats(ro_dev(feat, dev), N, h, w, H, W, st_h)
         return max(rel(o_h, o_r), rel(st_h.sum(0), st_r.sum(0))), 2e-5
     return run
 
@@ -477,9 +669,9 @@ def case_upsample_stats(N, h, w, H, W, C, Cs, seed=8):
         wide_r[:, C:] = torch.randn(N * H * W, Cs - C, generator=g)
         wide_h[:, C:] = wide_r[:, C:].to(dev)
         st_r = torch.zeros(16, 2, Cs, dtype=torch.float64)
-        st_h = torch.zeros(16, 2, Cs, dtype=torch.float64, device=dev)
+        st_h = out_dev((16, 2, Cs), torch.float64, dev, fill=0)
         SPEC.upsample_fwd(x, N, h, w, wide_r[:, :C], H, W, stats=st_r)
-        K.upsample_fwd(to_dev(x, dev), N, h, w, wide_h[:, :C], H, W, stats=st_h)
+        K.upsample_fwd(ro_dev(x, dev), N, h, w, wide_h[:, :C], H, W, stats=st_h)
         SPEC.colstats_window(wide_r[:, C:], st_r, C)
         K.colstats_window(wide_h[:, C:], st_h, C)
         full = torch.zeros(16, 2, Cs, dtype=torch.float64)
@@ -495,14 +687,14 @@ def case_resample(N, h, w, H, W, C, seed=6):
         x = padded(N * h * w, C, g)
         o_r, o_h = padded(N * H * W, C, g), to_dev(padded(N * H * W, C, g), dev)
         SPEC.upsample_fwd(x, N, h, w, o_r, H, W)
-        K.upsample_fwd(to_dev(x, dev), N, h, w, o_h, H, W)
+        K.upsample_fwd(ro_dev(x, dev), N, h, w, o_h, H, W)
         ref_t = torch.nn.functional.interpolate(x.reshape(N, h, w, C).permute(0, 3, 1, 2), size=(H, W), mode="bilinear",
                                                 align_corners=True).permute(0, 2, 3, 1).reshape(N * H * W, C)
         errs = [rel(o_h, o_r), rel(o_h, ref_t)]
         d = padded(N * H * W, C, g)
         dx_r, dx_h = padded(N * h * w, C, g), to_dev(padded(N * h * w, C, g), dev)
         SPEC.upsample_bwd(d, N, H, W, dx_r, h, w)
-        K.upsample_bwd(to_dev(d, dev), N, H, W, dx_h, h, w)
+        K.upsample_bwd(ro_dev(d, dev), N, H, W, dx_h, h, w)
         errs.append(rel(dx_h, dx_r))
         return max(errs), 2e-5
     return run
@@ -513,9 +705,9 @@ def case_head(N, h, w, H, W, C, seed=7):
         g = gen(seed)
         K = hip()
         x = padded(N * h * w, C, g)
-        o_r, o_h = torch.empty(N, C, H, W), torch.empty(N, C, H, W, device=dev)
+        o_r, o_h = torch.empty(N, C, H, W), out_dev((N, C, H, W), torch.float32, dev)
         SPEC.head_upsample_fwd(x, N, h, w, o_r)
-        K.head_upsample_fwd(to_dev(x, dev), N, h, w, o_h)
+        K.head_upsample_fwd(ro_dev(x, dev), N, h, w, o_h)
         ref_t = torch.nn.functional.interpolate(x.reshape(N, h, w, C).permute(0, 3, 1, 2), size=(H, W), mode="bilinear",
                                                 align_corners=True)
         errs = [rel(o_h, o_r), rel(o_h, ref_t)]
@@ -524,10 +716,10 @@ def case_head(N, h, w, H, W, C, seed=7):
         dx_r = base.clone()
         SPEC.head_upsample_bwd(d, dx_r, N, h, w, True)
         dx_h = to_dev(base, dev)
-        K.head_upsample_bwd(d.to(dev), dx_h, N, h, w, True)
+        K.head_upsample_bwd(ro_dev(d, dev), dx_h, N, h, w, True)
         errs.append(rel(dx_h, dx_r))
         dx_h2 = to_dev(base, dev)
-        K.head_upsample_bwd(d.to(dev), dx_h2, N, h, w, False)
+        K.head_upsample_bwd(ro_dev(d, dev), dx_h2, N, h, w, False)
         errs.append(rel(dx_h2, dx_r - base))
         return max(errs), 2e-5
     return run
@@ -538,14 +730,14 @@ def case_gap(N, HW, C, seed=8):
         g = gen(seed)
         K = hip()
         x = padded(N * HW, C, g)
-        o_r, o_h = torch.empty(N, C), torch.empty(N, C, device=dev)
+        o_r, o_h = torch.empty(N, C), out_dev((N, C), torch.float32, dev)
         SPEC.gap_fwd(x, N, o_r, 1.0 / HW)
-        K.gap_fwd(to_dev(x, dev), N, o_h, 1.0 / HW)
+        K.gap_fwd(ro_dev(x, dev), N, o_h, 1.0 / HW)
         errs = [rel(o_h, o_r)]
         ad = padded(N * HW, C, g)
         b_r, b_h = padded(N * HW, C, g), to_dev(padded(N * HW, C, g), dev)
         SPEC.broadcast_rows(o_r, N, b_r, 0.25, ad)
-        K.broadcast_rows(o_r.to(dev), N, b_h, 0.25, to_dev(ad, dev))
+        K.broadcast_rows(ro_dev(o_r, dev), N, b_h, 0.25, ro_dev(ad, dev))
         errs.append(rel(b_h, b_r))
         return max(errs), 2e-5
     return run
@@ -554,11 +746,11 @@ def case_gap(N, HW, C, seed=8):
 def case_dropout(P, C, p, seed=9):
     def run(dev):
         K = hip()
-        m = torch.zeros(P, round4(C), dtype=torch.uint8, device=dev)[:, :C]
+        m = out_dev((P, round4(C)), torch.uint8, dev, fill=0)[:, :C]      # uda_dropout_mask writes round4(C) bytes per row (its documented shape)
         K.dropout_mask(m, p, 1234, 7)
-        m2 = torch.zeros(P, round4(C), dtype=torch.uint8, device=dev)[:, :C]
+        m2 = out_dev((P, round4(C)), torch.uint8, dev, fill=0)[:, :C]      # uda_dropout_mask writes round4(C) bytes per row (its documented shape)
         K.dropout_mask(m2, p, 1234, 7)
-        m3 = torch.zeros(P, round4(C), dtype=torch.uint8, device=dev)[:, :C]
+        m3 = out_dev((P, round4(C)), torch.uint8, dev, fill=0)[:, :C]      # uda_dropout_mask writes round4(C) bytes per row (its documented shape)
         K.dropout_mask(m3, p, 1234, 8)
         assert torch.equal(m, m2), "same (seed, offset) must reproduce the mask"
         assert not torch.equal(m, m3), "different offsets must give different masks"
@@ -733,8 +925,8 @@ def case_proto(B, h, C, mode, seed=12):
         errs.append(rel(w_h, w_r))
         s_r = torch.zeros(4, C + 1, dtype=torch.float64)
         SPEC.proto_reduce(feat, w_r, s_r)
-        s_h = torch.zeros(4, C + 1, dtype=torch.float64, device=dev)
-        fh, wh = to_dev(feat, dev), w_r.to(dev)
+        s_h = out_dev((4, C + 1), torch.float64, dev, fill=0)
+        fh, wh = ro_dev(feat, dev), ro_dev(w_r, dev)
         K.proto_reduce(fh, wh, s_h)
         errs += [rel(s_h, s_r), rel(K.proto_finalize(s_h), SPEC.proto_finalize(s_r))]
         dC = torch.randn(4, C, generator=g)
@@ -755,10 +947,10 @@ def case_adam(n, seed=13):
         g = gen(seed)
         p, gr = torch.randn(n, generator=g), torch.randn(n, generator=g)
         m, v = 0.1 * torch.randn(n, generator=g), torch.rand(n, generator=g) * 0.01
-        ph, mh, vh = p.to(dev), m.to(dev), v.to(dev)
+        ph, mh, vh = out_like(p, dev), out_like(m, dev), out_like(v, dev)
         for step in (1, 2, 7):
             SPEC.adam_step(p, gr, m, v, 1e-3, 0.9, 0.99, 1e-8, step)
-            hip().adam_step(ph, gr.to(dev), mh, vh, 1e-3, 0.9, 0.99, 1e-8, step)
+            hip().adam_step(ph, ro_dev(gr, dev), mh, vh, 1e-3, 0.9, 0.99, 1e-8, step)
         ref = torch.nn.Parameter(torch.randn(n, generator=gen(seed)))
         return max(rel(ph, p), rel(mh, m), rel(vh, v)), 1e-5
     return run
@@ -771,13 +963,13 @@ def case_feat4(P, C, seed=14):
         feat = padded(P, C, g)
         coef = torch.randn(4, C + 1, generator=g)
         o_r = SPEC.feat_dot4(feat, coef)
-        o_h = K.feat_dot4(to_dev(feat, dev), coef.to(dev))
+        o_h = K.feat_dot4(ro_dev(feat, dev), ro_dev(coef, dev))
         w = torch.randn(P, 4, generator=g)
         base = padded(P, C, g)
         d_r = base.clone()
         SPEC.feat_rank4(w, coef, d_r, True)
         d_h = to_dev(base, dev)
-        K.feat_rank4(w.to(dev), coef.to(dev), d_h, True)
+        K.feat_rank4(ro_dev(w, dev), ro_dev(coef, dev), d_h, True)
         return max(rel(o_h, o_r), rel(d_h, d_r)), 2e-5
     return run
 
@@ -831,12 +1023,12 @@ def case_stem7(N, H, W, seed=16):
         y_r, st_r = padded(Po, 64, g), torch.zeros(16, 2, 64, dtype=torch.float64)
         SPEC.stem7_fwd(x, w, y_r, st_r)
         K = hip()
-        y_h, st_h = to_dev(padded(Po, 64, g), dev), torch.zeros(16, 2, 64, dtype=torch.float64, device=dev)
-        K.stem7_fwd(x.to(dev), w.to(dev), y_h, st_h)
+        y_h, st_h = to_dev(padded(Po, 64, g), dev), out_dev((16, 2, 64), torch.float64, dev, fill=0)
+        K.stem7_fwd(ro_dev(x, dev), ro_dev(w, dev), y_h, st_h)
         dy = padded(Po, 64, g)
-        dw_r, dw_h = torch.empty(64, 3, 7, 7), torch.empty(64, 3, 7, 7, device=dev)
+        dw_r, dw_h = torch.empty(64, 3, 7, 7), out_dev((64, 3, 7, 7), torch.float32, dev)
         SPEC.stem7_wgrad(x, dy, dw_r)
-        K.stem7_wgrad(x.to(dev), to_dev(dy, dev), dw_h)
+        K.stem7_wgrad(ro_dev(x, dev), ro_dev(dy, dev), dw_h)
         return max(rel(y_h, y_r), rel(st_h.sum(0), st_r.sum(0)), rel(dw_h, dw_r)), 3e-5
     return run
 
@@ -849,12 +1041,12 @@ def case_maxpool(N, H, W, C, seed=17):
         Po = N * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1)
         z_r, i_r = padded(Po, C, g), torch.zeros(Po, round4(C), dtype=torch.uint8)[:, :C]
         SPEC.maxpool_fwd(src, z_r, i_r)
-        z_h, i_h = to_dev(padded(Po, C, g), dev), torch.zeros(Po, round4(C), dtype=torch.uint8, device=dev)[:, :C]
+        z_h, i_h = to_dev(padded(Po, C, g), dev), out_dev((Po, round4(C)), torch.uint8, dev, fill=0, cols=C)[:, :C]
         K.maxpool_fwd(act_to(src, dev), z_h, i_h)
         dz = padded(Po, C, g)
         du_r, du_h = padded(N * H * W, C, g), to_dev(padded(N * H * W, C, g), dev)
         SPEC.maxpool_bwd(dz, i_r, N, H, W, du_r)
-        K.maxpool_bwd(to_dev(dz, dev), i_h, N, H, W, du_h)
+        K.maxpool_bwd(ro_dev(dz, dev), i_h, N, H, W, du_h)
         return max(rel(z_h, z_r), float((i_h.cpu() != i_r).sum()), rel(du_h, du_r)), 1e-6
     return run
 
@@ -867,10 +1059,10 @@ def case_rows_stride(N, H, W, C, s, seed=18):
         big, small = padded(N * H * W, C, g), padded(Po, C, g)
         o_r, o_h = padded(Po, C, g), to_dev(padded(Po, C, g), dev)
         SPEC.rows_stride(big, N, H, W, s, o_r)
-        K.rows_stride(to_dev(big, dev), N, H, W, s, o_h)
+        K.rows_stride(ro_dev(big, dev), N, H, W, s, o_h)
         f_r, f_h = padded(N * H * W, C, g), to_dev(padded(N * H * W, C, g), dev)
         SPEC.rows_stride(small, N, H, W, s, f_r, scatter=True)
-        K.rows_stride(to_dev(small, dev), N, H, W, s, f_h, scatter=True)
+        K.rows_stride(ro_dev(small, dev), N, H, W, s, f_h, scatter=True)
         return max(rel(o_h, o_r), rel(f_h, f_r)), 0.0
     return run
 
@@ -890,7 +1082,7 @@ def case_bottleneck_tail(N, H, W, C, seed=19):
         dz = padded(a.P, C, g)
         g_r, g_h = padded(a.P, C, g), to_dev(padded(a.P, C, g), dev)
         SPEC.relu_gate(dz, z_r, g_r)
-        K.relu_gate(to_dev(dz, dev), to_dev(z_r, dev), g_h)
+        K.relu_gate(ro_dev(dz, dev), ro_dev(z_r, dev), g_h)
         errs.append(rel(g_h, g_r))
         return max(errs), 1e-6
     return run
@@ -942,17 +1134,17 @@ def case_s2d(N, H, W, C, nchw, vh=None, vw=None, seed=20):
         src = torch.randn(N, C, H, W, generator=g) if nchw else padded(N * H * W, C, g)
         z_r, z_h = padded(N * Hz * Wz, 4 * C, g), to_dev(padded(N * Hz * Wz, 4 * C, g), dev)
         SPEC.s2d_fwd(src, nchw, N, H, W, C, vh_, vw_, 0.2, z_r)
-        K.s2d_fwd(src.to(dev) if nchw else to_dev(src, dev), nchw, N, H, W, C, vh_, vw_, 0.2, z_h)
+        K.s2d_fwd(ro_dev(src, dev), nchw, N, H, W, C, vh_, vw_, 0.2, z_h)
         errs = [rel(z_h, z_r)]
         dz = torch.randn(N * Hz * Wz, 4 * C, generator=g)
         zs = torch.randn(N * Hz * Wz, 4 * C, generator=g)
         for sign in (None, zs):
             if nchw:
-                d_r, d_h = torch.empty(N, C, H, W), torch.empty(N, C, H, W, device=dev)
+                d_r, d_h = torch.empty(N, C, H, W), out_dev((N, C, H, W), torch.float32, dev)
             else:
                 d_r, d_h = padded(N * H * W, C, g), to_dev(padded(N * H * W, C, g), dev)
             SPEC.s2d_bwd(dz, sign, 0.2, N, H, W, C, vh_, vw_, d_r, nchw)
-            K.s2d_bwd(dz.to(dev), None if sign is None else sign.to(dev), 0.2, N, H, W, C, vh_, vw_, d_h, nchw)
+            K.s2d_bwd(ro_dev(dz, dev), ro_dev(sign, dev), 0.2, N, H, W, C, vh_, vw_, d_h, nchw)
             errs.append(rel(d_h, d_r))
         return max(errs), 0.0
     return run
@@ -1221,14 +1413,14 @@ def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47):
         st_r = torch.zeros(16, 2, C, dtype=torch.float64)
         SPEC.upconv_fwd(gl, N, h, w, o_r, H, W, ad, dil, st_r)
         o_h = to_dev(padded(N * H * W, C, g), dev)
-        st_h = torch.zeros(16, 2, C, dtype=torch.float64, device=dev)
-        K.upconv_fwd(gl.to(dev), N, h, w, o_h, H, W, to_dev(ad, dev), dil, st_h)
+        st_h = out_dev((16, 2, C), torch.float64, dev, fill=0)
+        K.upconv_fwd(ro_dev(gl, dev), N, h, w, o_h, H, W, ro_dev(ad, dev), dil, st_h)
         errs = [rel(o_h, o_r), rel(st_h.sum(0), st_r.sum(0))]
         dy = padded(N * H * W, C, g)
         dg_r = torch.empty(N * h * w, 9 * C)
         SPEC.upconv_bwd(dy, N, H, W, dg_r, h, w, dil)
-        dg_h = torch.empty(N * h * w, 9 * C, device=dev)
-        K.upconv_bwd(to_dev(dy, dev), N, H, W, dg_h, h, w, dil)
+        dg_h = out_dev((N * h * w, 9 * C), torch.float32, dev)
+        K.upconv_bwd(ro_dev(dy, dev), N, H, W, dg_h, h, w, dil)
         errs.append(rel(dg_h, dg_r))
         return max(errs), 2e-5
     return run
@@ -1249,11 +1441,11 @@ def case_upconv_identity(N, h, w, H, W, Cf, Cl, Cout, seed=48):
         f2 = to_dev(f.permute(0, 2, 3, 1).reshape(N * h * w, Cf).contiguous(), dev)
         l2 = to_dev(low.permute(0, 2, 3, 1).reshape(N * H * W, Cl).contiguous(), dev)
         w_taps = wt[:, :Cf].permute(2, 3, 0, 1).reshape(9 * Cout, Cf, 1, 1).contiguous()
-        gl = torch.empty(N * h * w, 9 * Cout, device=dev)
+        gl = out_dev((N * h * w, 9 * Cout), torch.float32, dev)
         K.conv(Act(f2, N, h, w), K.relayout_ohwi(w_taps.to(dev)), 1, 1, gl)
-        y0 = torch.empty(N * H * W, Cout, device=dev)
+        y0 = out_dev((N * H * W, Cout), torch.float32, dev)
         K.conv(Act(l2, N, H, W), K.relayout_ohwi(wt[:, Cf:].contiguous().to(dev)), 3, 1, y0)
-        y = torch.empty(N * H * W, Cout, device=dev)
+        y = out_dev((N * H * W, Cout), torch.float32, dev)
         K.upconv_fwd(gl, N, h, w, y, H, W, y0)
         return rel(y, ref), 2e-5
     return run
@@ -1370,13 +1562,13 @@ def case_adv_s2d(N, C, H, W, op, seed=73):
         x = 3 * torch.randn(N, C, H, W, generator=g)
         x[0, 0, 0, :4] = torch.tensor([30., -30., 90., -90.])          # saturated sigmoids: log(s + 1e-7) at s = 0 and s = 1
         Hz, Wz = (H + 5) // 2, (W + 5) // 2
-        z_r, z_h = torch.empty(N * Hz * Wz, 4 * C), torch.empty(N * Hz * Wz, 4 * C, device=dev)
+        z_r, z_h = torch.empty(N * Hz * Wz, 4 * C), out_dev((N * Hz * Wz, 4 * C), torch.float32, dev)
         SPEC.adv_s2d_fwd(x, op, z_r)
-        K.adv_s2d_fwd(x.to(dev), op, z_h)
+        K.adv_s2d_fwd(ro_dev(x, dev), op, z_h)
         dz = torch.randn(N * Hz * Wz, 4 * C, generator=g)
-        d_r, d_h = torch.empty_like(x), torch.empty(N, C, H, W, device=dev)
+        d_r, d_h = torch.empty_like(x), out_dev((N, C, H, W), torch.float32, dev)
         SPEC.adv_s2d_bwd(dz, x, op, d_r)
-        K.adv_s2d_bwd(dz.to(dev), x.to(dev), op, d_h)
+        K.adv_s2d_bwd(ro_dev(dz, dev), ro_dev(x, dev), op, d_h)
         return max(rel(z_h, z_r), rel(d_h, d_r)), 5e-6
     return run
 
@@ -1390,3 +1582,219 @@ CASES += [
     ("adv_s2d sigmoid C=1 64x64", case_adv_s2d(2, 1, 64, 64, 1)),
     ("adv_s2d entropy C=2 50x46", case_adv_s2d(2, 2, 50, 46, 2)),
 ]
+
+
+# ---------------------------------------------------------------- column windows of wide buffers, as engine.py's call sites use them
+# Each case builds one wide matrix whose columns outside the window hold live finite data, runs the producers in the engine's order and
+# after every call holds the window against the statement and every other bit - the other columns, the padding lanes, the guard rows,
+# the neighbouring slices of the shared fp64 arena, every operand - against its state before the call (only_writes).
+def _no_spill(what):
+    got = footprint_violations()
+    assert got == [], "%s wrote outside its window: (buffer, first position) %s" % (what, got)
+
+
+def _arena(sizes, dev):
+    """consecutive [16, nq, C] slices of one fp64 arena (engine.py _Arena.take), on the CPU and on the device"""
+    n = sum(16 * nq * C for nq, C in sizes)
+    ar, ah = torch.zeros(n, dtype=torch.float64), out_dev((n,), torch.float64, dev, fill=0, name="statistics arena")
+    out, off = [], 0
+    for nq, C in sizes:
+        m = 16 * nq * C
+        out.append((ar[off:off + m].view(16, nq, C), ah[off:off + m].view(16, nq, C)))
+        off += m
+    return out
+
+
+ASPP_BRANCHES = ((1, 1), (3, 6), (3, 12), (3, 18))
+
+
+def case_window_aspp(N, H, W, seed=80, *, routes):
+    """engine.py forward, ASPP: 1x1 and three dilated 3x3 convs 320 -> 256 with statistics into windows 0..3 of cat [P, 1280],
+    broadcast_rows into [1024, 1280)"""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        P = N * H * W
+        src = make_src(N, H, W, 320, g, lazy=False)
+        cat_r = padded(P, 1280, g)
+        cat_h = to_dev(cat_r, dev, name="cat")
+        st = _arena([(2, 256)] * 5, dev)
+        sh = act_to(src, dev)
+        errs = []
+        for j, (k, dil) in enumerate(ASPP_BRANCHES):
+            sl = slice(256 * j, 256 * (j + 1))
+            w = torch.randn(256, 320, k, k, generator=g) / (320 * k * k) ** 0.5
+            SPEC.conv(src, SPEC.relayout_ohwi(w), k, dil, cat_r[:, sl], None, None, st[j][0])
+            wl = ro_dev(K.relayout_ohwi(w.to(dev)), dev, name="weight %d" % j)
+            _check_route(K.conv_route(sh, wl, k, dil, cat_h[:, sl], stats=st[j][1]), routes[j], K.mfma)
+            only_writes(cat_h[:, sl], st[j][1])
+            K.conv(sh, wl, k, dil, cat_h[:, sl], stats=st[j][1])
+            _no_spill("conv %dx%d dil %d into window %d" % (k, k, dil, j))
+            errs += [rel(cat_h[:, sl], cat_r[:, sl]), rel(st[j][1].sum(0), st[j][0].sum(0))]
+        yg = padded(N, 256, g)
+        SPEC.broadcast_rows(yg, N, cat_r[:, 1024:1280], 1.0)
+        ygh = ro_dev(yg, dev, name="yg")
+        only_writes(cat_h[:, 1024:1280])
+        K.broadcast_rows(ygh, N, cat_h[:, 1024:1280], 1.0)
+        _no_spill("broadcast_rows into window 4")
+        errs.append(rel(cat_h, cat_r))
+        return max(errs), 2e-5
+    run.plan_queries = [(_query("conv", N, H, W, 320, 256, k, dil, stats=True, ldy=1284), routes[j]) for j, (k, dil) in enumerate(ASPP_BRANCHES)]
+    return run
+
+
+def case_window_decoder_fwd(N, h, w, H, W, seed=81, *, route):
+    """engine.py forward, decoder: xf [P, 305] (ld 308) assembled by upsample_fwd with statistics -> [0, 256), bn_apply ->
+    [256, 304), the 256 -> 1 boundary head (bias, keep-mask) -> [304, 305); then colstats_window over [256, 305)"""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        P = N * H * W
+        xf_r = _poison(torch.empty(P, 308))[:, :305]
+        xf_r.copy_(torch.randn(P, 305, generator=g))
+        xf_h = to_dev(xf_r, dev, name="xf")
+        (_, _), (s_r, s_h), (_, _) = st = _arena([(2, 48), (2, 305), (2, 256)], dev)
+        feat = padded(N * h * w, 256, g)
+        SPEC.upsample_fwd(feat, N, h, w, xf_r[:, 0:256], H, W, stats=s_r)
+        fh = ro_dev(feat, dev, name="feature")
+        only_writes(xf_h[:, 0:256], s_h)
+        K.upsample_fwd(fh, N, h, w, xf_h[:, 0:256], H, W, stats=s_h)
+        _no_spill("upsample_fwd into [0, 256)")
+        errs = [rel(xf_h[:, 0:256], xf_r[:, 0:256]), rel(s_h.sum(0), s_r.sum(0))]
+        lo = make_src(N, H, W, 48, g, True, ACT_RELU)
+        SPEC.bn_apply(lo, xf_r[:, 256:304], None)
+        loh = act_to(lo, dev)
+        only_writes(xf_h[:, 256:304])
+        K.bn_apply(loh, xf_h[:, 256:304], None)
+        _no_spill("bn_apply into [256, 304)")
+        errs.append(rel(xf_h[:, 256:304], xf_r[:, 256:304]))
+        b2 = make_src(N, H, W, 256, g, True, ACT_RELU, mask=True)
+        wt, b = torch.randn(1, 256, 1, 1, generator=g) / 16.0, torch.randn(1, generator=g)
+        SPEC.conv(b2, SPEC.relayout_ohwi(wt), 1, 1, xf_r[:, 304:305], b)
+        b2h, wl, bh = act_to(b2, dev), ro_dev(K.relayout_ohwi(wt.to(dev)), dev, name="head weight"), ro_dev(b, dev, name="head bias")
+        _check_route(K.conv_route(b2h, wl, 1, 1, xf_h[:, 304:305], bias=bh), route, K.mfma)
+        only_writes(xf_h[:, 304:305])
+        K.conv(b2h, wl, 1, 1, xf_h[:, 304:305], bias=bh)
+        _no_spill("conv1x1 256 -> 1 into [304, 305)")
+        errs.append(rel(xf_h[:, 304:305], xf_r[:, 304:305]))
+        SPEC.colstats_window(xf_r[:, 256:305], s_r, 256)
+        only_writes(s_h)
+        K.colstats_window(xf_h[:, 256:305], s_h, 256)
+        _no_spill("colstats_window over [256, 305)")
+        full = torch.zeros(16, 2, 305, dtype=torch.float64)
+        SPEC.colstats(xf_r, full)
+        errs += [rel(s_h.sum(0), s_r.sum(0)), rel(s_h.sum(0), full.sum(0)), rel(xf_h, xf_r)]
+        assert all(float(a.abs().sum()) == 0.0 for a in (st[0][1], st[2][1]))
+        return max(errs), 2e-5
+    run.plan_queries = [(_query("conv", N, H, W, 256, 1, 1, 1, lazy=True, mask=True, bias=True, ldy=308), route)]
+    return run
+
+
+def case_window_decoder_bwd(N, H, W, seed=82, *, route):
+    """engine.py backward, decoder: d_xf [P, 305] (ld 308, lanes 305..307 zeroed): bnbwd_apply (low-rank dU of the 305 -> 2 head) in
+    place over [:, :305], head_upsample_bwd accumulating into [304, 305), the 3x3 input gradient 48 <- 256 accumulating in place
+    into [256, 304).  The boundary head's NCHW gradient is four times d_xf's grid on each side; the zero lanes must still be zero bits."""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        P = N * H * W
+        base = torch.zeros(P, 308)
+        base[:, :305] = torch.randn(P, 305, generator=g)
+        d_r = base.clone()[:, :305]
+        d_h = to_dev(base[:, :305], dev, name="d_xf")
+        frame = _frame_of(d_h)
+        lanes = d_h.as_strided((P, 3), (308, 1), d_h.storage_offset() + 305)
+        lanes.zero_()                                                    # (to_dev poisons the lanes: the engine zeroes them)
+        x = padded(P, 305, g)
+        sc, shf = 0.5 + torch.rand(305, generator=g), 0.3 * torch.randn(305, generator=g)
+        x[(x * sc + shf).abs() < 1e-4] += 0.01
+        y = Act(x, N, H, W, sc, shf, ACT_RELU, None, 1.0, BNRec("t", 0.1 * torch.randn(305, generator=g), 0.5 + torch.rand(305, generator=g), float(P), False))
+        d2, w2 = padded(P, 2, g), torch.randn(2, 305, generator=g) / 305 ** 0.5
+        s_r = torch.zeros(16, 3, 305, dtype=torch.float64)
+        SPEC.bnbwd_reduce(None, y, s_r, lowrank=(d2, w2))
+        gr = torch.empty(4, 305)
+        SPEC.bnbwd_finalize(s_r, y, gr[0], gr[1], gr[2], gr[3])
+        SPEC.bnbwd_apply(None, y, gr[0], gr[1], d_r, d_r.clone(), lowrank=(d2, w2))
+        yh, d2h, w2h, gh = act_to(y, dev), ro_dev(d2, dev, name="d_x1b"), ro_dev(w2, dev, name="w_head"), ro_dev(gr, dev, name="c1 c2")
+        only_writes(d_h)
+        K.bnbwd_apply(None, yh, gh[0], gh[1], d_h, d_h, lowrank=(d2h, w2h))
+        _no_spill("bnbwd_apply in place over [:, :305]")
+        errs = [rel(d_h, d_r)]
+        gx2 = torch.randn(N, 1, 4 * H, 4 * W, generator=g)
+        SPEC.head_upsample_bwd(gx2, d_r[:, 304:305], N, H, W, True)
+        gx2h = ro_dev(gx2, dev, name="gx2")
+        only_writes(d_h[:, 304:305])
+        K.head_upsample_bwd(gx2h, d_h[:, 304:305], N, H, W, True)
+        _no_spill("head_upsample_bwd into [304, 305)")
+        errs.append(rel(d_h[:, 304:305], d_r[:, 304:305]))
+        dy = padded(P, 256, g)
+        wt = torch.randn(256, 48, 3, 3, generator=g) / (48 * 9) ** 0.5
+        ref = torch.nn.grad.conv2d_input((N, 48, H, W), wt, dy.reshape(N, H, W, 256).permute(0, 3, 1, 2), 1, 1, 1)
+        d_r[:, 256:304] += ref.permute(0, 2, 3, 1).reshape(P, 48)
+        wd, dyh = ro_dev(K.relayout_dgrad(wt.to(dev)), dev, name="low_dgrad weight"), Act(ro_dev(dy, dev, name="dy1"), N, H, W)
+        win = d_h[:, 256:304]
+        _check_route(K.conv_route(dyh, wd, 3, 1, win, addend=win), route, K.mfma)
+        only_writes(win)
+        K.conv(dyh, wd, 3, 1, win, addend=win)
+        _no_spill("dgrad3x3 48 <- 256 in place into [256, 304)")
+        errs.append(rel(d_h, d_r))
+        assert frame is _frame_of(lanes) and int((lanes.view(torch.int32) != 0).sum()) == 0, "lanes 305..307 are no longer zero bits"
+        return max(errs), 2e-5
+    run.plan_queries = [(_query("conv", N, H, W, 256, 48, 3, 1, addend=True, ldy=308, ld_add=308), route)]
+    return run
+
+
+def case_window_coef(first, seed=83):
+    """bn_finalize into the channel window [first, first + 256) of coef [4][1280] (engine.py: coef[q][..., sl]), and tn_gain over the
+    same window of the per-half coefficients [4][2][1280]"""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        sl = slice(first, first + 256)
+        xs = [2.0 * torch.randn(40, 256, generator=g) + 0.5, 0.7 * torch.randn(24, 256, generator=g) - 0.2]
+        (_, _), (s0r, s0h), (s1r, s1h), (_, _) = st = _arena([(2, 64), (2, 256), (2, 256), (2, 64)], dev)
+        SPEC.colstats(xs[0], s0r)
+        SPEC.colstats(xs[1], s1r)
+        s0h.copy_(s0r)
+        s1h.copy_(s1r)
+        gamma, beta = 0.5 + torch.rand(256, generator=g), torch.randn(256, generator=g)
+        rm, rv = torch.randn(256, generator=g), 0.5 + torch.rand(256, generator=g)
+        cr = torch.randn(4, 1280, generator=g)
+        ch = out_like(cr, dev, name="coef")
+        rmh, rvh, gah, beh = out_like(rm, dev, name="running mean"), out_like(rv, dev, name="running var"), ro_dev(gamma, dev), ro_dev(beta, dev)
+        SPEC.bn_finalize(s0r, 40.0, gamma, beta, rm, rv, 0.1, 1e-5, cr[0][sl], cr[1][sl], cr[2][sl], cr[3][sl])
+        only_writes(rmh, rvh, *(ch[q][sl] for q in range(4)))
+        K.bn_finalize(s0h, 40.0, gah, beh, rmh, rvh, 0.1, 1e-5, ch[0][sl], ch[1][sl], ch[2][sl], ch[3][sl])
+        _no_spill("bn_finalize into coef[q][%d:%d]" % (first, first + 256))
+        errs = [rel(ch, cr), rel(rmh, rm), rel(rvh, rv)]
+        tr = torch.randn(4, 2, 1280, generator=g)
+        th = out_like(tr, dev, name="coef per half")
+        gr, gh = torch.empty(256), out_dev((256,), torch.float32, dev, name="gain")
+        SPEC.tn_gain(s0r, s1r, 40.0, 24.0, 1e-5, tr[0][0][sl], tr[1][0][sl], tr[0][1][sl], tr[1][1][sl], gr)
+        only_writes(gh, th[0][0][sl], th[1][0][sl], th[0][1][sl], th[1][1][sl])
+        K.tn_gain(s0h, s1h, 40.0, 24.0, 1e-5, th[0][0][sl], th[1][0][sl], th[0][1][sl], th[1][1][sl], gh)
+        _no_spill("tn_gain over coef[q][h][%d:%d]" % (first, first + 256))
+        errs += [rel(th, tr), rel(gh, gr)]
+        return max(errs), 2e-6
+    return run
+
+
+# the routes of "conv1x1 320->256 P=N", "conv3x3 320->256 dil6" and "dgrad3x3 48<-256 addend" above: the wide row strides change none
+ASPP_ROUTES = ("ws 64x128 k1 xf0",) + (("ws 64x128 k3 xf0", "x3 128x128 k3"),) * 3
+DEC_BWD_ROUTE = ("low 64x64 pipe", "x3 256x64 k3")
+WINDOW_CASES = [
+    ("aspp windows of cat [128, 1280]: 2 x 8x8", case_window_aspp(2, 8, 8, routes=ASPP_ROUTES)),
+    ("aspp windows of cat [126, 1280]: 2 x 9x7 (ragged tiles)", case_window_aspp(2, 9, 7, routes=ASPP_ROUTES)),
+    ("decoder forward windows of xf [512, 308]: 2 x (4x4 -> 16x16)", case_window_decoder_fwd(2, 4, 4, 16, 16, route="heads 128x1")),
+    ("decoder forward windows of xf [286, 308]: 2 x (5x7 -> 13x11)", case_window_decoder_fwd(2, 5, 7, 13, 11, route="heads 128x1")),
+    ("decoder backward windows of d_xf [512, 308]: 2 x 16x16", case_window_decoder_bwd(2, 16, 16, route=DEC_BWD_ROUTE)),
+    ("decoder backward windows of d_xf [286, 308]: 2 x 13x11", case_window_decoder_bwd(2, 13, 11, route=DEC_BWD_ROUTE)),
+    ("coefficient window [0, 256) of [4][1280]", case_window_coef(0)),
+    ("coefficient window [512, 768) of [4][1280]", case_window_coef(512)),
+    ("coefficient window [1024, 1280) of [4][1280]", case_window_coef(1024)),
+]
+WINDOW_CASES = [(name, footprinted(fn)) for name, fn in WINDOW_CASES]
+
+
+# every case begins with a cleared footprint registry and runs with guarded workspaces (footprint_violations() after it)
+CASES = [(name, footprinted(fn)) for name, fn in CASES]

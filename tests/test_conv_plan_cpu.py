@@ -6,7 +6,7 @@ import os
 
 import pytest
 
-from kernel_cases import CASES, _declared, plan_route
+from kernel_cases import CASES, WINDOW_CASES, _declared, plan_route
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "uda_clr_amd", "lib", "libuda_clr_hip.so")
@@ -39,6 +39,17 @@ def test_declared_routes_are_what_the_library_plans(K, mode):
         got = plan_route(K, fn.plan_query)
         if got != _declared(fn.route, K.mfma):
             wrong[name] = (got, _declared(fn.route, K.mfma))
+    assert not wrong, wrong
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16x3"])
+def test_declared_routes_of_the_window_cases_are_what_the_library_plans(K, mode):
+    """the dense calls of the window cases (tests/test_footprint_gpu.py): column windows of wide matrices, ldy / ld_add far above Cout"""
+    K.mfma = K.MFMA_BF16X3 if mode == "bf16x3" else K.MFMA_F32
+    queries = [(name, q, route) for name, fn in WINDOW_CASES for q, route in getattr(fn, "plan_queries", [])]
+    assert len(queries) == 12 and all(q["ldy"] > q["Cout"] + 200 for _, q, _ in queries)
+    wrong = {(name, q["k"], q["dil"]): (plan_route(K, q), _declared(route, K.mfma)) for name, q, route in queries
+             if plan_route(K, q) != _declared(route, K.mfma)}
     assert not wrong, wrong
 
 

@@ -7,11 +7,18 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from kernel_cases import act_to, gen, hip, make_src, padded, to_dev
+from kernel_cases import act_to, footprint, footprint_violations, gen, hip, make_src, out_dev, padded, ro_dev, to_dev
 from uda_clr_amd.acts import ACT_NONE, ACT_RELU, Act
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
+
+
+@pytest.fixture(autouse=True)
+def _footprint():
+    """every test starts with an empty footprint registry and runs with guarded workspaces (kernel_cases.footprint)"""
+    with footprint():
+        yield
 
 # fp32 sums of at most 9 * 64 products (y, dx) and of N * Ho * Wo <= 3,000 products (dw, statistics; fp32 within a workgroup's
 # tile, fp64 across tiles): the bound test_xception_kernels_gpu.py uses for sums of this length
@@ -51,17 +58,18 @@ def test_stem7s1_matches_fp64(N, H, W):
 
     K = hip()
     yh = to_dev(padded(P, 16, g), DEV)
-    st = torch.zeros(16, 2, 16, dtype=torch.float64, device=DEV)
-    K.stem7s1_fwd(x.to(DEV), K.relayout_hwio(w.to(DEV)), yh, st)
+    st = out_dev((16, 2, 16), torch.float64, DEV, fill=0)
+    K.stem7s1_fwd(ro_dev(x, DEV), ro_dev(K.relayout_hwio(w.to(DEV)), DEV), yh, st)
     yh2 = to_dev(padded(P, 16, g), DEV)
-    K.stem7s1_fwd(x.to(DEV), K.relayout_hwio(w.to(DEV)), yh2, None)           # without the statistics epilogue
-    dwh = torch.empty(16, 3, 7, 7, device=DEV)
-    K.stem7s1_wgrad(x.to(DEV), to_dev(dy, DEV), dwh)
+    K.stem7s1_fwd(ro_dev(x, DEV), ro_dev(K.relayout_hwio(w.to(DEV)), DEV), yh2, None)           # without the statistics epilogue
+    dwh = out_dev((16, 3, 7, 7), torch.float32, DEV)
+    K.stem7s1_wgrad(ro_dev(x, DEV), ro_dev(dy, DEV), dwh)
     torch.cuda.synchronize()
     errs = {"y": _rel(yh, yr), "y_nostats": _rel(yh2, yr), "sum": _rel(st.sum(0)[0], yr.sum(0)),
             "sumsq": _rel(st.sum(0)[1], (yr * yr).sum(0)), "dw": _rel(dwh, dwr)}
     print(errs)
     assert max(errs.values()) < BOUND, errs
+    assert footprint_violations() == [], "a kernel wrote outside its outputs: (buffer, first position)"
 
 
 # (N, H, W, Cin, Cout, stride, BN + ReLU prologue): the model's pairs (16 -> 16; 16 -> 32 stride 2; 64 -> 64 stride 2, and
@@ -99,15 +107,15 @@ def test_conv3n_matches_fp64(N, H, W, Cin, Cout, stride, lazy):
     K = hip()
     sh = act_to(src, DEV)
     yh = to_dev(padded(Po, Cout, g), DEV)
-    st = torch.zeros(16, 2, Cout, dtype=torch.float64, device=DEV)
-    K.conv3n_fwd(sh, K.relayout_hwio(w.to(DEV)), stride, yh, st)
-    dwh = torch.empty(Cout, Cin, 3, 3, device=DEV)
-    K.conv3n_wgrad(sh, to_dev(dy, DEV), stride, dwh)
+    st = out_dev((16, 2, Cout), torch.float64, DEV, fill=0)
+    K.conv3n_fwd(sh, ro_dev(K.relayout_hwio(w.to(DEV)), DEV), stride, yh, st)
+    dwh = out_dev((Cout, Cin, 3, 3), torch.float32, DEV)
+    K.conv3n_wgrad(sh, ro_dev(dy, DEV), stride, dwh)
     # input gradient the way the engine forms it: the stride-1 kernel on the (zero-stuffed) gradient with flipped, transposed weights
-    dyf = to_dev(dy, DEV)
+    dyf = ro_dev(dy, DEV)
     if stride != 1:
         dyf = to_dev(padded(N * H * W, Cout, g), DEV)
-        K.rows_stride(to_dev(dy, DEV), N, H, W, stride, dyf, scatter=True)
+        K.rows_stride(ro_dev(dy, DEV), N, H, W, stride, dyf, scatter=True)
     dxh = to_dev(padded(N * H * W, Cin, g), DEV)
     K.conv3n_fwd(Act(dyf, N, H, W), K.relayout_hwio(w.to(DEV), True), 1, dxh, None)
     torch.cuda.synchronize()
@@ -115,6 +123,7 @@ def test_conv3n_matches_fp64(N, H, W, Cin, Cout, stride, lazy):
             "dx": _rel(dxh, _rows(dx)), "dw": _rel(dwh, dwr)}
     print(errs)
     assert max(errs.values()) < BOUND, errs
+    assert footprint_violations() == [], "a kernel wrote outside its outputs: (buffer, first position)"
 
 
 def test_statistics_are_added_into():
@@ -125,12 +134,13 @@ def test_statistics_are_added_into():
     K = hip()
     w = K.relayout_hwio(torch.randn(16, 16, 3, 3, generator=g).to(DEV))
     y = to_dev(padded(N * H * W, 16, g), DEV)
-    st = torch.zeros(16, 2, 16, dtype=torch.float64, device=DEV)
+    st = out_dev((16, 2, 16), torch.float64, DEV, fill=0)
     K.conv3n_fwd(src, w, 1, y, st)
     once = st.sum(0).clone()
     K.conv3n_fwd(src, w, 1, y, st)
     torch.cuda.synchronize()
     assert _rel(st.sum(0), 2 * once) < 1e-12
+    assert footprint_violations() == [], "a kernel wrote outside its outputs: (buffer, first position)"
 
 
 def test_entries_reject_what_no_kernel_serves():
@@ -146,7 +156,7 @@ def test_entries_reject_what_no_kernel_serves():
     with pytest.raises(RuntimeError, match="16, 32 or 64"):
         K.conv3n_fwd(src, torch.zeros(3, 3, 16, 128, device=DEV), 1, out)
     with pytest.raises(RuntimeError, match="16, 32 or 64"):
-        K.conv3n_wgrad(src, to_dev(padded(16, 128, g), DEV), 1, torch.empty(128, 16, 3, 3, device=DEV))
+        K.conv3n_wgrad(src, to_dev(padded(16, 128, g), DEV), 1, out_dev((128, 16, 3, 3), torch.float32, DEV))
     masked = act_to(make_src(1, 4, 4, 16, g, True, ACT_RELU, mask=True), DEV)
     with pytest.raises(RuntimeError, match="mask"):
         K.conv3n_fwd(masked, torch.zeros(3, 3, 16, 16, device=DEV), 1, to_dev(padded(16, 16, g), DEV))
@@ -154,3 +164,5 @@ def test_entries_reject_what_no_kernel_serves():
     w = K.relayout_ohwi(torch.zeros(32, 16, 3, 3, device=DEV))
     with pytest.raises(RuntimeError, match="stride 2"):
         K.conv(src, w, 3, 1, to_dev(padded(4, 32, g), DEV), stride=2)
+    torch.cuda.synchronize()
+    assert footprint_violations() == [], "a refused call wrote something: (buffer, first position)"

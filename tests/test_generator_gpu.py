@@ -42,6 +42,23 @@ def test_padding_columns_never_leak(monkeypatch):
     assert not bad, list(bad.items())[:10]
 
 
+def test_work_buffers_and_statistics_arena_are_written_inside(monkeypatch):
+    """The same poisoned forward and backward with every work buffer of the engine between guard rows and the statistics arenas
+    between guard doubles (engine_guards.guarded): every guard is bit-intact afterwards, the results meet the same bounds."""
+    import engine_guards
+    from uda_clr_amd import engine
+    monkeypatch.setattr(engine, "POISON_BUFFERS", True)
+    with engine_guards.guarded() as guards:
+        fwd, grads, stats, _ = model_cases.train_parity(DEV, S=96)
+        torch.cuda.synchronize()
+    assert guards.counts()[0] >= 100 and guards.counts()[1] >= 2, guards.counts()
+    assert guards.violations() == [], "(buffer, side, first changed guard element)"
+    assert max(fwd.values()) < 1e-3, fwd
+    assert stats < 1e-3
+    bad, gmean = model_cases.grads_ok(grads)
+    assert not bad, list(bad.items())[:10]
+
+
 @pytest.mark.parametrize("tag", ["64", "512"])
 def test_matches_reference_fixtures(tag):
     errs = model_cases.golden_parity(DEV, tag)
@@ -68,6 +85,37 @@ def test_resnet_train_forward_backward_matches_oracle():
     print("gradient noise vs the fp32 oracle's: geometric mean %.3f over %d tensors" % (gmean, len(grads)))
     assert not bad, list(bad.items())[:10]
     assert gmean < 4.0, gmean
+
+
+def _resnet_checks(fwd64, grads, stats):
+    """the bounds of test_resnet_train_forward_backward_matches_oracle"""
+    for n, (e, floor) in fwd64.items():
+        assert e < 3.0 * floor + 2e-4, (n, e, floor)
+    assert stats < 5e-3
+    bad, gmean = model_cases.grads_ok(grads)
+    assert not bad, list(bad.items())[:10]
+    assert gmean < 4.0, gmean
+
+
+def test_resnet_padding_columns_never_leak(monkeypatch):
+    """Every fp32 work matrix starts as NaN / Inf / 3e38 (engine.POISON_BUFFERS): same results as on clean buffers."""
+    from uda_clr_amd import engine
+    monkeypatch.setattr(engine, "POISON_BUFFERS", True)
+    fwd, grads, stats, fwd64 = model_cases.train_parity(DEV, S=96, backbone="resnet")
+    _resnet_checks(fwd64, grads, stats)
+
+
+def test_resnet_work_buffers_and_statistics_arena_are_written_inside(monkeypatch):
+    """the same run between guard rows / guard doubles (engine_guards.guarded): every guard bit-intact, same bounds"""
+    import engine_guards
+    from uda_clr_amd import engine
+    monkeypatch.setattr(engine, "POISON_BUFFERS", True)
+    with engine_guards.guarded() as guards:
+        fwd, grads, stats, fwd64 = model_cases.train_parity(DEV, S=96, backbone="resnet")
+        torch.cuda.synchronize()
+    assert guards.counts()[0] >= 100 and guards.counts()[1] >= 2, guards.counts()
+    assert guards.violations() == [], "(buffer, side, first changed guard element)"
+    _resnet_checks(fwd64, grads, stats)
 
 
 @pytest.mark.parametrize("tag", ["resnet_128", "resnet_256"])

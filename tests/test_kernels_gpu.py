@@ -1,8 +1,10 @@
-"""-m gpu: every HIP kernel, called through the C ABI, against its fp32 torch statement."""
+"""-m gpu: every HIP kernel, called through the C ABI, against its fp32 torch statement - and, after the values, against its write
+footprint: nothing outside the output windows, the queried workspace bytes and (never) a read-only operand may have changed
+(kernel_cases.footprint_violations)."""
 import pytest
 import torch
 
-from kernel_cases import CASES
+from kernel_cases import CASES, footprint_violations
 
 pytestmark = pytest.mark.gpu
 
@@ -12,6 +14,7 @@ def test_kernel_matches_spec(name, fn):
     err, tol = fn(torch.device("cuda:0"))
     torch.cuda.synchronize()
     assert err <= tol, "%s: rel err %.3e > %.1e" % (name, err, tol)
+    assert footprint_violations() == [], "%s wrote outside its outputs: (buffer, first position)" % name
 
 
 # ---- the dense-conv cases again with the wide tiles on the OTHER matrix instructions than the session default (UDA_CLR_MFMA):
@@ -32,6 +35,7 @@ def test_kernel_matches_spec_on_the_other_matrix_instructions(name, fn):
     finally:
         K.mfma = keep
     assert err <= tol, "%s (mfma mode %d): rel err %.3e > %.1e" % (name, 1 - keep, err, tol)
+    assert footprint_violations() == [], "%s (mfma mode %d) wrote outside its outputs: (buffer, first position)" % (name, 1 - keep)
 
 
 def test_operands_beyond_the_32_bit_offsets_run_as_image_groups():

@@ -34,6 +34,20 @@ def test_padding_columns_never_leak(monkeypatch):
     backbone_cases.train_checks(fwd64, grads, stats)
 
 
+def test_work_buffers_and_statistics_arena_are_written_inside(monkeypatch):
+    """The same poisoned run with every work buffer of the engine between guard rows and the statistics arenas between guard
+    doubles (engine_guards.guarded): every guard is bit-intact afterwards, the results meet the same bounds."""
+    import engine_guards
+    from uda_clr_amd import engine
+    monkeypatch.setattr(engine, "POISON_BUFFERS", True)
+    with engine_guards.guarded() as guards:
+        fwd, grads, stats, fwd64 = model_cases.train_parity(DEV, S=96, backbone="xception", oracle_forward=xception_ref.deeplab_forward)
+        torch.cuda.synchronize()
+    assert guards.counts()[0] >= 100 and guards.counts()[1] >= 2, guards.counts()
+    assert guards.violations() == [], "(buffer, side, first changed guard element)"
+    backbone_cases.train_checks(fwd64, grads, stats)
+
+
 @pytest.mark.parametrize("tag", ["xception_128", "xception_256", "xception_os8_128"])
 def test_matches_reference_fixtures(tag):
     backbone_cases.check_golden(golden_errors(DEV, tag))

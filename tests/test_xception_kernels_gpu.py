@@ -8,11 +8,18 @@ import torch
 import torch.nn.functional as F
 
 from dw_shapes import SHAPES, declared
-from kernel_cases import act_to, gen, hip, make_src, padded, to_dev
+from kernel_cases import act_to, footprint, footprint_violations, gen, hip, make_src, out_dev, padded, ro_dev, to_dev
 from uda_clr_amd.acts import ACT_NONE, ACT_RELU
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
+
+
+@pytest.fixture(autouse=True)
+def _footprint():
+    """every test starts with an empty footprint registry and runs with guarded workspaces (kernel_cases.footprint)"""
+    with footprint():
+        yield
 
 
 def _rel(a, b):
@@ -59,17 +66,18 @@ def test_depthwise_matches_fp64(family, N, H, W, C, stride, dil, lazy):
     w9 = K.relayout_dw(w.to(DEV))
     sh = act_to(src, DEV)
     yh = to_dev(padded(Po, C, g), DEV)
-    st = torch.zeros(16, 2, C, dtype=torch.float64, device=DEV)
+    st = out_dev((16, 2, C), torch.float64, DEV, fill=0)
     K.dwconv_fwd(sh, w9, stride, dil, 0, yh, st, family=family)
     dxh = to_dev(padded(N * H * W, C, g), DEV)
-    K.dwconv_dgrad(to_dev(dy, DEV), w9, stride, dil, N, H, W, dxh, family=family)
-    dwh = torch.empty(C, 1, 3, 3, device=DEV)
-    K.dwconv_wgrad(sh, to_dev(dy, DEV), stride, dil, 0, dwh, family=family)
+    K.dwconv_dgrad(ro_dev(dy, DEV), w9, stride, dil, N, H, W, dxh, family=family)
+    dwh = out_dev((C, 1, 3, 3), torch.float32, DEV)
+    K.dwconv_wgrad(sh, ro_dev(dy, DEV), stride, dil, 0, dwh, family=family)
     torch.cuda.synchronize()
     errs = {"y": _rel(yh, yr), "sum": _rel(st.sum(0)[0], yr.sum(0)), "sumsq": _rel(st.sum(0)[1], (yr * yr).sum(0)),
             "dx": _rel(dxh, _rows(dx)), "dw": _rel(dwh, dwr)}
     # fp32 sums of 9 products (y, dx) and of up to 9 * 300 products (dw, statistics): measured <= 1e-6 relative
     assert max(errs.values()) < 2e-5, errs
+    assert footprint_violations() == [], "a kernel wrote outside its outputs: (buffer, first position)"
 
 
 def test_stride1_input_gradient_is_the_flipped_forward():
@@ -84,10 +92,11 @@ def test_stride1_input_gradient_is_the_flipped_forward():
     a = to_dev(padded(N * H * W, C, g), DEV)
     b = to_dev(padded(N * H * W, C, g), DEV)
     from uda_clr_amd.acts import Act
-    K.dwconv_fwd(Act(to_dev(dy, DEV), N, H, W), w9.flip(0).contiguous(), 1, dil, 0, a, None)
-    K.dwconv_dgrad(to_dev(dy, DEV), w9, 1, dil, N, H, W, b)
+    K.dwconv_fwd(Act(ro_dev(dy, DEV), N, H, W), w9.flip(0).contiguous(), 1, dil, 0, a, None)
+    K.dwconv_dgrad(ro_dev(dy, DEV), w9, 1, dil, N, H, W, b)
     torch.cuda.synchronize()
     assert _rel(a, b) < 1e-6
+    assert footprint_violations() == [], "a kernel wrote outside its outputs: (buffer, first position)"
 
 
 def test_routed_entries_reject_what_no_kernel_serves():
@@ -98,3 +107,5 @@ def test_routed_entries_reject_what_no_kernel_serves():
     out = to_dev(padded(16, 2052, g), DEV)
     with pytest.raises(RuntimeError, match="2048"):
         K.dwconv_fwd(src, w9, 1, 1, 0, out)
+    torch.cuda.synchronize()
+    assert footprint_violations() == [], "a refused call wrote something: (buffer, first position)"
