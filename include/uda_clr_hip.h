@@ -400,13 +400,22 @@ int uda_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
  * caller runs the nine tap GEMMs at LOW resolution (g = f W_all^T, [N*h*w, 9*C], tap-major columns) and these kernels do
  * the interpolation.  fwd: y[p,:] = addend[p % addend_rows,:] + sum_t [p + d_t inside H x W] bilinear(g_t)(p + d_t),
  * align_corners=True, d_t = ((t/3) - 1, (t%3) - 1) * dil.  bwd: dg = adjoint of that sum applied to dy (gather form).
- * stats (double[UDA_STAT_SLOTS][2][C], ADDED into, or null): per-channel sum / sum of squares of y for the next BatchNorm;
- * uda_upconv_fused_stats tells whether a geometry supports them (otherwise accumulate with uda_colstats). */
-int uda_upconv_fused_stats(int h, int w, int H, int W, int C, int dil);
+ * stats (double[UDA_STAT_SLOTS][2][C], ADDED into, or null): per-channel sum / sum of squares of y for the next BatchNorm,
+ * for every geometry: accumulated by the interpolation kernel where its launch plan (csrc/upconv_plan.h) says so, by a
+ * uda_colstats launch over y after it on the same stream otherwise.  Since version 3 that includes operands beyond the 32-bit
+ * extents of the strip kernels (N*h*w*ldg*4 >= 2^31 bytes of g, ...), where a call with stats was refused before. */
 int uda_upconv_fwd(const float* g, int64_t ldg, int N, int h, int w, int C, int dil, const float* addend, int64_t ld_add,
                    int64_t addend_rows, float* y, int64_t ldy, int H, int W, double* stats, void* stream);
 int uda_upconv_bwd(const float* dy, int64_t ldy, int N, int H, int W, int C, int dil, float* dg, int64_t ldg, int h, int w,
                    void* stream);
+/* The launch planned for uda_upconv_fwd (op 0) / uda_upconv_bwd (op 1) as text: "fwd tile", "fwd strip3", "fwd strip4",
+ * "fwd pixel", "bwd wave" or "bwd thread", then the grid and for the tile kernel R, RC and lds; a forward route with want_stats
+ * ends in "stats fused" or "stats colstats"; "none" for refused arguments.  has_addend ... want_stats are not read for op 1.
+ * Same contract as uda_dwconv_route. */
+int uda_upconv_route(int op, int N, int h, int w, int H, int W, int C, int dil, int64_t ldg, int has_addend, int64_t ld_add,
+                     int64_t addend_rows, int want_stats, char* buf, int len);
+/* every "<op> <kernel>" uda_upconv_route can begin with, one per line */
+const char* uda_upconv_route_list(void);
 
 /* ---- evaluation post-processing of the predicted probability maps (utils/Utils.py:427-463: postprocessing +
  * get_largest_fillhole), per image and channel (0 cup, 1 disc): threshold -> 5 x 7x7 median (zero padded) -> erosion by the

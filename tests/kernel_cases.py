@@ -286,7 +286,8 @@ def make_src(N, H, W, C, g, lazy=True, act=ACT_RELU, mask=False, bn=False, q1=Fa
 # ------------------------------------------------------------------------------------- cases
 # Dense cases (conv / dgrad / wgrad) declare with ``route=`` the launch the library must plan for their call (HipKernels.conv_route /
 # wgrad_route: family, tile, template variant, splits).  The labels are the test ids and stay as they were written; where a label's
-# parenthesised remark about tiles or kernels and the route differ, the route is what runs - it is asserted.
+# parenthesised remark about tiles or kernels and the route differ, the route is what runs - it is asserted.  The same holds for the
+# depthwise, stem and upconv cases (HipKernels.dw_route / stem_route / upconv_route).
 def _declared(route, mfma):
     """a dense case's declared route: one text, or (f32, bf16x3) where the two MFMA modes differ"""
     return route if isinstance(route, str) else route[mfma]
@@ -1403,7 +1404,17 @@ CASES += [
 
 
 # ---------------------------------------------------------------- upsample-then-conv3x3 by low-resolution tap GEMMs + interpolation
-def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47):
+def upconv_routes(K, q):
+    """("fwd <kernel>", "bwd <kernel>") the library plans for an upconv case's two calls, from its recorded arguments
+    (``run.upconv_query``) alone - no GPU needed"""
+    fwd = K.upconv_route("fwd", q["N"], q["h"], q["w"], q["H"], q["W"], q["C"], q["dil"], q["ldg"], q["ld_add"], q["addend_rows"], stats=True)
+    return _entry(fwd), _entry(K.upconv_route("bwd", q["N"], q["h"], q["w"], q["H"], q["W"], q["C"], q["dil"], q["ldg"]))
+
+
+def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47, *, route=None):
+    """route: the "fwd <kernel>" / "bwd <kernel>" HipKernels.upconv_route must begin with for the two calls (asserted on the real
+    tensors before them, and without a GPU by test_upconv_plan_cpu.py, which also wants one of every case in CASES; None - the
+    shape fuzzer - asserts nothing).  As with the dense cases, where a label's remark and the route differ the route is what runs."""
     def run(dev):
         g = gen(seed)
         K = hip()
@@ -1414,7 +1425,13 @@ def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47):
         SPEC.upconv_fwd(gl, N, h, w, o_r, H, W, ad, dil, st_r)
         o_h = to_dev(padded(N * H * W, C, g), dev)
         st_h = out_dev((16, 2, C), torch.float64, dev, fill=0)
-        K.upconv_fwd(ro_dev(gl, dev), N, h, w, o_h, H, W, ro_dev(ad, dev), dil, st_h)
+        gl_h, ad_h = ro_dev(gl, dev), ro_dev(ad, dev)
+        q = run.upconv_query              # g and dg are contiguous [N*h*w, 9*C]
+        assert gl_h.stride(0) == q["ldg"] and (ad is None or (ad_h.stride(0), ad_h.shape[0]) == (q["ld_add"], q["addend_rows"])), \
+            "upconv_query does not describe the tensors of this call"
+        got = upconv_routes(K, q)
+        assert route is None or got == tuple(route), "planned routes %r, the case declares %r" % (got, route)
+        K.upconv_fwd(gl_h, N, h, w, o_h, H, W, ad_h, dil, st_h)
         errs = [rel(o_h, o_r), rel(st_h.sum(0), st_r.sum(0))]
         dy = padded(N * H * W, C, g)
         dg_r = torch.empty(N * h * w, 9 * C)
@@ -1423,6 +1440,9 @@ def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47):
         K.upconv_bwd(ro_dev(dy, dev), N, H, W, dg_h, h, w, dil)
         errs.append(rel(dg_h, dg_r))
         return max(errs), 2e-5
+    run.upconv_query = dict(N=N, h=h, w=w, H=H, W=W, C=C, dil=dil, ldg=9 * C, ld_add=None if addend_rows is None else round4(C) + 4,
+                            addend_rows=addend_rows or 0)
+    run.route = route
     return run
 
 
@@ -1452,21 +1472,29 @@ def case_upconv_identity(N, h, w, H, W, Cf, Cl, Cout, seed=48):
 
 
 CASES += [
-    ("upconv fwd/bwd 2 x (8x8 -> 32x32) x 64", case_upconv(2, 8, 8, 32, 32, 64)),
-    ("upconv fwd/bwd 1 x (5x7 -> 12x20) x 8, addend", case_upconv(1, 5, 7, 12, 20, 8, addend_rows=240)),
-    ("upconv fwd/bwd 4 x (4x4 -> 16x16) x 16, addend shared by 2 reps", case_upconv(4, 4, 4, 16, 16, 16, addend_rows=512)),
-    ("upconv fwd/bwd 1 x (16x16 -> 32x32) x 12 dil 2 (pixel kernel + colstats)", case_upconv(1, 16, 16, 32, 32, 12, dil=2)),
-    ("upconv fwd/bwd 2 x (16x16 -> 32x32) x 32 (x2: 4-column strips)", case_upconv(2, 16, 16, 32, 32, 32)),
-    ("upconv fwd/bwd 1 x (5x7 -> 13x18) x 8 (W % 4 != 0: pixel kernel), addend", case_upconv(1, 5, 7, 13, 18, 8, addend_rows=234)),
-    ("upconv fwd/bwd 2 x (1x1 -> 4x4) x 4 (degenerate source)", case_upconv(2, 1, 1, 4, 4, 4)),
-    ("upconv fwd/bwd 1 x (43x43 -> 128x128) x 8 (scale exactly 1/3: 4-column strips)", case_upconv(1, 43, 43, 128, 128, 8)),
-    ("upconv fwd/bwd 1 x (85x85 -> 128x128) x 8 (scale 0.661: 4-column strips)", case_upconv(1, 85, 85, 128, 128, 8)),
-    ("upconv fwd/bwd 1 x (86x86 -> 128x128) x 8 (scale 0.669: pixel kernel)", case_upconv(1, 86, 86, 128, 128, 8)),
-    ("upconv fwd/bwd 3 x (32x32 -> 128x128) x 256 (the decoder's shape)", case_upconv(3, 32, 32, 128, 128, 256, addend_rows=16384)),
-    ("upconv fwd/bwd 2 x (4x4 -> 16x16) x 256 (tile kernel, one tile; wave-per-pixel bwd)", case_upconv(2, 4, 4, 16, 16, 256, addend_rows=256)),
-    ("upconv fwd/bwd 1 x (5x9 -> 17x33) x 256 (exact ratio 1/4, odd sizes: strip / pixel fwd, wave bwd)", case_upconv(1, 5, 9, 17, 33, 256)),
-    ("upconv fwd/bwd 1 x (9x5 -> 32x16) x 256 (tile kernel, ratio 0.258 / 0.267), addend", case_upconv(1, 9, 5, 32, 16, 256, addend_rows=512)),
-    ("upconv fwd/bwd 2 x (16x16 -> 48x64) x 256 (tile kernel at x3 / x4.2)", case_upconv(2, 16, 16, 48, 64, 256)),
+    ("upconv fwd/bwd 2 x (8x8 -> 32x32) x 64", case_upconv(2, 8, 8, 32, 32, 64, route=("fwd tile", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (5x7 -> 12x20) x 8, addend", case_upconv(1, 5, 7, 12, 20, 8, addend_rows=240, route=("fwd strip3", "bwd thread"))),
+    ("upconv fwd/bwd 4 x (4x4 -> 16x16) x 16, addend shared by 2 reps", case_upconv(4, 4, 4, 16, 16, 16, addend_rows=512, route=("fwd strip3", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (16x16 -> 32x32) x 12 dil 2 (pixel kernel + colstats)", case_upconv(1, 16, 16, 32, 32, 12, dil=2, route=("fwd pixel", "bwd thread"))),
+    ("upconv fwd/bwd 2 x (16x16 -> 32x32) x 32 (x2: 4-column strips)", case_upconv(2, 16, 16, 32, 32, 32, route=("fwd strip4", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (5x7 -> 13x18) x 8 (W % 4 != 0: pixel kernel), addend", case_upconv(1, 5, 7, 13, 18, 8, addend_rows=234, route=("fwd pixel", "bwd thread"))),
+    ("upconv fwd/bwd 2 x (1x1 -> 4x4) x 4 (degenerate source)", case_upconv(2, 1, 1, 4, 4, 4, route=("fwd strip3", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (43x43 -> 128x128) x 8 (scale exactly 1/3: 4-column strips)", case_upconv(1, 43, 43, 128, 128, 8, route=("fwd strip4", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (85x85 -> 128x128) x 8 (scale 0.661: 4-column strips)", case_upconv(1, 85, 85, 128, 128, 8, route=("fwd pixel", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (86x86 -> 128x128) x 8 (scale 0.669: pixel kernel)", case_upconv(1, 86, 86, 128, 128, 8, route=("fwd pixel", "bwd thread"))),
+    ("upconv fwd/bwd 3 x (32x32 -> 128x128) x 256 (the decoder's shape)", case_upconv(3, 32, 32, 128, 128, 256, addend_rows=16384, route=("fwd tile", "bwd wave"))),
+    ("upconv fwd/bwd 2 x (4x4 -> 16x16) x 256 (tile kernel, one tile; wave-per-pixel bwd)", case_upconv(2, 4, 4, 16, 16, 256, addend_rows=256, route=("fwd tile", "bwd wave"))),
+    ("upconv fwd/bwd 1 x (5x9 -> 17x33) x 256 (exact ratio 1/4, odd sizes: strip / pixel fwd, wave bwd)", case_upconv(1, 5, 9, 17, 33, 256, route=("fwd pixel", "bwd wave"))),
+    ("upconv fwd/bwd 1 x (9x5 -> 32x16) x 256 (tile kernel, ratio 0.258 / 0.267), addend", case_upconv(1, 9, 5, 32, 16, 256, addend_rows=512, route=("fwd tile", "bwd wave"))),
+    ("upconv fwd/bwd 2 x (16x16 -> 48x64) x 256 (tile kernel at x3 / x4.2)", case_upconv(2, 16, 16, 48, 64, 256, route=("fwd tile", "bwd wave"))),
+    ("upconv fwd/bwd 1 x (83x83 -> 128x128) x 8 (3*sw = 1.937: the last width on 4-column strips, 84 is on the pixel kernel)",
+     case_upconv(1, 83, 83, 128, 128, 8, route=("fwd strip4", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (10x5 -> 16x16) x 32 (tile geometry, footprint 10 x 5 over the LDS bound: 3-column strips)",
+     case_upconv(1, 10, 5, 16, 16, 32, route=("fwd strip3", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (2x2 -> 16x16) x 256 (x15: 36 tap rows exceed the wave kernel's weight table, thread bwd)",
+     case_upconv(1, 2, 2, 16, 16, 256, route=("fwd tile", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (8x8 -> 16x16) x 256 (x2, the output-stride-8 geometry: 4-column strips, wave bwd)",
+     case_upconv(1, 8, 8, 16, 16, 256, route=("fwd strip4", "bwd wave"))),
     ("upconv identity vs interpolate+conv2d 2 x (8x8 -> 32x32), 64+16 -> 32", case_upconv_identity(2, 8, 8, 32, 32, 64, 16, 32)),
 ]
 

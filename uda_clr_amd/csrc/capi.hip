@@ -12,4 +12,4 @@ int uda_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* uda_last_error(void) { return g_err; }
-extern "C" int uda_version(void) { return 2; }
+extern "C" int uda_version(void) { return 3; }

@@ -17,9 +17,10 @@
 //                    deterministic, no float atomics)
 //
 // Both are bound by cache / HBM bandwidth (the strip kernel: 13.5 cached 16-byte reads per 16-byte output at x4).
-#include <algorithm>
+// Which of the kernels below a call runs, with which grid, is decided in upconv_plan.h and nowhere else.
 #include "common.h"
 #include "bilinear.h"
+#include "upconv_plan.h"
 
 __global__ __launch_bounds__(256) void upconv_fwd_kernel(const float* __restrict__ g, int64_t ldg, int N, int h, int w, int C,
                                                          int dil, const float* __restrict__ addend, int64_t ld_add,
@@ -197,9 +198,7 @@ __global__ __launch_bounds__(256) void upconv_fwd_strip_kernel(const float* __re
 //         V[tw][c] = sum_th lh0(th) * g_{th,tw}[h0(th)][a + c] + lh1(th) * g_{th,tw}[h1(th)][a + c],   y[j] += cw[tw][j][c] * V[tw][c]
 //     (90 instead of 162 four-channel multiply-adds per strip), on packed pairs (v_pk_fma_f32).
 //   Same sums as the strip kernel in another association: results agree to fp32 rounding, not bit for bit.
-#define UPT_TH 16
-#define UPT_TW 16
-#define UPT_CS 32            // channels per workgroup (8 granules of 4)
+//   (UPT_TH x UPT_TW, UPT_CS: upconv_plan.h)
 __global__ __launch_bounds__(256) void upconv_fwd_tile_kernel(const float* __restrict__ g, int64_t ldg, int N, int h, int w, int C,
                                                               const float* __restrict__ addend, int64_t ld_add, int64_t add_rows,
                                                               float* __restrict__ y, int64_t ldy, int H, int W, float sh, float sw,
@@ -364,77 +363,41 @@ __global__ __launch_bounds__(256) void upconv_fwd_tile_kernel(const float* __res
     }
 }
 
-// rows (columns) of the low-resolution footprint of a tile whose tap positions span [o_min, o_max] (clipped to the image)
-static int upconv_foot(int o_min, int o_max, float scale, int n_in, int n_out) {
-    const float lo = scale * (float)(o_min < 0 ? 0 : o_min), hi = scale * (float)(o_max > n_out - 1 ? n_out - 1 : o_max);
-    int i_lo = (int)lo, i_hi = (int)hi;
-    if (i_lo > n_in - 1) i_lo = n_in - 1;
-    if (i_hi > n_in - 1) i_hi = n_in - 1;
-    i_hi += i_hi < n_in - 1 ? 1 : 0;
-    return i_hi - i_lo + 1;
-}
-
-static bool upconv_strip_ok(int w, int W, int C, int dil, int H = 4) {
-    if (H % 4) return false;
-    // the four tap positions of a strip span 3*sw low-resolution columns: floor(frac + 3*sw) + 1 <= NC - 1 with NC <= 4
-    // (margins of 2 %: the column indices come from fp32 products scale * x, whose rounding must not push a strip over its last cached column)
-    return W % 4 == 0 && dil == 1 && C % 4 == 0 && 3.f * bil_scale(w, W) < 1.96f && 256 % (C / 4) == 0;       // (+ H % 4 == 0, checked by the caller)
-}
-
-extern "C" int uda_upconv_fused_stats(int h, int w, int H, int W, int C, int dil) {
-    (void)h; (void)H;
-    return upconv_strip_ok(w, W, C, dil, H) ? 1 : 0;
-}
-
+// y = addend + the interpolated taps of g, by the kernel upconv_plan chooses.  stats (or null): the tile and strip kernels add y's
+// per-channel sums to it themselves; after the pixel kernel uda_colstats over y follows on the same stream - also beyond the strip
+// kernels' 32-bit extents (N * h * w * ldg * 4 >= 2^31: 228 images of 32 x 32 x 2304), where this entry once refused a call with stats.
 extern "C" int uda_upconv_fwd(const float* g, int64_t ldg, int N, int h, int w, int C, int dil, const float* addend,
                               int64_t ld_add, int64_t addend_rows, float* y, int64_t ldy, int H, int W, double* stats,
                               void* stream) {
-    UDA_REQUIRE(g && y && uda_aligned16(g) && uda_aligned16(y) && C > 0 && C % 4 == 0 && ldg % 4 == 0 && ldy % 4 == 0 &&
-                    ldg >= 9 * (int64_t)C && ldy >= C, "uda_upconv_fwd: g must be [N*h*w, >= 9*C], C and lds multiples of 4, 16-byte aligned");
-    UDA_REQUIRE(N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && dil >= 1, "uda_upconv_fwd: bad geometry");
-    UDA_REQUIRE(!addend || (uda_aligned16(addend) && ld_add % 4 == 0 && ld_add >= C && addend_rows > 0 &&
-                            ((int64_t)N * H * W) % addend_rows == 0),
-                "uda_upconv_fwd: addend must be [addend_rows, >= C] with addend_rows dividing N*H*W");
+    UDA_REQUIRE(g && y && uda_aligned16(g) && uda_aligned16(y) && (!addend || uda_aligned16(addend)) && ldy % 4 == 0 && ldy >= C,
+                "uda_upconv_fwd: g, y and addend must be 16-byte aligned, y [N*H*W, >= C] with a row stride that is a multiple of 4");
+    const UpconvPlan p = upconv_plan(UP_FWD, N, h, w, H, W, C, dil, ldg, addend != nullptr, ld_add, addend_rows, stats != nullptr);
+    UDA_REQUIRE(!p.error, "uda_upconv_fwd: %s", p.error);
     hipStream_t st = (hipStream_t)stream;
-    const float sh = bil_scale(h, H), sw = bil_scale(w, W);
-    const int G = C / 4;
-    const int64_t lim32 = (int64_t)1 << 31;          // the strip kernel indexes in 32 bits
-    if (upconv_strip_ok(w, W, C, dil, H) && (int64_t)N * H * W < lim32 && (int64_t)N * H * (W / 4) * G < lim32 - 65536 * 256 &&
-        (int64_t)N * h * w * ldg * 4 < lim32 && (!addend || addend_rows * ld_add < lim32 * 4)) {
-        // the LDS-tiled kernel where the tiling fits (x4-like upsampling of a map whose sides are multiples of 16)
-        if (3.f * sw < 0.98f && H % UPT_TH == 0 && W % UPT_TW == 0 && C % UPT_CS == 0) {
-            int R = 1, RC = 1;
-            for (int ty = 0; ty < H / UPT_TH; ++ty) R = std::max(R, upconv_foot(ty * UPT_TH - 1, ty * UPT_TH + UPT_TH, sh, h, H));
-            for (int tx = 0; tx < W / UPT_TW; ++tx) RC = std::max(RC, upconv_foot(tx * UPT_TW - 1, tx * UPT_TW + UPT_TW, sw, w, W));
-            const size_t lds = (size_t)R * RC * 72 * sizeof(float4);
-            const int64_t nwg = (int64_t)N * (H / UPT_TH) * (W / UPT_TW) * (C / UPT_CS);
-            if (lds <= 64 * 1024 - 8192 && nwg < lim32) {
-                hipLaunchKernelGGL(upconv_fwd_tile_kernel, dim3((unsigned)nwg), dim3(256), lds, st, g, ldg, N, h, w, C, addend, ld_add,
-                                   addend ? addend_rows : 1, y, ldy, H, W, sh, sw, stats, R, RC);
-                UDA_LAUNCH_CHECK("upconv_fwd_tile");
-                return 0;
-            }
-        }
-        const int64_t total = (int64_t)N * H * (W / 4) * G;
-        int grid = uda_cdiv(total, 256);
-        if (grid > 4096) grid = 4096;           // bounded: the statistics epilogue issues 2*C atomics per workgroup
-        if (3.f * sw < 0.98f)
-            hipLaunchKernelGGL(upconv_fwd_strip_kernel<3>, dim3(grid), dim3(256), 0, st, g, ldg, N, h, w, C, dil, addend, ld_add,
-                               addend ? addend_rows : 1, y, ldy, H, W, sh, sw, stats);
-        else
-            hipLaunchKernelGGL(upconv_fwd_strip_kernel<4>, dim3(grid), dim3(256), 0, st, g, ldg, N, h, w, C, dil, addend, ld_add,
-                               addend ? addend_rows : 1, y, ldy, H, W, sh, sw, stats);
+    const int64_t arows = addend ? addend_rows : 1;
+    double* fused = p.fused_stats ? stats : nullptr;
+    switch (p.kernel) {
+    case UPK_TILE:
+        hipLaunchKernelGGL(upconv_fwd_tile_kernel, dim3(p.grid), dim3(256), p.lds, st, g, ldg, N, h, w, C, addend, ld_add, arows, y, ldy, H, W,
+                           p.sh, p.sw, fused, p.R, p.RC);
+        UDA_LAUNCH_CHECK("upconv_fwd_tile");
+        break;
+    case UPK_STRIP3:
+        hipLaunchKernelGGL(upconv_fwd_strip_kernel<3>, dim3(p.grid), dim3(256), 0, st, g, ldg, N, h, w, C, dil, addend, ld_add, arows, y, ldy,
+                           H, W, p.sh, p.sw, fused);
         UDA_LAUNCH_CHECK("upconv_fwd_strip");
-        return 0;
+        break;
+    case UPK_STRIP4:
+        hipLaunchKernelGGL(upconv_fwd_strip_kernel<4>, dim3(p.grid), dim3(256), 0, st, g, ldg, N, h, w, C, dil, addend, ld_add, arows, y, ldy,
+                           H, W, p.sh, p.sw, fused);
+        UDA_LAUNCH_CHECK("upconv_fwd_strip");
+        break;
+    default:        // UPK_PIXEL
+        hipLaunchKernelGGL(upconv_fwd_kernel, dim3(p.grid), dim3(256), 0, st, g, ldg, N, h, w, C, dil, addend, ld_add, arows, y, ldy, H, W,
+                           p.sh, p.sw);
+        UDA_LAUNCH_CHECK("upconv_fwd");
     }
-    UDA_REQUIRE(!stats, "uda_upconv_fwd: the fused statistics need W %% 4 == 0, dil == 1, an upsampling factor >= 1.5 and C/4 dividing 256; "
-                        "accumulate them with uda_colstats instead");
-    const int64_t total = (int64_t)N * H * W * G;
-    int grid = uda_cdiv(total, 256);
-    if (grid > 65536) grid = 65536;
-    hipLaunchKernelGGL(upconv_fwd_kernel, dim3(grid), dim3(256), 0, st, g, ldg, N, h, w, C, dil, addend, ld_add,
-                       addend ? addend_rows : 1, y, ldy, H, W, sh, sw);
-    UDA_LAUNCH_CHECK("upconv_fwd");
+    if (stats && !p.fused_stats) return uda_colstats(y, ldy, (int64_t)N * H * W, C, 2, stats, stream);
     return 0;
 }
 
@@ -559,24 +522,35 @@ __global__ __launch_bounds__(256) void upconv_bwd_wave_kernel(const float* __res
 
 extern "C" int uda_upconv_bwd(const float* dy, int64_t ldy, int N, int H, int W, int C, int dil, float* dg, int64_t ldg, int h,
                               int w, void* stream) {
-    UDA_REQUIRE(dy && dg && uda_aligned16(dy) && uda_aligned16(dg) && C > 0 && C % 4 == 0 && ldg % 4 == 0 && ldy % 4 == 0 &&
-                    ldg >= 9 * (int64_t)C && ldy >= C, "uda_upconv_bwd: dg must be [N*h*w, >= 9*C], C and lds multiples of 4, 16-byte aligned");
-    UDA_REQUIRE(N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && dil >= 1, "uda_upconv_bwd: bad geometry");
-    const int64_t total = (int64_t)N * h * w * (C / 4);
-    int grid = uda_cdiv(total, 256);
-    if (grid > 65536) grid = 65536;
-    const float sh = bil_scale(h, H), sw = bil_scale(w, W);
-    // one wave per low-resolution pixel when its 64 lanes are exactly the channel granules and the tap ranges fit the 32-entry weight tables
-    if (C == 256 && dil == 1 && sh > 0.f && sw > 0.f && 2.f / sh + 6.f <= 32.f && 2.f / sw + 6.f <= 32.f && (int64_t)N * h * w < ((int64_t)1 << 31)) {
-        const int64_t npix = (int64_t)N * h * w;
-        int gw = (int)uda_cdiv(npix, 4);
-        if (gw > 65536) gw = 65536;
-        hipLaunchKernelGGL(upconv_bwd_wave_kernel, dim3(gw), dim3(256), 0, (hipStream_t)stream, dy, ldy, N, H, W, C, dg, ldg, h, w, sh, sw);
+    UDA_REQUIRE(dy && dg && uda_aligned16(dy) && uda_aligned16(dg) && ldy % 4 == 0 && ldy >= C,
+                "uda_upconv_bwd: dy and dg must be 16-byte aligned, dy [N*H*W, >= C] with a row stride that is a multiple of 4");
+    const UpconvPlan p = upconv_plan(UP_BWD, N, h, w, H, W, C, dil, ldg, false, 0, 0, false);
+    UDA_REQUIRE(!p.error, "uda_upconv_bwd: %s", p.error);
+    hipStream_t st = (hipStream_t)stream;
+    if (p.kernel == UPK_WAVE) {
+        hipLaunchKernelGGL(upconv_bwd_wave_kernel, dim3(p.grid), dim3(256), 0, st, dy, ldy, N, H, W, C, dg, ldg, h, w, p.sh, p.sw);
         UDA_LAUNCH_CHECK("upconv_bwd_wave");
-        return 0;
+    } else {
+        hipLaunchKernelGGL(upconv_bwd_kernel, dim3(p.grid), dim3(256), 0, st, dy, ldy, N, H, W, C, dil, dg, ldg, h, w, p.sh, p.sw);
+        UDA_LAUNCH_CHECK("upconv_bwd");
     }
-    hipLaunchKernelGGL(upconv_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, ldy, N, H, W, C, dil, dg, ldg, h, w,
-                       sh, sw);
-    UDA_LAUNCH_CHECK("upconv_bwd");
     return 0;
 }
+
+// ---- routes: the plan as a short stable text, for tests and tools
+/* "fwd tile grid 768 R 6 RC 6 lds 41472", "fwd strip3 grid 32", "fwd strip4 ...", "fwd pixel ...", "bwd wave grid 768", "bwd thread ...";
+ * a forward route with want_stats ends in " stats fused" (the kernel accumulates them) or " stats colstats" (uda_colstats follows);
+ * "none" for refused arguments.  Returns the text's length (as snprintf), -1 without a buffer. */
+extern "C" int uda_upconv_route(int op, int N, int h, int w, int H, int W, int C, int dil, int64_t ldg, int has_addend, int64_t ld_add,
+                                int64_t addend_rows, int want_stats, char* buf, int len) {
+    static const char* const NAME[] = {"none", "fwd tile", "fwd strip3", "fwd strip4", "fwd pixel", "bwd wave", "bwd thread"};
+    if (!buf || len < 1) return -1;
+    const UpconvPlan p = upconv_plan(op, N, h, w, H, W, C, dil, ldg, has_addend != 0, ld_add, addend_rows, want_stats != 0);
+    if (p.error) return snprintf(buf, len, "none");
+    const char* stats = op != UP_FWD || !want_stats ? "" : p.fused_stats ? " stats fused" : " stats colstats";
+    if (p.kernel == UPK_TILE) return snprintf(buf, len, "%s grid %u R %d RC %d lds %zu%s", NAME[p.kernel], p.grid, p.R, p.RC, p.lds, stats);
+    return snprintf(buf, len, "%s grid %u%s", NAME[p.kernel], p.grid, stats);
+}
+
+/* every "<op> <kernel>" uda_upconv_route can begin with, one per line */
+extern "C" const char* uda_upconv_route_list(void) { return "fwd tile\nfwd strip3\nfwd strip4\nfwd pixel\nbwd wave\nbwd thread"; }

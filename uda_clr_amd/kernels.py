@@ -131,9 +131,10 @@ SYMBOLS = {
     "uda_adv_loss_bwd": (_I, [_P, _I, _P, _I, _F, _F, _P, _P, _P, _P]),
     "uda_adv_s2d_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P]),
     "uda_adv_s2d_bwd": (_I, [_P, _L, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "uda_upconv_fused_stats": (_I, [_I, _I, _I, _I, _I, _I]),
     "uda_upconv_fwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _I, _P, _P]),
     "uda_upconv_bwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P]),
+    "uda_upconv_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _L, _I, _L, _L, _I, C.c_char_p, _I]),
+    "uda_upconv_route_list": (C.c_char_p, []),
     "uda_postprocess_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_postprocess": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _U, _P]),
     "uda_surface_distance_workspace_bytes": (_U, [_I, _I, _I]),
@@ -164,8 +165,9 @@ def load_library(path: Optional[str] = None):
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)          # AttributeError -> symbol missing
         fn.restype, fn.argtypes = res, args
-    if lib.uda_version() < 2:            # version 1 has no `family` argument in uda_dwconv_*: it would read the stream there
-        raise RuntimeError("%s is ABI version %d, these bindings need 2 - rebuild it" % (path, lib.uda_version()))
+    if lib.uda_version() < 3:            # version 1 has no `family` argument in uda_dwconv_*: it would read the stream there;
+        #                                  version 2 refuses uda_upconv_fwd with stats where the kernel does not accumulate them
+        raise RuntimeError("%s is ABI version %d, these bindings need 3 - rebuild it" % (path, lib.uda_version()))
     _lib = lib
     return lib
 
@@ -176,6 +178,7 @@ class UdaError(RuntimeError):
 
 _DW_FAMILY = {"": 0, "flat": 1, "tiled": 2, "cb": 3}      # UDA_DW_AUTO, _FLAT, _TILED, _CB
 _DW_OP = {"fwd": 0, "dgrad": 1, "wgrad": 2}                # UDA_DW_FWD, _DGRAD, _WGRAD
+_UP_OP = {"fwd": 0, "bwd": 1}                              # uda_upconv_route's op
 
 
 def _family(family: str) -> int:
@@ -904,7 +907,7 @@ class HipKernels:
     def upconv_fwd(self, g, N, h, w, out, H, W, addend=None, dil=1, stats=None):
         """out[p] = addend[p % addend.rows] + sum over the 9 taps of the bilinear (align_corners) read of g's tap plane at the tap
         position; g: [N*h*w, 9*C] (tap-major columns), out: [N*H*W, C]; stats ([SLOTS, 2, C] fp64, added into): column sums
-        and sums of squares of out (fused into the kernel where the geometry allows, a colstats pass otherwise)."""
+        and sums of squares of out (by the kernel or by a colstats launch after it, as the library's launch plan says)."""
         self._dev(g)
         Cc = out.shape[1]
         assert g.shape == (N * h * w, 9 * Cc) and out.shape[0] == N * H * W
@@ -913,12 +916,8 @@ class HipKernels:
         ad, lda, rows = (None, 0, 1) if addend is None else (_mat(addend, "addend") + (addend.shape[0],))
         if addend is not None:
             assert addend.shape[1] == Cc and (N * H * W) % addend.shape[0] == 0
-        fused = stats is not None and bool(self.lib.uda_upconv_fused_stats(h, w, H, W, Cc, dil))
         self._ck_stats(stats, Cc)
-        self._ck(self.lib.uda_upconv_fwd(gp, ldg, N, h, w, Cc, dil, ad, lda, rows, o, ldo, H, W, _ptr(stats) if fused else None,
-                                         self._stream()))
-        if stats is not None and not fused:
-            self.colstats(out, stats)
+        self._ck(self.lib.uda_upconv_fwd(gp, ldg, N, h, w, Cc, dil, ad, lda, rows, o, ldo, H, W, _ptr(stats), self._stream()))
 
     def upconv_bwd(self, dy, N, H, W, dg, h, w, dil=1):
         self._dev(dy)
@@ -927,6 +926,15 @@ class HipKernels:
         d, ldy = _mat(dy, "dy")
         gp, ldg = _mat(dg, "dg")
         self._ck(self.lib.uda_upconv_bwd(d, ldy, N, H, W, Cc, dil, gp, ldg, h, w, self._stream()))
+
+    def upconv_route(self, op, N, h, w, H, W, Cc, dil=1, ldg=None, ld_add=None, addend_rows=0, stats=False) -> str:
+        """The launch the library plans for ``upconv_fwd`` (op "fwd") / ``upconv_bwd`` (op "bwd"): "<op> <kernel> grid ...", for a
+        forward with statistics ending in "stats fused" or "stats colstats"; "none" for arguments the entry refuses
+        (uda_upconv_route).  ldg: row stride of g / dg (default 9 * Cc); ld_add: row stride of the addend, None without one."""
+        buf = C.create_string_buffer(96)
+        self.lib.uda_upconv_route(_UP_OP[op], N, h, w, H, W, Cc, dil, 9 * Cc if ldg is None else ldg, int(ld_add is not None),
+                                  ld_add or 0, addend_rows, int(stats), buf, len(buf))
+        return buf.value.decode()
 
     def head_upsample_fwd(self, x, N, h, w, out):
         self._dev(x)
