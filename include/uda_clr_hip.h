@@ -428,6 +428,27 @@ size_t uda_postprocess_workspace_bytes(int B, int H, int W);
 int uda_postprocess(const float* pred, int B, int H, int W, float thr_cup, float thr_disc, int sweeps, uint8_t* out,
                     int* not_converged, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- prediction pictures (utils/Utils.py:515-585, save_per_img): the display mask per structure, the contour overlay and the
+ * byte image it is painted on.  Channel 0 = cup, 1 = disc.
+ * uda_display_masks: prob f32 [B,2,H,W] (read-only) -> out uint8 [B,2,H,W] in {0,1}: the outermost row / column ring read as 0 ->
+ *   > thr (both channels) -> the chain of uda_postprocess (5 medians, erosion, largest component, fill) -> dilation by the L1
+ *   ball of radius 7 (outside = unset) -> holes filled once more.  The reference's second largest-component step changes nothing
+ *   (a diamond dilation of one 8-connected set is 8-connected) and is not run.  sweeps and not_converged as uda_postprocess, with
+ *   DEVICE int[3]: components, first flood, second flood.  Limits and workspace rule as uda_postprocess.
+ * uda_overlay_u8: image, out uint8 [B,H,W,3] (out may not alias image), masks uint8 [B,2,H,W] (nonzero = set).  The vertices of
+ *   find_contours(mask, 0.5) on a binary mask are the midpoints of all 4-adjacent in-image pixel pairs that differ; each paints
+ *   the seven pixels (int(y + dy), int(x + dx)), (dy, dx) in (0,0) (1,0) (1,1) (0,1) (-1,0) (-1,-1) (0,-1).  Channel 1's outline is
+ *   (0, 255, 0), channel 0's (0, 0, 255) on top of it; every other pixel is the image's.  A target whose row or column lies outside
+ *   the image is dropped (the reference raises at H / W and wraps at -1).  Computed as a gather, one thread per output pixel:
+ *   every byte of out is written once, bit-identical from run to run and for an image alone or inside any batch.
+ * uda_image_u8: x f32 [B,3,H,W] in [-1, 1] -> out uint8 [B,H,W,3] = clip(rint((x + 1) * 127.5), 0, 255), fp32, no fma.
+ * H, W >= 1, H * W < 2^30; a null pointer, a bad size or a short workspace returns the error before any launch. */
+size_t uda_display_masks_workspace_bytes(int B, int H, int W);
+int uda_display_masks(const float* prob, int B, int H, int W, float thr, int sweeps, uint8_t* out, int* not_converged,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int uda_overlay_u8(const uint8_t* image, const uint8_t* masks, int B, int H, int W, uint8_t* out, void* stream);
+int uda_image_u8(const float* x, int B, int H, int W, uint8_t* out, void* stream);
+
 /* ---- exact surface distances of one (prediction, ground truth) mask pair per image and class: what the per-image ASD /
  * ASSD / Hausdorff figures of an evaluation are closed forms of.  The reference keeps the 1-D scan of a squared distance
  * transform (utils/metrics.py:62-68, `_upscan`) without its callers; the masks are those of utils/Utils.py:438-463.

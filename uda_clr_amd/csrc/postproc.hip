@@ -14,6 +14,10 @@
 //   whole tiles, not single pixels) for a bounded number of launches; the last launch reports whether anything still changed,
 //   and the entry point returns that count in *not_converged (device int) so a caller can ask for more sweeps.
 //
+//   uda_display_masks   utils/Utils.py:515-553 of the reference (the display mask of save_per_img): the border ring read as 0, one
+//       threshold, the chain above, then binary_dilation(diamond(7)) with the outside unset and the holes filled once more
+//       (why the reference's second largest-component step is left out and the second fill is not).
+//
 // Latency-bound byte work on small planes (validation only, not on the training path).
 #include "common.h"
 
@@ -25,6 +29,18 @@ __global__ __launch_bounds__(256) void pp_threshold_kernel(const float* __restri
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
     mask[plane * HW + p] = pred[plane * HW + p] > ((plane & 1) ? thr_disc : thr_cup) ? 1 : 0;
+}
+
+// the same comparison with the outermost row / column ring of the plane read as 0 (the display chain, utils/Utils.py:525-537
+// zeroes that ring in the caller's array; here the input stays read-only)
+__global__ __launch_bounds__(256) void pp_threshold_ring_kernel(const float* __restrict__ pred, int H, int W, float thr,
+                                                                uint8_t* __restrict__ mask) {
+    const int plane = blockIdx.y;
+    const int64_t HW = (int64_t)H * W, p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const int h = (int)(p / W), w = (int)(p % W);
+    const bool ring = h == 0 || w == 0 || h == H - 1 || w == W - 1;
+    mask[plane * HW + p] = (!ring && pred[plane * HW + p] > thr) ? 1 : 0;
 }
 
 // window sum over (2R+1)^2 with zeros outside the image; out = sum >= need
@@ -51,16 +67,19 @@ __global__ __launch_bounds__(256) void pp_median7_kernel(const uint8_t* __restri
     }
 }
 
-// erosion by the L1 ball of radius R, pixels outside the image count as set
+// erosion by the L1 ball of radius R, pixels outside the image count as set.  FLIP = 1 reads and writes the complement: the
+// dilation by the same ball with everything outside the image unset (dilate(M) = ~erode(~M), and "outside set" for ~M is
+// "outside unset" for M).
 #define PP_ER 7
-__global__ __launch_bounds__(256) void pp_erode_kernel(const uint8_t* __restrict__ in, int H, int W, uint8_t* __restrict__ out) {
+template <int FLIP>
+__device__ __forceinline__ void pp_erode_tile(const uint8_t* __restrict__ in, int H, int W, uint8_t* __restrict__ out) {
     __shared__ uint8_t t[PP_T + 2 * PP_ER][PP_T + 2 * PP_ER + 2];
     const int plane = blockIdx.z, h0 = blockIdx.y * PP_T, w0 = blockIdx.x * PP_T;
     const uint8_t* I = in + (int64_t)plane * H * W;
     for (int e = threadIdx.x; e < (PP_T + 2 * PP_ER) * (PP_T + 2 * PP_ER); e += 256) {
         const int r = e / (PP_T + 2 * PP_ER), c = e % (PP_T + 2 * PP_ER);
         const int h = h0 + r - PP_ER, w = w0 + c - PP_ER;
-        t[r][c] = (h >= 0 && h < H && w >= 0 && w < W) ? I[(int64_t)h * W + w] : 1;
+        t[r][c] = (h >= 0 && h < H && w >= 0 && w < W) ? (I[(int64_t)h * W + w] ^ FLIP) : 1;
     }
     __syncthreads();
     for (int e = threadIdx.x; e < PP_T * PP_T; e += 256) {
@@ -72,8 +91,17 @@ __global__ __launch_bounds__(256) void pp_erode_kernel(const uint8_t* __restrict
             const int span = PP_ER - (dy < 0 ? -dy : dy);
             for (int dx = -span; dx <= span; ++dx) all &= t[r + PP_ER + dy][c + PP_ER + dx];
         }
-        out[((int64_t)plane * H + h) * W + w] = all;
+        out[((int64_t)plane * H + h) * W + w] = all ^ FLIP;
     }
+}
+
+__global__ __launch_bounds__(256) void pp_erode_kernel(const uint8_t* __restrict__ in, int H, int W, uint8_t* __restrict__ out) {
+    pp_erode_tile<0>(in, H, W, out);
+}
+
+// in, out in {0,1}
+__global__ __launch_bounds__(256) void pp_dilate_kernel(const uint8_t* __restrict__ in, int H, int W, uint8_t* __restrict__ out) {
+    pp_erode_tile<1>(in, H, W, out);
 }
 
 __global__ __launch_bounds__(256) void pp_label_init_kernel(const uint8_t* __restrict__ mask, int64_t HW, int* __restrict__ lab) {
@@ -168,6 +196,11 @@ __global__ __launch_bounds__(1024) void pp_argmax_kernel(const int* __restrict__
     if (threadIdx.x == 0) best[plane] = red[0] == 0 ? 0 : (int)(0xffffffffu - (unsigned)(red[0] & 0xffffffffll)) + 1;
 }
 
+// flood labels: 1 = reached from the border, 2 = background not (yet) reached, 0 = foreground (does not propagate)
+__device__ __forceinline__ int pp_flood_seed(bool fg, int h, int w, int H, int W) {
+    return fg ? 0 : ((h == 0 || w == 0 || h == H - 1 || w == W - 1) ? 1 : 2);
+}
+
 // keep the largest component; start the border flood of its complement: reach = 1 on background pixels of the image border
 __global__ __launch_bounds__(256) void pp_keep_kernel(const int* __restrict__ lab, const int* __restrict__ best, int H, int W,
                                                       uint8_t* __restrict__ keep, int* __restrict__ reach) {
@@ -178,8 +211,15 @@ __global__ __launch_bounds__(256) void pp_keep_kernel(const int* __restrict__ la
     const uint8_t k = (b > 0 && lab[plane * HW + p] == b) ? 1 : 0;
     keep[plane * HW + p] = k;
     const int h = (int)(p / W), w = (int)(p % W);
-    // flood labels: 1 = reached from the border, 2 = background not (yet) reached, 0 = foreground (does not propagate)
-    reach[plane * HW + p] = k ? 0 : ((h == 0 || w == 0 || h == H - 1 || w == W - 1) ? 1 : 2);
+    reach[plane * HW + p] = pp_flood_seed(k, h, w, H, W);
+}
+
+// start the border flood of the complement of a mask that is kept whole
+__global__ __launch_bounds__(256) void pp_flood_init_kernel(const uint8_t* __restrict__ mask, int H, int W, int* __restrict__ reach) {
+    const int plane = blockIdx.y;
+    const int64_t HW = (int64_t)H * W, p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    reach[plane * HW + p] = pp_flood_seed(mask[plane * HW + p] != 0, (int)(p / W), (int)(p % W), H, W);
 }
 
 __global__ __launch_bounds__(256) void pp_fill_kernel(const uint8_t* __restrict__ keep, const int* __restrict__ reach, int64_t HW,
@@ -195,12 +235,11 @@ extern "C" size_t uda_postprocess_workspace_bytes(int B, int H, int W) {
     return planes * HW * (2 * sizeof(uint8_t) + 3 * sizeof(int)) + planes * sizeof(int) + 256;
 }
 
-extern "C" int uda_postprocess(const float* pred, int B, int H, int W, float thr_cup, float thr_disc, int sweeps,
-                               uint8_t* out, int* not_converged, void* workspace, size_t workspace_bytes, void* stream) {
-    UDA_REQUIRE(pred && out && not_converged && workspace && B > 0 && H > 0 && W > 0 && sweeps >= 1, "uda_postprocess: bad args");
-    UDA_REQUIRE((int64_t)H * W < ((int64_t)1 << 30), "uda_postprocess: plane too large for 32-bit labels");
-    UDA_REQUIRE(workspace_bytes >= uda_postprocess_workspace_bytes(B, H, W), "uda_postprocess: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
+// The chain both entries share, from the thresholded planes to the filled largest component.  display = false: exactly
+// uda_postprocess (per-channel thresholds, the filled mask is the result).  display = true: the border ring is read as 0, one
+// threshold, and the filled mask goes on through the dilation and a second fill (uda_display_masks).
+static int pp_run(const char* who, bool display, const float* pred, int B, int H, int W, float thr_cup, float thr_disc, int sweeps,
+                  uint8_t* out, int* not_converged, void* workspace, hipStream_t st) {
     const int planes = 2 * B;
     const int64_t HW = (int64_t)H * W;
     // workspace: labA, labB, cnt (int planes), best (int per plane), mA, mB (byte planes)
@@ -211,7 +250,8 @@ extern "C" int uda_postprocess(const float* pred, int B, int H, int W, float thr
     uint8_t* mA = (uint8_t*)(best + planes + 16);
     uint8_t* mB = mA + planes * HW;
     const dim3 flat(uda_cdiv(HW, 256), planes), tiles(uda_cdiv(W, PP_T), uda_cdiv(H, PP_T), planes);
-    hipLaunchKernelGGL(pp_threshold_kernel, flat, dim3(256), 0, st, pred, HW, thr_cup, thr_disc, mA);
+    if (display) hipLaunchKernelGGL(pp_threshold_ring_kernel, flat, dim3(256), 0, st, pred, H, W, thr_cup, mA);
+    else hipLaunchKernelGGL(pp_threshold_kernel, flat, dim3(256), 0, st, pred, HW, thr_cup, thr_disc, mA);
     for (int i = 0; i < 5; ++i) {
         hipLaunchKernelGGL(pp_median7_kernel, tiles, dim3(256), 0, st, mA, H, W, mB);
         uint8_t* t = mA; mA = mB; mB = t;
@@ -219,13 +259,13 @@ extern "C" int uda_postprocess(const float* pred, int B, int H, int W, float thr
     hipLaunchKernelGGL(pp_erode_kernel, tiles, dim3(256), 0, st, mA, H, W, mB);          // eroded mask in mB
     hipLaunchKernelGGL(pp_label_init_kernel, flat, dim3(256), 0, st, mB, HW, labA);
     UDA_LAUNCH_CHECK("postprocess (masks)");
-    if (hipMemsetAsync(not_converged, 0, 2 * sizeof(int), st) != hipSuccess) return uda_set_error("uda_postprocess: memset failed");
+    if (hipMemsetAsync(not_converged, 0, (display ? 3 : 2) * sizeof(int), st) != hipSuccess) return uda_set_error("%s: memset failed", who);
     int* scratch_flag = best + planes;             // absorbs the flags of all but the last sweep
     for (int i = 0; i <= sweeps; ++i) {            // the extra sweep only reports: anything it still changes = not converged
         hipLaunchKernelGGL(pp_propagate_kernel<1>, tiles, dim3(256), 0, st, labA, H, W, labB, i == sweeps ? not_converged : scratch_flag);
         int* t = labA; labA = labB; labB = t;
     }
-    if (hipMemsetAsync(cnt, 0, planes * HW * sizeof(int), st) != hipSuccess) return uda_set_error("uda_postprocess: memset failed");
+    if (hipMemsetAsync(cnt, 0, planes * HW * sizeof(int), st) != hipSuccess) return uda_set_error("%s: memset failed", who);
     hipLaunchKernelGGL(pp_area_kernel, flat, dim3(256), 0, st, labA, HW, cnt);
     hipLaunchKernelGGL(pp_argmax_kernel, dim3(planes), dim3(1024), 0, st, cnt, HW, best);
     hipLaunchKernelGGL(pp_keep_kernel, flat, dim3(256), 0, st, labA, best, H, W, mA, labB);   // keep mask in mA, flood labels in labB
@@ -236,7 +276,39 @@ extern "C" int uda_postprocess(const float* pred, int B, int H, int W, float thr
         hipLaunchKernelGGL(pp_propagate_kernel<0>, tiles, dim3(256), 0, st, fa, H, W, fb, i == sweeps ? not_converged + 1 : scratch_flag);
         int* t = fa; fa = fb; fb = t;
     }
-    hipLaunchKernelGGL(pp_fill_kernel, flat, dim3(256), 0, st, mA, fa, HW, out);
+    hipLaunchKernelGGL(pp_fill_kernel, flat, dim3(256), 0, st, mA, fa, HW, display ? mB : out);
     UDA_LAUNCH_CHECK("postprocess (fill)");
+    if (!display) return 0;
+    hipLaunchKernelGGL(pp_dilate_kernel, tiles, dim3(256), 0, st, mB, H, W, mA);          // dilated mask in mA
+    // utils/Utils.py:552 takes the largest component once more here.  That changes nothing and is left out: mB holds one
+    // 8-connected set (or none), the diamond contains the 3x3 cross, so two dilated 8-neighbours' diamonds overlap and the
+    // dilation is 8-connected again; an empty plane stays empty.  The second fill is needed: the dilation can close a gap
+    // that leaked the first one.
+    hipLaunchKernelGGL(pp_flood_init_kernel, flat, dim3(256), 0, st, mA, H, W, fa);
+    for (int i = 0; i <= sweeps; ++i) {
+        hipLaunchKernelGGL(pp_propagate_kernel<0>, tiles, dim3(256), 0, st, fa, H, W, fb, i == sweeps ? not_converged + 2 : scratch_flag);
+        int* t = fa; fa = fb; fb = t;
+    }
+    hipLaunchKernelGGL(pp_fill_kernel, flat, dim3(256), 0, st, mA, fa, HW, out);
+    UDA_LAUNCH_CHECK("display masks (dilation, fill)");
     return 0;
+}
+
+extern "C" int uda_postprocess(const float* pred, int B, int H, int W, float thr_cup, float thr_disc, int sweeps,
+                               uint8_t* out, int* not_converged, void* workspace, size_t workspace_bytes, void* stream) {
+    UDA_REQUIRE(pred && out && not_converged && workspace && B > 0 && H > 0 && W > 0 && sweeps >= 1, "uda_postprocess: bad args");
+    UDA_REQUIRE((int64_t)H * W < ((int64_t)1 << 30), "uda_postprocess: plane too large for 32-bit labels");
+    UDA_REQUIRE(workspace_bytes >= uda_postprocess_workspace_bytes(B, H, W), "uda_postprocess: workspace too small");
+    return pp_run("uda_postprocess", false, pred, B, H, W, thr_cup, thr_disc, sweeps, out, not_converged, workspace, (hipStream_t)stream);
+}
+
+// utils/Utils.py:515-553: the display mask of save_per_img (include/uda_clr_hip.h)
+extern "C" size_t uda_display_masks_workspace_bytes(int B, int H, int W) { return uda_postprocess_workspace_bytes(B, H, W); }
+
+extern "C" int uda_display_masks(const float* prob, int B, int H, int W, float thr, int sweeps, uint8_t* out, int* not_converged,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    UDA_REQUIRE(prob && out && not_converged && workspace && B > 0 && H > 0 && W > 0 && sweeps >= 1, "uda_display_masks: bad args");
+    UDA_REQUIRE((int64_t)H * W < ((int64_t)1 << 30), "uda_display_masks: plane too large for 32-bit labels");
+    UDA_REQUIRE(workspace_bytes >= uda_display_masks_workspace_bytes(B, H, W), "uda_display_masks: workspace too small");
+    return pp_run("uda_display_masks", true, prob, B, H, W, thr, thr, sweeps, out, not_converged, workspace, (hipStream_t)stream);
 }

@@ -49,6 +49,12 @@ def _rows(g: torch.Tensor) -> torch.Tensor:
     return g.permute(0, 2, 3, 1).reshape(n * h * w, c)
 
 
+def check_input_size(H, W):
+    """the generator takes inputs whose height and width are multiples of 16 (no padding is invented)"""
+    if H % 16 or W % 16:
+        raise ValueError("input height/width must be multiples of 16, got %dx%d" % (H, W))
+
+
 STAT_SLOTS = 16     # UDA_STAT_SLOTS: replicas of every per-channel statistics accumulator
 
 
@@ -311,8 +317,7 @@ class GeneratorEngine:
         training = training if bn_training is None else bool(bn_training)
         S = ctx.S
         N, _, Hin, Win = x.shape
-        if Hin % 16 or Win % 16:
-            raise ValueError("input height/width must be multiples of 16, got %dx%d" % (Hin, Win))
+        check_input_size(Hin, Win)
         ctx.N = N
         if training:
             ctx.arena = _Arena(x, STAT_SLOTS * 2 * self.bn_channels * (2 if self.tn else 1))

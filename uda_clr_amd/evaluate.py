@@ -8,8 +8,11 @@ On request (``hd95``, ``tolerances``, ``cdr``) the batch goes through ``ops.surf
 the order statistics, tolerance counts and row extents that the 95th-percentile Hausdorff distance, the surface Dice at a tolerance
 and the vertical cup-to-disc ratio are closed forms of - still one copy per batch.
 
+With ``save_dir`` every image also leaves three PNG files there: ``overlay/`` (the reference's contour picture, utils/Utils.py:515-585),
+``original_image/`` and ``mask/`` (the evaluation masks the metrics were computed on, BEAL grey coding).
+
     python -m uda_clr_amd.evaluate --data-dir DIR --dataset Drishti-GS --checkpoint FILE [--hd95] [--tolerance 2 ...] [--cdr]
-                                   [--csv per_image.csv] [--json result.json]
+                                   [--csv per_image.csv] [--json result.json] [--save-dir DIR]
 """
 import argparse
 import csv
@@ -40,7 +43,7 @@ def extra_fields(hd95=False, tolerances=(), cdr=False):
     return tuple(names + (["vcdr_pred", "vcdr_gt", "cdr_error"] if cdr else []))
 
 
-def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=False, tolerances=(), cdr=False):
+def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=False, tolerances=(), cdr=False, save_dir=None):
     """Score ``model`` on every image of ``loader``.
 
     model       callable whose first output (or only output) is the [B,2,H,W] logits (cup, disc), e.g. ``DeepLab``
@@ -56,7 +59,12 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
     tolerances  pixel distances tau: also 'cup_nsd_<tau>', 'disc_nsd_<tau>' (tau as %g), the share of both borders' pixels within tau
                 of the other border (d2 <= floor(tau^2))
     cdr         True: also 'vcdr_pred', 'vcdr_gt' (cup height / disc height in rows, NaN without a disc) and 'cdr_error' = |pred - gt|
-    With any of the three set, per-image dicts and 'mean' carry the added names and the result lists them as 'extra_fields'."""
+    With any of the three set, per-image dicts and 'mean' carry the added names and the result lists them as 'extra_fields'.
+
+    save_dir    a folder: per image also <save_dir>/overlay/<stem>.png (outlines of the display masks of ``prob``: disc green, cup blue,
+                ``Utils.save_per_img_batch``), original_image/<stem>.png and mask/<stem>.png (``pred``, the masks the figures above
+                were computed on: 0 = cup, 128 = disc only, 255 = background).  The returned result is the same with and without it;
+                None (the default) makes no further call."""
     tolerances = tuple(float(t) for t in tolerances)
     extra = extra_fields(hd95, tolerances, cdr)
     dev = torch.device("cuda") if torch.cuda.is_available() else None
@@ -96,7 +104,11 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
                         more["cup_nsd_%g" % tau], more["disc_nsd_%g" % tau] = nsd[:, 0, t], nsd[:, 1, t]
                 if cdr:
                     more.update(metrics.vertical_cdr_from_profile(profile))
-                for i, name in enumerate(_names(sample, dice.shape[0], len(per_image))):
+                names = _names(sample, dice.shape[0], len(per_image))
+                if save_dir is not None:
+                    Utils.save_per_img_batch(image, save_dir, names, prob)
+                    Utils.save_mask_batch(pred, save_dir, names)
+                for i, name in enumerate(names):
                     per_image.append({"img_name": name,
                                       "cup_dice": float(dice[i, 0]), "disc_dice": float(dice[i, 1]),
                                       "cup_assd": float(sm["assd"][i, 0]), "disc_assd": float(sm["assd"][i, 1]),
@@ -142,6 +154,7 @@ def build_parser():
     ap.add_argument("--cdr", action="store_true", help="vertical cup-to-disc ratio and its error")
     ap.add_argument("--csv", default=None, metavar="PATH", help="one row per image")
     ap.add_argument("--json", default=None, metavar="PATH", help="the whole result")
+    ap.add_argument("--save-dir", default=None, metavar="DIR", help="write overlay/, original_image/ and mask/ PNG files per image")
     return ap
 
 
@@ -194,7 +207,7 @@ def main(argv=None, model=None):
         model = load_generator(args.checkpoint, args.backbone, args.out_stride, args.use_TN,
                                torch.device("cuda") if torch.cuda.is_available() else None)
     res = evaluate(model, loader, dataset=args.dataset, threshold=args.threshold, postprocess=not args.no_postprocess,
-                   hd95=args.hd95, tolerances=tuple(args.tolerance), cdr=args.cdr)
+                   hd95=args.hd95, tolerances=tuple(args.tolerance), cdr=args.cdr, save_dir=args.save_dir)
     print(format_mean(res))
     if args.csv:
         write_csv(args.csv, res)

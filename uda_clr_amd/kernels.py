@@ -137,6 +137,10 @@ SYMBOLS = {
     "uda_upconv_route_list": (C.c_char_p, []),
     "uda_postprocess_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_postprocess": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _U, _P]),
+    "uda_display_masks_workspace_bytes": (_U, [_I, _I, _I]),
+    "uda_display_masks": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _P, _U, _P]),
+    "uda_overlay_u8": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "uda_image_u8": (_I, [_P, _I, _I, _I, _P, _P]),
     "uda_surface_distance_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_surface_distance": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _U, _P]),
     "uda_surface_profile_workspace_bytes": (_U, [_I, _I, _I]),
@@ -1226,6 +1230,57 @@ class HipKernels:
                 return out
             n *= 2
         raise UdaError("uda_postprocess: label propagation did not converge after %d sweeps" % (n // 2))   # the last attempt's
+
+    def display_masks(self, prob, threshold=0.75, sweeps=None):
+        """prob f32 [B,2,H,W] probabilities (left unchanged) -> uint8 [B,2,H,W] display masks of the reference's ``save_per_img``
+        (include/uda_clr_hip.h, uda_display_masks).  Sweeps, doubling and the six attempts as ``postprocess``; the device reports
+        three propagations here (components, first flood, second flood)."""
+        self._dev(prob)
+        if prob.dtype != torch.float32 or not prob.is_contiguous() or prob.dim() != 4 or prob.shape[1] != 2:
+            raise ValueError("display_masks: contiguous float32 [B, 2, H, W] probabilities (got %s %s)" % (prob.dtype, tuple(prob.shape)))
+        B, _, H, W = prob.shape
+        out = torch.empty(B, 2, H, W, dtype=torch.uint8, device=prob.device)
+        flags = torch.zeros(3, dtype=torch.int32, device=prob.device)
+        ws = self._ws(prob, self.lib.uda_display_masks_workspace_bytes(B, H, W))
+        n = int(sweeps) if sweeps else 2 * ((H + 31) // 32 + (W + 31) // 32) + 4
+        for _ in range(6):
+            self._ck(self.lib.uda_display_masks(prob.data_ptr(), B, H, W, float(threshold), n, out.data_ptr(), flags.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), self._stream()))
+            if int(flags.sum()) == 0:            # host sync: evaluation path only
+                return out
+            n *= 2
+        raise UdaError("uda_display_masks: label propagation did not converge after %d sweeps" % (n // 2))   # the last attempt's
+
+    def overlay_u8(self, image_u8, masks_u8, out=None):
+        """image uint8 [B,H,W,3], masks uint8 [B,2,H,W] (nonzero = set) -> uint8 [B,H,W,3]: channel 1's outline in (0, 255, 0),
+        channel 0's in (0, 0, 255) over it, the image elsewhere (include/uda_clr_hip.h, uda_overlay_u8).  ``out`` may not alias
+        the image."""
+        for t in (image_u8, masks_u8):
+            self._dev(t)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4:
+                raise ValueError("overlay_u8: contiguous uint8 tensors (got %s %s)" % (t.dtype, tuple(t.shape)))
+        B, H, W, ch = image_u8.shape
+        if ch != 3 or tuple(masks_u8.shape) != (B, 2, H, W):
+            raise ValueError("overlay_u8: image [B, H, W, 3] and masks [B, 2, H, W] (got %s and %s)" % (tuple(image_u8.shape), tuple(masks_u8.shape)))
+        if out is None:
+            out = torch.empty_like(image_u8)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.shape != image_u8.shape or not out.is_cuda:
+            raise ValueError("overlay_u8: out must be a contiguous uint8 device tensor of the image's shape")
+        self._ck(self.lib.uda_overlay_u8(image_u8.data_ptr(), masks_u8.data_ptr(), B, H, W, out.data_ptr(), self._stream()))
+        return out
+
+    def image_u8(self, x, out=None):
+        """f32 [B,3,H,W] in [-1, 1] -> uint8 [B,H,W,3] = clip(rint((x + 1) * 127.5), 0, 255) (uda_image_u8)."""
+        self._dev(x)
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("image_u8: contiguous float32 [B, 3, H, W] (got %s %s)" % (x.dtype, tuple(x.shape)))
+        B, _, H, W = x.shape
+        if out is None:
+            out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=x.device)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != (B, H, W, 3) or not out.is_cuda:
+            raise ValueError("image_u8: out must be a contiguous uint8 [B, H, W, 3] device tensor")
+        self._ck(self.lib.uda_image_u8(x.data_ptr(), B, H, W, out.data_ptr(), self._stream()))
+        return out
 
     def surface_distance(self, pred_u8, gt_u8, want_d2=False):
         """uint8 [B,2,H,W] masks (nonzero = set) -> (table f64 [B,2,2,3], counts i64 [B,2,3][, d2 i32 [B,2,2,H,W]]) on the

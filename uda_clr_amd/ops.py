@@ -385,6 +385,54 @@ def _mask_u8(m):
     return (m if m.dtype == torch.bool else m > 0.5).to(torch.uint8).contiguous()
 
 
+def _to_device(*tensors):
+    """the tensors on one device: that of the first device tensor among them, else cuda (CPU tensors are moved there)"""
+    if not any(t.is_cuda for t in tensors) and not torch.cuda.is_available():
+        raise RuntimeError("uda_clr_amd pictures compute only on the MI355X HIP kernels (there is no CPU fallback)")
+    dev = next((t.device for t in tensors if t.is_cuda), torch.device("cuda"))
+    return [t.detach().to(dev) for t in tensors]
+
+
+def display_masks(prob, threshold=0.75):
+    """[B,2,H,W] (cup, disc) probabilities -> uint8 [B,2,H,W] display masks on the device, the chain of the reference's
+    ``save_per_img`` (utils/Utils.py:523-553): the outermost pixel ring read as 0, ``> threshold`` for both channels whatever the
+    dataset, five 7x7 medians, diamond(7) erosion, largest component, fill, diamond(7) dilation, fill.  ``prob`` is not modified
+    (the reference zeroes the ring in the caller's array).  Runs on the device (uda_display_masks); a CPU tensor is moved there."""
+    if prob.dim() != 4 or prob.shape[1] != 2:
+        raise ValueError("expected [B, 2, H, W] probabilities, got %s" % (tuple(prob.shape),))
+    (prob,) = _to_device(prob)
+    return kernels().display_masks(prob.contiguous().float(), threshold)
+
+
+def overlay(image, prob_or_masks):
+    """The reference's contour picture (utils/Utils.py:556-580) of a batch on the device -> uint8 [B,H,W,3]: the outline of channel
+    1 (disc) in (0, 255, 0), that of channel 0 (cup) in (0, 0, 255) over it, three pixels wide, the image elsewhere.
+        image          float [B,3,H,W] in [-1, 1] (bytes = clip(rint((x + 1) * 127.5), 0, 255)) or uint8 [B,H,W,3]
+        prob_or_masks  [B,2,H,W]: floating point = probabilities, run through ``display_masks``; uint8 or bool = masks, used as is
+    Outline pixels that would fall outside the image are dropped.  Neither argument is modified."""
+    if prob_or_masks.dim() != 4 or prob_or_masks.shape[1] != 2:
+        raise ValueError("expected [B, 2, H, W] probabilities or masks, got %s" % (tuple(prob_or_masks.shape),))
+    image, second = _to_device(image, prob_or_masks)
+    K = kernels()
+    if image.dtype == torch.uint8:
+        if image.dim() != 4 or image.shape[3] != 3:
+            raise ValueError("a uint8 image is [B, H, W, 3], got %s" % (tuple(image.shape),))
+        image = image.contiguous()
+    elif image.is_floating_point():
+        if image.dim() != 4 or image.shape[1] != 3:
+            raise ValueError("a float image is [B, 3, H, W], got %s" % (tuple(image.shape),))
+        image = K.image_u8(image.contiguous().float())
+    else:
+        raise ValueError("overlay: image must be float [B, 3, H, W] or uint8 [B, H, W, 3], got %s" % image.dtype)
+    if second.is_floating_point():
+        masks = K.display_masks(second.contiguous().float())
+    elif second.dtype in (torch.uint8, torch.bool):
+        masks = second.to(torch.uint8).contiguous()
+    else:
+        raise ValueError("overlay: probabilities (floating point) or masks (uint8 / bool), got %s" % second.dtype)
+    return K.overlay_u8(image, masks)
+
+
 def surface_distances(pred_mask, gt_mask):
     """Per image and class (cup, disc) the surface-distance table and the Dice counts of a [B,2,H,W] mask pair (uint8, bool or
     float; set means > 0.5), on the host after one synchronising copy:

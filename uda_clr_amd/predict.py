@@ -1,0 +1,137 @@
+"""Run a trained generator on a folder of fundus images that have no ground-truth masks.
+
+Every image file of ``--images`` is read with PIL, normalised as ``Normalize_tf`` normalises the image (v / 127.5 - 1) and batched
+with the images of its own size; per batch forward -> sigmoid -> ``postprocessing_batch`` -> pictures, all on the device:
+
+    <out>/overlay/<stem>.png          outlines of the display masks over the image (utils/Utils.py:515-585; disc green, cup blue)
+    <out>/original_image/<stem>.png   the image as it was fed
+    <out>/mask/<stem>.png             the evaluation mask, BEAL grey coding: 0 = cup, 128 = disc only, 255 = background
+    --csv FILE                        img_name, vcdr_pred: the predicted vertical cup-to-disc ratio (cup rows / disc rows, nan without a disc)
+
+An image whose height or width is not a multiple of 16 is refused by name: the generator takes no other size and no padding is invented.
+
+    python -m uda_clr_amd.predict --images DIR --checkpoint FILE --out DIR [--backbone mobilenet] [--out-stride 16] [--use_TN]
+                                  [--dataset Drishti-GS] [--threshold 0.75] [--batch-size 8] [--csv FILE]
+"""
+import argparse
+import csv
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import ops
+from .engine import check_input_size
+from .evaluate import load_generator
+from .utils import Utils, metrics
+
+EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="python -m uda_clr_amd.predict", description="Masks, contour pictures and the vertical CDR of a folder of fundus images.")
+    ap.add_argument("--images", required=True, metavar="DIR", help="folder of image files (no masks needed)")
+    ap.add_argument("--checkpoint", default=None, help="file with a 'model_state_dict'")
+    ap.add_argument("--out", required=True, metavar="DIR")
+    ap.add_argument("--backbone", default="mobilenet")
+    ap.add_argument("--out-stride", type=int, default=16)
+    ap.add_argument("--use_TN", action="store_true", help="TransNorm in place of BatchNorm, as the trainers' switch")
+    ap.add_argument("--dataset", default="Drishti-GS", help="as utils.Utils.postprocessing: names starting with 'D' threshold cup > 0.1, disc > 0.5")
+    ap.add_argument("--threshold", type=float, default=0.75)
+    ap.add_argument("--batch-size", type=int, default=8)
+    ap.add_argument("--csv", default=None, metavar="FILE", help="one row per image: img_name, vcdr_pred")
+    return ap
+
+
+def list_images(folder):
+    names = sorted(n for n in os.listdir(folder) if n.lower().endswith(EXTENSIONS))
+    if not names:
+        raise SystemExit("no image files under %s" % folder)
+    return names
+
+
+def read_images(folder, names):
+    """-> [(name, uint8 [H,W,3])], every size checked before anything runs"""
+    from PIL import Image
+    out = []
+    for name in names:
+        with Image.open(os.path.join(folder, name)) as im:
+            a = np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
+        try:
+            check_input_size(a.shape[0], a.shape[1])
+        except ValueError as e:
+            raise ValueError("%s: %s" % (name, e)) from None
+        out.append((name, a))
+    return out
+
+
+def batches(images, batch_size):
+    """images of one size together, in the order of their first image, at most ``batch_size`` each: [(names, uint8 [B,H,W,3])]"""
+    groups = {}
+    for name, a in images:
+        groups.setdefault(a.shape, []).append((name, a))
+    out = []
+    for group in groups.values():
+        for i in range(0, len(group), batch_size):
+            part = group[i:i + batch_size]
+            out.append(([n for n, _ in part], np.stack([a for _, a in part])))
+    return out
+
+
+def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_size=8):
+    """``images`` as ``read_images`` returns them -> [{'img_name', 'vcdr_pred'}] in batch order; writes the three folders."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("uda_clr_amd computes only on the MI355X HIP kernels (there is no CPU fallback)")
+    dev = torch.device("cuda")
+    was_training = getattr(model, "training", False)
+    if hasattr(model, "eval"):
+        model.eval()
+    rows = []
+    try:
+        with torch.no_grad():
+            for names, u8 in batches(images, batch_size):
+                u8 = torch.from_numpy(u8).to(dev)
+                x = (u8.permute(0, 3, 1, 2).float() / 127.5 - 1.0).contiguous()          # Normalize_tf's image, ToTensor's layout
+                out = model(x)
+                logits = out[0] if isinstance(out, (tuple, list)) else out
+                prob = torch.sigmoid(logits.float())
+                pred = Utils.postprocessing_batch(prob, threshold, dataset)
+                Utils.save_per_img_batch(u8, out_dir, names, prob)
+                Utils.save_mask_batch(pred, out_dir, names)
+                # the prediction as both masks: slot 1 of 'extent' is the prediction's first and last row per class
+                profile = ops.surface_profile(pred, pred, percentiles=(), tolerances=())[2]
+                vcdr = metrics.vertical_cdr_from_profile(profile)["vcdr_pred"]
+                rows += [{"img_name": n, "vcdr_pred": float(v)} for n, v in zip(names, vcdr)]
+    finally:
+        if was_training and hasattr(model, "train"):
+            model.train()
+    return rows
+
+
+def write_csv(path, rows):
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(("img_name", "vcdr_pred"))
+        for r in rows:
+            w.writerow([r["img_name"], repr(r["vcdr_pred"])])
+
+
+def main(argv=None, model=None):
+    """The command line.  ``model``: a callable to run instead of the checkpoint's DeepLab (tests)."""
+    args = build_parser().parse_args(argv)
+    images = read_images(args.images, list_images(args.images))
+    if model is None:
+        if not args.checkpoint:
+            raise SystemExit("--checkpoint is required")
+        model = load_generator(args.checkpoint, args.backbone, args.out_stride, args.use_TN,
+                               torch.device("cuda") if torch.cuda.is_available() else None)
+    rows = predict(model, images, args.out, dataset=args.dataset, threshold=args.threshold, batch_size=args.batch_size)
+    print("%d images -> %s" % (len(rows), args.out))
+    if args.csv:
+        write_csv(args.csv, rows)
+    return rows
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
