@@ -485,6 +485,31 @@ int uda_surface_profile(const uint8_t* pred, const uint8_t* gt, int B, int H, in
                         const int32_t* tol2, int T, double* table, int64_t* counts, int64_t* order, int64_t* within,
                         int64_t* extent, int32_t* d2, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- optic-disc morphometry of one (cup, disc) mask pair per image: the integers that the horizontal, vertical and area cup-to-disc
+ * ratios, the rim-to-disc profile around the disc, the cup's decentration and an ellipse summary of each structure are closed forms
+ * of (utils/metrics.py, morphometry_from_moments).  The reference (utils/metrics.py, utils/Utils.py) has none of these figures: the
+ * definitions are this project's.  Integers only, no floating-point atomics: bit-identical from run to run, an image's rows the same
+ * alone and inside any batch.
+ *   masks   uint8 [B][2: 0 cup, 1 disc][H][W], nonzero = set; never written.
+ *   sectors DEVICE int64 [K][2] = (x, y) of K boundary rays in strictly counter-clockwise order, x to the right and y UP, |x|, |y| <=
+ *           2^30 (utils.metrics.sector_table); K a multiple of 8, 8 <= K <= 360.  An argument, so that the kernel and any restatement
+ *           of it decide on the same numbers.
+ * Per image b and class k, r and c a pixel's row and column, all int64:
+ *   moments [B][2][6] = (n, sum r, sum c, sum r^2, sum c^2, sum r*c) over the set pixels; zeros for an empty plane.
+ *   extent  [B][2][4] = (first row, last row, first column, last column) with a set pixel; (-1, -1, -1, -1) for an empty plane.
+ *   overlap [B]       = pixels set in both planes.
+ *   radial  [B][2][K]: with (n, Sr, Sc) the DISC plane's n, sum r, sum c (the disc centroid is the origin for both classes) and
+ *           u = (ux, uy) = (n * c - Sc, -(n * r - Sr)), cross(a, u) = a.x * u.y - a.y * u.x, s_K = s_0: a set pixel with u != 0
+ *           belongs to the one sector j with cross(s_j, u) >= 0 and cross(s_j+1, u) < 0 (a pixel exactly on a boundary ray to the
+ *           sector that starts there); radial[b][k][j] = the largest ux^2 + uy^2 over the pixels of class k in sector j, -1 if the
+ *           sector holds none, -1 everywhere if the disc plane is empty.  A pixel with u = 0 is in no sector.  |u| < 2^30, so the
+ *           cross products stay below 2^61 and |u|^2 below 2^60.  sqrt(radial) / n is a distance in pixels.
+ * Limits as uda_surface_distance (1 <= H, W <= 1024, B <= 8192); a null pointer, a bad size, a K that is no multiple of 8 in 8..360
+ * or a workspace below uda_disc_morphometry_workspace_bytes returns the error before any launch and writes nothing. */
+size_t uda_disc_morphometry_workspace_bytes(int B, int H, int W, int K);
+int uda_disc_morphometry(const uint8_t* masks, int B, int H, int W, const int64_t* sectors, int K, int64_t* moments, int64_t* extent,
+                         int64_t* overlap, int64_t* radial, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- device-side tail of the input pipeline. The reference's dataloader workers run these per sample
  * on the CPU with scipy.ndimage; here they run per uint8 BATCH on the GPU, bit-identical to the scipy calls.
  * uda_normalize_tf: dataloaders/custom_transforms.py:432-466 (Normalize_tf), :414-429 (GetBoundary), :504-507 (ToTensor).

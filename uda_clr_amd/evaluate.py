@@ -6,13 +6,15 @@ The forward, ``postprocessing_batch`` and ``ops.surface_distances`` run per batc
 
 On request (``hd95``, ``tolerances``, ``cdr``) the batch goes through ``ops.surface_profile`` instead - the same table and counts plus
 the order statistics, tolerance counts and row extents that the 95th-percentile Hausdorff distance, the surface Dice at a tolerance
-and the vertical cup-to-disc ratio are closed forms of - still one copy per batch.
+and the vertical cup-to-disc ratio are closed forms of - still one copy per batch.  ``morphometry`` adds one ``ops.disc_morphometry``
+call per batch over the predicted and the true masks together: horizontal and area cup-to-disc ratio, the rim-to-disc profile's
+thinnest point and quadrant means, the cup's decentration.
 
 With ``save_dir`` every image also leaves three PNG files there: ``overlay/`` (the reference's contour picture, utils/Utils.py:515-585),
 ``original_image/`` and ``mask/`` (the evaluation masks the metrics were computed on, BEAL grey coding).
 
     python -m uda_clr_amd.evaluate --data-dir DIR --dataset Drishti-GS --checkpoint FILE [--hd95] [--tolerance 2 ...] [--cdr]
-                                   [--csv per_image.csv] [--json result.json] [--save-dir DIR]
+                                   [--morphometry [--sectors 72]] [--csv per_image.csv] [--json result.json] [--save-dir DIR]
 """
 import argparse
 import csv
@@ -35,15 +37,35 @@ def _names(sample, B, seen):
     return [str(n) for n in ([names] if isinstance(names, str) else list(names))]
 
 
-def extra_fields(hd95=False, tolerances=(), cdr=False):
+MORPHOMETRY_FIELDS = tuple("%s_%s" % (x, s) for x in ("hcdr", "acdr", "rdr_min") for s in ("pred", "gt", "error")) + tuple(
+    "rim_%s_%s" % (q, s) for q in ("up", "left", "down", "right") for s in ("pred", "gt")) + ("cup_offset_pred",)
+
+
+def extra_fields(hd95=False, tolerances=(), cdr=False, morphometry=False):
     """names of the per-image figures that ``evaluate`` adds for these arguments, in the order of its tables"""
     names = ["cup_hd95", "disc_hd95"] if hd95 else []
     for tau in tolerances:
         names += ["cup_nsd_%g" % tau, "disc_nsd_%g" % tau]
-    return tuple(names + (["vcdr_pred", "vcdr_gt", "cdr_error"] if cdr else []))
+    return tuple(names + (["vcdr_pred", "vcdr_gt", "cdr_error"] if cdr else [])) + (MORPHOMETRY_FIELDS if morphometry else ())
 
 
-def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=False, tolerances=(), cdr=False, save_dir=None):
+def morphometry_columns(pred, gt, sectors=72):
+    """{name: [B] float64} of MORPHOMETRY_FIELDS for [B,2,H,W] prediction and ground-truth masks: ONE ``ops.disc_morphometry`` call over
+    both, stacked along the batch, and the closed forms of ``metrics.morphometry_from_moments``"""
+    B = pred.shape[0]
+    f = metrics.morphometry_from_moments(ops.disc_morphometry(torch.cat([ops._mask_u8(pred), ops._mask_u8(gt)]), sectors))
+    cols = {}
+    for x in ("hcdr", "acdr", "rdr_min"):
+        cols[x + "_pred"], cols[x + "_gt"] = f[x][:B], f[x][B:]
+        cols[x + "_error"] = np.abs(f[x][:B] - f[x][B:])
+    for q in ("up", "left", "down", "right"):
+        cols["rim_%s_pred" % q], cols["rim_%s_gt" % q] = f["rim_" + q][:B], f["rim_" + q][B:]
+    cols["cup_offset_pred"] = np.hypot(f["cup_offset"][:B, 0], f["cup_offset"][:B, 1])
+    return cols
+
+
+def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=False, tolerances=(), cdr=False, morphometry=False,
+             sectors=72, save_dir=None):
     """Score ``model`` on every image of ``loader``.
 
     model       callable whose first output (or only output) is the [B,2,H,W] logits (cup, disc), e.g. ``DeepLab``
@@ -59,14 +81,20 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
     tolerances  pixel distances tau: also 'cup_nsd_<tau>', 'disc_nsd_<tau>' (tau as %g), the share of both borders' pixels within tau
                 of the other border (d2 <= floor(tau^2))
     cdr         True: also 'vcdr_pred', 'vcdr_gt' (cup height / disc height in rows, NaN without a disc) and 'cdr_error' = |pred - gt|
-    With any of the three set, per-image dicts and 'mean' carry the added names and the result lists them as 'extra_fields'.
+    morphometry True: also, from ONE ``ops.disc_morphometry`` call per batch over the prediction and ground-truth masks together
+                (``sectors`` sectors around the disc centroid), 'hcdr', 'acdr' (horizontal and area cup-to-disc ratio) and 'rdr_min'
+                (the thinnest rim-to-disc ratio) as '<x>_pred', '<x>_gt', '<x>_error' = |pred - gt|; 'rim_{up,left,down,right}_pred' /
+                '_gt' (mean rim-to-disc ratio per 90-degree quadrant); 'cup_offset_pred' (distance of the predicted cup's centroid from
+                the predicted disc's, pixels).  False (the default) makes no further call.
+    With any of the four set, per-image dicts and 'mean' carry the added names and the result lists them as 'extra_fields'.
 
     save_dir    a folder: per image also <save_dir>/overlay/<stem>.png (outlines of the display masks of ``prob``: disc green, cup blue,
                 ``Utils.save_per_img_batch``), original_image/<stem>.png and mask/<stem>.png (``pred``, the masks the figures above
                 were computed on: 0 = cup, 128 = disc only, 255 = background).  The returned result is the same with and without it;
                 None (the default) makes no further call."""
     tolerances = tuple(float(t) for t in tolerances)
-    extra = extra_fields(hd95, tolerances, cdr)
+    profiled = extra_fields(hd95, tolerances, cdr)
+    extra = extra_fields(hd95, tolerances, cdr, morphometry)
     dev = torch.device("cuda") if torch.cuda.is_available() else None
     was_training = getattr(model, "training", False)
     if hasattr(model, "eval"):
@@ -88,7 +116,7 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
                 else:
                     thr_cup, thr_disc = (0.1, 0.5) if dataset[0] == 'D' else (threshold, threshold)
                     pred = torch.stack([prob[:, 0] > thr_cup, prob[:, 1] > thr_disc], 1)
-                if extra:                                                            # the batch's one copy to the host, either way
+                if profiled:                                                         # the batch's one copy to the host, either way
                     table, counts, profile = ops.surface_profile(pred, target > 0.5, percentiles=(95,) if hd95 else (), tolerances=tolerances)
                 else:
                     table, counts = ops.surface_distances(pred, target > 0.5)
@@ -104,6 +132,8 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
                         more["cup_nsd_%g" % tau], more["disc_nsd_%g" % tau] = nsd[:, 0, t], nsd[:, 1, t]
                 if cdr:
                     more.update(metrics.vertical_cdr_from_profile(profile))
+                if morphometry:
+                    more.update(morphometry_columns(pred, target > 0.5, sectors))
                 names = _names(sample, dice.shape[0], len(per_image))
                 if save_dir is not None:
                     Utils.save_per_img_batch(image, save_dir, names, prob)
@@ -152,6 +182,8 @@ def build_parser():
     ap.add_argument("--hd95", action="store_true")
     ap.add_argument("--tolerance", type=float, nargs="+", default=[], metavar="TAU", help="surface Dice at these pixel tolerances")
     ap.add_argument("--cdr", action="store_true", help="vertical cup-to-disc ratio and its error")
+    ap.add_argument("--morphometry", action="store_true", help="horizontal and area CDR, thinnest rim, rim per quadrant, cup offset")
+    ap.add_argument("--sectors", type=int, default=72, metavar="K", help="sectors of the rim profile: a multiple of 8 in 8..360")
     ap.add_argument("--csv", default=None, metavar="PATH", help="one row per image")
     ap.add_argument("--json", default=None, metavar="PATH", help="the whole result")
     ap.add_argument("--save-dir", default=None, metavar="DIR", help="write overlay/, original_image/ and mask/ PNG files per image")
@@ -207,7 +239,8 @@ def main(argv=None, model=None):
         model = load_generator(args.checkpoint, args.backbone, args.out_stride, args.use_TN,
                                torch.device("cuda") if torch.cuda.is_available() else None)
     res = evaluate(model, loader, dataset=args.dataset, threshold=args.threshold, postprocess=not args.no_postprocess,
-                   hd95=args.hd95, tolerances=tuple(args.tolerance), cdr=args.cdr, save_dir=args.save_dir)
+                   hd95=args.hd95, tolerances=tuple(args.tolerance), cdr=args.cdr, save_dir=args.save_dir,
+                   morphometry=args.morphometry, sectors=args.sectors)
     print(format_mean(res))
     if args.csv:
         write_csv(args.csv, res)

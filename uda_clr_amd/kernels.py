@@ -145,6 +145,8 @@ SYMBOLS = {
     "uda_surface_distance": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _U, _P]),
     "uda_surface_profile_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_surface_profile": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _U, _P]),
+    "uda_disc_morphometry_workspace_bytes": (_U, [_I, _I, _I, _I]),
+    "uda_disc_morphometry": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _U, _P]),
     "uda_normalize_tf_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_normalize_tf": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _U, _P]),
     "uda_field_smooth": (_I, [_P, _I, _I, _I, _P, _I, _D, _P, _P, _P]),
@@ -1333,6 +1335,33 @@ class HipKernels:
                                               table.data_ptr(), counts.data_ptr(), order.data_ptr(), within.data_ptr(), extent.data_ptr(),
                                               None, ws.data_ptr(), ws.numel(), self._stream()))
         out = (table, counts, order, within, extent)
+        return out + (packed,) if want_packed else out
+
+    def disc_morphometry(self, masks_u8, sectors, want_packed=False):
+        """uint8 [B,2,H,W] masks (0 cup, 1 disc; nonzero = set), sectors int64 [K,2] on the device (``utils.metrics.sector_table``)
+        -> (moments i64 [B,2,6], extent i64 [B,2,4], overlap i64 [B], radial i64 [B,2,K]) on the device (include/uda_clr_hip.h,
+        uda_disc_morphometry): per class n, sum r, sum c, sum r^2, sum c^2, sum r*c; first and last row and column; the pixels set
+        in both planes; per sector about the disc centroid the largest squared distance scaled by n_disc^2, -1 for an empty sector.
+        The four are views of one int64 buffer, handed back as a fifth value with ``want_packed`` (one copy moves all)."""
+        self._dev(masks_u8)
+        if masks_u8.dtype != torch.uint8 or not masks_u8.is_contiguous() or masks_u8.dim() != 4 or masks_u8.shape[1] != 2:
+            raise ValueError("disc_morphometry: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (masks_u8.dtype, tuple(masks_u8.shape)))
+        if not sectors.is_cuda:
+            raise UdaError("HIP kernels need device tensors (got %s); there is no CPU fallback" % sectors.device)
+        if sectors.dtype != torch.int64 or not sectors.is_contiguous() or sectors.dim() != 2 or sectors.shape[1] != 2:
+            raise ValueError("disc_morphometry: contiguous int64 [K, 2] sector table (got %s %s)" % (sectors.dtype, tuple(sectors.shape)))
+        K = sectors.shape[0]
+        if K % 8 or not 8 <= K <= 360:
+            raise ValueError("disc_morphometry: the number of sectors must be a multiple of 8 in 8..360, got %d" % K)
+        B, _, H, W = masks_u8.shape
+        sizes = (B * 12, B * 8, B, B * 2 * K)
+        packed = torch.empty(sum(sizes), dtype=torch.int64, device=masks_u8.device)
+        moments, extent, overlap, radial = torch.split(packed, sizes)
+        moments, extent, radial = moments.view(B, 2, 6), extent.view(B, 2, 4), radial.view(B, 2, K)
+        ws = self._ws(masks_u8, self.lib.uda_disc_morphometry_workspace_bytes(B, H, W, K))
+        self._ck(self.lib.uda_disc_morphometry(masks_u8.data_ptr(), B, H, W, sectors.data_ptr(), K, moments.data_ptr(), extent.data_ptr(),
+                                               overlap.data_ptr(), radial.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        out = (moments, extent, overlap, radial)
         return out + (packed,) if want_packed else out
 
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):

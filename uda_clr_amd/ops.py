@@ -483,3 +483,36 @@ def surface_profile(pred_mask, gt_mask, percentiles=(95,), tolerances=()):
     profile = {"order": order.reshape(B, 2, 3, Q, 2), "within": within.reshape(B, 2, 2, T), "extent": extent.reshape(B, 2, 2, 2),
                "quantiles": quantiles, "tolerances": tol, "tol2": tol2}
     return table.view(np.float64).reshape(B, 2, 2, 3), counts.reshape(B, 2, 3), profile
+
+
+def disc_morphometry(masks, sectors=72):
+    """The integers of the optic-disc morphometry of a [B,2,H,W] (cup, disc) mask batch (uint8, bool or float; set means > 0.5), on the
+    host after ONE synchronising copy:
+        sectors   K (a multiple of 8 in 8..360; the table is ``utils.metrics.sector_table(K)``), or an int64 [K,2] table of boundary
+                  rays (x right, y up, strictly counter-clockwise, |x|, |y| <= 2^30)
+    -> {'moments' int64 [B,2,6]: per class n, sum r, sum c, sum r^2, sum c^2, sum r*c over the set pixels (row r, column c)
+        'extent'  int64 [B,2,4]: first row, last row, first column, last column with a set pixel; -1 for an empty plane
+        'overlap' int64 [B]: pixels set in both planes
+        'radial'  int64 [B,2,K]: per sector about the DISC centroid the largest ux^2 + uy^2 of u = (n c - sum c, -(n r - sum r)) with
+                  the disc's n and sums (sqrt / n is a distance in pixels); -1 for a sector without a pixel, and without a disc
+        'table'   int64 [K,2]: the sector table that was used}
+    as numpy arrays (``utils.metrics.morphometry_from_moments`` turns them into the CDR family, the rim profile, the cup's decentration
+    and the ellipse summaries).  Runs on the device (uda_disc_morphometry); a CPU tensor is moved there."""
+    import numpy as np
+    from .utils.metrics import sector_table
+    table = sector_table(sectors) if isinstance(sectors, (int, np.integer)) else np.ascontiguousarray(np.asarray(sectors), dtype=np.int64)
+    if table.ndim != 2 or table.shape[1] != 2 or table.shape[0] % 8 or not 8 <= table.shape[0] <= 360:
+        raise ValueError("disc_morphometry: sectors is K or an int64 [K, 2] table, K a multiple of 8 in 8..360 (got shape %s)" % (table.shape,))
+    if np.abs(table).max() > 2 ** 30:
+        raise ValueError("disc_morphometry: sector table entries must lie within +-2^30")
+    if masks.dim() != 4 or masks.shape[1] != 2:
+        raise ValueError("expected a [B, 2, H, W] mask, got %s" % (tuple(masks.shape),))
+    if not masks.is_cuda and not torch.cuda.is_available():
+        raise RuntimeError("uda_clr_amd morphometry computes only on the MI355X HIP kernels (there is no CPU fallback)")
+    dev = masks.device if masks.is_cuda else torch.device("cuda")
+    packed = kernels().disc_morphometry(_mask_u8(masks.detach().to(dev)), torch.from_numpy(table).to(dev), want_packed=True)[-1]
+    host = packed.cpu().numpy()                                                                          # the one copy (it synchronises)
+    B, K = masks.shape[0], table.shape[0]
+    moments, extent, overlap, radial = np.split(host, np.cumsum([B * 12, B * 8, B]))
+    return {"moments": moments.reshape(B, 2, 6), "extent": extent.reshape(B, 2, 4), "overlap": overlap.reshape(B),
+            "radial": radial.reshape(B, 2, K), "table": table}

@@ -11,7 +11,11 @@ with the images of its own size; per batch forward -> sigmoid -> ``postprocessin
 An image whose height or width is not a multiple of 16 is refused by name: the generator takes no other size and no padding is invented.
 
     python -m uda_clr_amd.predict --images DIR --checkpoint FILE --out DIR [--backbone mobilenet] [--out-stride 16] [--use_TN]
-                                  [--dataset Drishti-GS] [--threshold 0.75] [--batch-size 8] [--csv FILE]
+                                  [--dataset Drishti-GS] [--threshold 0.75] [--batch-size 8] [--csv FILE] [--morphometry [--sectors 72]]
+
+With ``--morphometry`` the CSV also carries, per image, hcdr_pred and acdr_pred (horizontal and area cup-to-disc ratio), rdr_min_pred and
+rim_{up,left,down,right}_pred (thinnest and per-quadrant rim-to-disc ratio), cup_offset_pred (pixels) and {cup,disc}_{major,minor,
+orientation} (ellipse axes in pixels, degrees counter-clockwise from "right"); without it the CSV is img_name, vcdr_pred.
 """
 import argparse
 import csv
@@ -41,6 +45,8 @@ def build_parser():
     ap.add_argument("--threshold", type=float, default=0.75)
     ap.add_argument("--batch-size", type=int, default=8)
     ap.add_argument("--csv", default=None, metavar="FILE", help="one row per image: img_name, vcdr_pred")
+    ap.add_argument("--morphometry", action="store_true", help="the CSV also gets horizontal and area CDR, rim profile figures, cup offset, ellipse axes")
+    ap.add_argument("--sectors", type=int, default=72, metavar="K", help="sectors of the rim profile: a multiple of 8 in 8..360")
     return ap
 
 
@@ -79,8 +85,26 @@ def batches(images, batch_size):
     return out
 
 
-def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_size=8):
-    """``images`` as ``read_images`` returns them -> [{'img_name', 'vcdr_pred'}] in batch order; writes the three folders."""
+MORPHOMETRY_COLUMNS = ("hcdr_pred", "acdr_pred", "rdr_min_pred", "rim_up_pred", "rim_left_pred", "rim_down_pred", "rim_right_pred",
+                       "cup_offset_pred") + tuple("%s_%s" % (c, x) for c in ("cup", "disc") for x in ("major", "minor", "orientation"))
+
+
+def morphometry_columns(pred, sectors=72):
+    """{name: [B] float64} of MORPHOMETRY_COLUMNS for [B,2,H,W] predicted masks: one ``ops.disc_morphometry`` call and its closed forms"""
+    f = metrics.morphometry_from_moments(ops.disc_morphometry(pred, sectors))
+    cols = {x + "_pred": f[x] for x in ("hcdr", "acdr", "rdr_min", "rim_up", "rim_left", "rim_down", "rim_right")}
+    cols["cup_offset_pred"] = np.hypot(f["cup_offset"][:, 0], f["cup_offset"][:, 1])
+    for k, c in enumerate(("cup", "disc")):
+        for x in ("major", "minor", "orientation"):
+            cols["%s_%s" % (c, x)] = f[x][:, k]
+    return cols
+
+
+def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_size=8, morphometry=False, sectors=72):
+    """``images`` as ``read_images`` returns them -> [{'img_name', 'vcdr_pred'}] in batch order; writes the three folders.
+    ``morphometry``: every row also carries MORPHOMETRY_COLUMNS (horizontal and area cup-to-disc ratio, the thinnest rim-to-disc ratio
+    of ``sectors`` sectors and its quadrant means, the cup's decentration in pixels, full axes in pixels and orientation in degrees of
+    the ellipse with each structure's covariance), from one ``ops.disc_morphometry`` call per batch."""
     if not torch.cuda.is_available():
         raise RuntimeError("uda_clr_amd computes only on the MI355X HIP kernels (there is no CPU fallback)")
     dev = torch.device("cuda")
@@ -102,7 +126,12 @@ def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_
                 # the prediction as both masks: slot 1 of 'extent' is the prediction's first and last row per class
                 profile = ops.surface_profile(pred, pred, percentiles=(), tolerances=())[2]
                 vcdr = metrics.vertical_cdr_from_profile(profile)["vcdr_pred"]
+                first = len(rows)
                 rows += [{"img_name": n, "vcdr_pred": float(v)} for n, v in zip(names, vcdr)]
+                if morphometry:
+                    cols = morphometry_columns(pred, sectors)
+                    for i in range(len(names)):
+                        rows[first + i].update({k: float(cols[k][i]) for k in MORPHOMETRY_COLUMNS})
     finally:
         if was_training and hasattr(model, "train"):
             model.train()
@@ -110,11 +139,13 @@ def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_
 
 
 def write_csv(path, rows):
+    """img_name, vcdr_pred, and MORPHOMETRY_COLUMNS where the rows carry them"""
+    more = MORPHOMETRY_COLUMNS if rows and MORPHOMETRY_COLUMNS[0] in rows[0] else ()
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(("img_name", "vcdr_pred"))
+        w.writerow(("img_name", "vcdr_pred") + more)
         for r in rows:
-            w.writerow([r["img_name"], repr(r["vcdr_pred"])])
+            w.writerow([r["img_name"], repr(r["vcdr_pred"])] + [repr(r[k]) for k in more])
 
 
 def main(argv=None, model=None):
@@ -126,7 +157,8 @@ def main(argv=None, model=None):
             raise SystemExit("--checkpoint is required")
         model = load_generator(args.checkpoint, args.backbone, args.out_stride, args.use_TN,
                                torch.device("cuda") if torch.cuda.is_available() else None)
-    rows = predict(model, images, args.out, dataset=args.dataset, threshold=args.threshold, batch_size=args.batch_size)
+    rows = predict(model, images, args.out, dataset=args.dataset, threshold=args.threshold, batch_size=args.batch_size,
+                   morphometry=args.morphometry, sectors=args.sectors)
     print("%d images -> %s" % (len(rows), args.out))
     if args.csv:
         write_csv(args.csv, rows)

@@ -6,6 +6,8 @@ return conventions).  The thresholding and the three pixel counts per class run 
     2x2 confusion (rows = label, cols = prediction): TP = I, FP = S - I, FN = G - I, TN = n - S - G + I
     PA = (TP + TN) / n,  IoU_fg = TP / (TP + FP + FN),  IoU_bg = TN / (TN + FP + FN)   (:149-168)
 """
+import math
+
 import numpy as np
 import torch
 
@@ -128,6 +130,94 @@ def vertical_cdr_from_profile(profile):
     with np.errstate(divide="ignore", invalid="ignore"):
         vcdr = np.where(diam[:, 1] > 0, diam[:, 0] / diam[:, 1], np.nan)                 # [B, slot]
     return {"vcdr_pred": vcdr[:, 1], "vcdr_gt": vcdr[:, 0], "cdr_error": np.abs(vcdr[:, 1] - vcdr[:, 0])}
+
+
+# ---- optic-disc morphometry: closed forms of the integers of ops.disc_morphometry.  Angles are in degrees,
+# counter-clockwise from "right" as the image is seen (x = column, y = -row); nothing is named nasal or temporal, because the
+# laterality of the eye is not known here.
+def sector_table(K):
+    """int64 [K,2]: the boundary rays (x, y) of K sectors, sector j spanning [360 j / K, 360 (j + 1) / K) degrees.  For j < K / 4,
+    s_j = (rint(2^30 cos t), rint(2^30 sin t)) at t = 2 pi j / K in float64; the other three quadrants are exact 90-degree rotations,
+    s_{j + K/4} = (-s_j.y, s_j.x).  K is a multiple of 8 in 8..360 (whole sectors per 90-degree quadrant centred on an axis)."""
+    K = int(K)
+    if K % 8 or not 8 <= K <= 360:
+        raise ValueError("sector_table: K must be a multiple of 8 in 8..360, got %d" % K)
+    q = K // 4
+    t = 2.0 * np.pi * np.arange(q, dtype=np.float64) / K
+    s = np.empty((K, 2), np.int64)
+    s[:q, 0], s[:q, 1] = np.rint(2.0 ** 30 * np.cos(t)), np.rint(2.0 ** 30 * np.sin(t))
+    for k in range(1, 4):
+        s[k * q:(k + 1) * q, 0], s[k * q:(k + 1) * q, 1] = -s[(k - 1) * q:k * q, 1], s[(k - 1) * q:k * q, 0]
+    return s
+
+
+def _row_means(a):
+    """[B,n] -> [B]: per row the correctly rounded sum (math.fsum: no order of summation to state) of the entries that are not NaN,
+    over their number; NaN where there is none"""
+    out = np.full(a.shape[0], np.nan)
+    for b, row in enumerate(a):
+        vals = [float(v) for v in row if not math.isnan(v)]
+        if vals:
+            out[b] = math.fsum(vals) / len(vals)
+    return out
+
+
+def morphometry_from_moments(m):
+    """m: the dict of ``ops.disc_morphometry`` -> dict of per-image float64 arrays (class 0 = cup, 1 = disc), all computed from the
+    exact integers; NaN where a figure has no meaning:
+        vcdr, hcdr [B]      cup / disc diameter along rows / columns (last - first + 1); NaN without a disc, 0 for an empty cup
+        acdr [B]            n_cup / n_disc; NaN without a disc
+        rim_area [B]        n_disc - overlap, pixels of the disc outside the cup
+        centroid [B,2,2]    (row, column) per class; NaN for an empty plane
+        major, minor [B,2]  4 sqrt(lambda) of the two eigenvalues of the pixel covariance, whose numerators n sum r^2 - (sum r)^2, ...
+                            are formed in integers: the full axes of the ellipse with that covariance; NaN for an empty plane
+        orientation [B,2]   angle of the major axis in (-90, 90] degrees (0 for a circle); eccentricity [B,2] = sqrt(1 - minor^2 / major^2)
+        cup_offset [B,2]    cup centroid - disc centroid as (rows, columns)
+        rim_ratio [B,K]     1 - R_cup / R_disc per sector, R = sqrt(radial) / n_disc the furthest pixel of the class in the sector:
+                            the rim's share of the disc radius there.  NaN where either sector holds no pixel; with a wholly empty cup,
+                            1 wherever the disc's sector holds one
+        rdr_min, rdr_min_angle [B]   the thinnest rim and the centre of its sector (the first of equals) in degrees
+        n_empty_sectors [B] sectors whose rim_ratio is NaN
+        rim_up, rim_left, rim_down, rim_right [B]   mean rim_ratio (NaN entries left out) of the 90-degree quadrants centred on 90, 180,
+                            270 and 0 degrees"""
+    mom, ext = np.asarray(m["moments"], np.int64), np.asarray(m["extent"], np.int64)
+    ovl, rad = np.asarray(m["overlap"], np.int64), np.asarray(m["radial"], np.int64)
+    B, K = rad.shape[0], rad.shape[2]
+    n, sr, sc, srr, scc, src = (mom[..., i] for i in range(6))                            # [B,2]
+    nf = n.astype(np.float64)
+    some, disc = n > 0, n[:, 1] > 0
+    out = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name, lo, hi in (("vcdr", 0, 1), ("hcdr", 2, 3)):
+            diam = np.where(ext[..., lo] < 0, 0, ext[..., hi] - ext[..., lo] + 1).astype(np.float64)
+            out[name] = np.where(diam[:, 1] > 0, diam[:, 0] / diam[:, 1], np.nan)
+        out["acdr"] = np.where(disc, nf[:, 0] / nf[:, 1], np.nan)
+        out["rim_area"] = (n[:, 1] - ovl).astype(np.float64)
+        cen = np.stack([sr / nf, sc / nf], -1)                                            # 0 / 0 = NaN for an empty plane
+        out["centroid"] = cen
+        n2 = nf * nf
+        vrr, vcc, vrc = (n * srr - sr * sr) / n2, (n * scc - sc * sc) / n2, (n * src - sr * sc) / n2      # integer numerators < 2^61
+        half, diff = (vcc + vrr) / 2.0, (vcc - vrr) / 2.0                                 # x = column, y = -row: cov_xy = -vrc
+        root = np.sqrt(diff * diff + vrc * vrc)
+        l1, l2 = half + root, np.maximum(half - root, 0.0)
+        out["major"], out["minor"] = 4.0 * np.sqrt(l1), 4.0 * np.sqrt(l2)
+        out["orientation"] = np.where(some, np.degrees(0.5 * np.arctan2(0.0 - 2.0 * vrc, vcc - vrr)), np.nan)      # 0.0 - 0.0 = +0.0: 90, not -90
+        out["eccentricity"] = np.where(l1 > 0, np.sqrt(1.0 - l2 / l1), np.where(some, 0.0, np.nan))
+        out["cup_offset"] = cen[:, 0] - cen[:, 1]
+        R = np.sqrt(np.maximum(rad, 0).astype(np.float64)) / nf[:, 1, None, None]         # [B,2,K]
+        ratio = np.where((rad < 0).any(1), np.nan, 1.0 - R[:, 0] / R[:, 1])
+        ratio = np.where((~some[:, 0])[:, None] & (rad[:, 1] >= 0), 1.0, ratio)
+    out["rim_ratio"] = ratio
+    empty = np.isnan(ratio)
+    out["n_empty_sectors"] = empty.sum(1).astype(np.float64)
+    first = np.where(empty, np.inf, ratio).argmin(1)
+    out["rdr_min"] = np.where(empty.all(1), np.nan, np.where(empty, np.inf, ratio).min(1))
+    out["rdr_min_angle"] = np.where(empty.all(1), np.nan, (first + 0.5) * (360.0 / K))
+    e = K // 8
+    turned = np.roll(ratio, e, axis=1)                                                    # entry 0 = sector K - K/8: -45 degrees
+    for i, name in enumerate(("rim_right", "rim_up", "rim_left", "rim_down")):
+        out[name] = _row_means(turned[:, 2 * e * i:2 * e * (i + 1)])
+    return out
 
 
 def hd95_2label(pred_mask, gt_mask):
