@@ -510,6 +510,35 @@ size_t uda_disc_morphometry_workspace_bytes(int B, int H, int W, int K);
 int uda_disc_morphometry(const uint8_t* masks, int B, int H, int W, const int64_t* sectors, int K, int64_t* moments, int64_t* extent,
                          int64_t* overlap, int64_t* radial, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- MC-dropout uncertainty at evaluation, and the integer tables that calibration and selective-prediction figures are closed
+ * forms of (utils/metrics.py, calibration_from_table / selective_from_table).  The reference trusts a target pseudo-label where the
+ * unbiased std over its T = 8 stochastic passes of sigmoid(x / 2) is below 0.04 (utils/Utils.py:165-166 `torch.sigmoid(preds / 2.0)`, `torch.std(preds, dim=0)`;
+ * :197-200 `std_map_small < 0.04`) and never scores that rule against labels; the tables and the maps beyond std and mean are this project's.
+ * uda_mc_uncertainty: logits f32 [T][n], 2 <= T <= 32, n > 0; one read of the logits; every output f32 [n] (std_u8: uint8 [n]) and
+ *   optional - null = not written, at least one given:
+ *     mean_prob   = mean_t sigmoid(x_t)
+ *     std_half    = unbiased std over t of sigmoid(x_t / 2), two-pass (utils/Utils.py:165-166, at full resolution)
+ *     entropy     = H(mean_prob), H(p) = -p log p - (1 - p) log(1 - p) in nats, 0 log 0 = 0
+ *     mutual_info = max(0, H(mean_prob) - mean_t H(sigmoid(x_t)))
+ *     std_u8      = min(255, (int)floorf(std_half * u8_scale)) of the very fp32 value stored to std_half (u8_scale finite, > 0)
+ *   An element's outputs depend on its own T logits only: any chunking of n gives the same bits.  16-byte loads and stores where n
+ *   % 4 == 0 and every pointer given is 16-byte (std_u8: 4-byte) aligned, element-wise otherwise.  uda_mc_stats is unchanged.
+ * uda_selective_tables: prob, unc f32 [B][2][H][W] (either may be null); pred, gt uint8 [B][2][H][W], nonzero = set, gt null = pred;
+ *   M confidence bins in 1..64; edges HOST float[K - 1], finite and strictly ascending, K uncertainty bins in 1..64 (read before the
+ *   call returns, passed to the kernel by value); 1 <= H, W <= 1024, B <= 8192.  All outputs int64, exact functions of the floats:
+ *     rel     [B][2][M][5] = (n, n_pos, sum q, sum q over gt-set pixels, sum q^2) per bin b = min(M - 1, (int)floorf(p * (float)M)),
+ *             q = (int)rintf(p * 65536.0f) (an exact multiply; sum q^2 <= 2^52).  Null = not wanted; needs prob.
+ *     risk    [B][2][K][4] = (TP, FP, FN, TN) of pred against gt per bin k = #{j : edges[j] <= u}: a value on an edge goes to the
+ *             upper bin, +inf to the last.  Null = not wanted; needs unc.  At least one of rel and risk.
+ *     invalid [B][2][2] = pixels whose p is NaN or outside [0, 1], pixels whose u is NaN or negative (-0.0 is not): each is left
+ *             out of that table only.  A column whose table is not asked for stays 0.
+ *   The entry zeroes the outputs it was given; no workspace.  Integer sums only: bit-identical from run to run, an image's rows the
+ *   same alone and inside any batch.  A bad argument returns the error before anything is written. */
+int uda_mc_uncertainty(const float* logits, int T, int64_t n, float* mean_prob, float* std_half, float* entropy, float* mutual_info,
+                       uint8_t* std_u8, float u8_scale, void* stream);
+int uda_selective_tables(const float* prob, const float* unc, const uint8_t* pred, const uint8_t* gt, int B, int H, int W, int M,
+                         const float* edges, int K, int64_t* rel, int64_t* risk, int64_t* invalid, void* stream);
+
 /* ---- device-side tail of the input pipeline. The reference's dataloader workers run these per sample
  * on the CPU with scipy.ndimage; here they run per uint8 BATCH on the GPU, bit-identical to the scipy calls.
  * uda_normalize_tf: dataloaders/custom_transforms.py:432-466 (Normalize_tf), :414-429 (GetBoundary), :504-507 (ToTensor).

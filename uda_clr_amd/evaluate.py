@@ -10,11 +10,18 @@ and the vertical cup-to-disc ratio are closed forms of - still one copy per batc
 call per batch over the predicted and the true masks together: horizontal and area cup-to-disc ratio, the rim-to-disc profile's
 thinnest point and quadrant means, the cup's decentration.
 
+``calibration`` and ``mc_passes`` add one ``ops.selective_tables`` call per batch: the reliability table of the deterministic
+probabilities against the labels (ECE, Brier score, reliability diagram) and, from T MC-dropout passes of the same batch
+(``DeepLab.mc_inference_logits`` -> ``ops.mc_uncertainty``), the errors of the scored masks per bin of the std of sigmoid(x / 2) - the
+quantity the trainer thresholds at 0.04 (reference utils/Utils.py:165-166, :197-200): what share of the pixels that mask keeps, how
+clean the kept labels are, and how well the uncertainty ranks the errors (AUROC, risk-coverage curve).
+
 With ``save_dir`` every image also leaves three PNG files there: ``overlay/`` (the reference's contour picture, utils/Utils.py:515-585),
 ``original_image/`` and ``mask/`` (the evaluation masks the metrics were computed on, BEAL grey coding).
 
     python -m uda_clr_amd.evaluate --data-dir DIR --dataset Drishti-GS --checkpoint FILE [--hd95] [--tolerance 2 ...] [--cdr]
-                                   [--morphometry [--sectors 72]] [--csv per_image.csv] [--json result.json] [--save-dir DIR]
+                                   [--morphometry [--sectors 72]] [--calibration [--bins 15]] [--mc-passes 8]
+                                   [--csv per_image.csv] [--json result.json] [--save-dir DIR]
 """
 import argparse
 import csv
@@ -41,12 +48,25 @@ MORPHOMETRY_FIELDS = tuple("%s_%s" % (x, s) for x in ("hcdr", "acdr", "rdr_min")
     "rim_%s_%s" % (q, s) for q in ("up", "left", "down", "right") for s in ("pred", "gt")) + ("cup_offset_pred",)
 
 
-def extra_fields(hd95=False, tolerances=(), cdr=False, morphometry=False):
+CALIBRATION_FIELDS = ("cup_ece", "disc_ece", "cup_brier", "disc_brier")
+UNCERTAINTY_U8_SCALE = 1600.0       # uncertainty/<stem>.png: grey = min(255, floor(std * 1600)), the trainer's 0.04 at grey 64
+
+
+def uncertainty_fields(report_edges=(0.04,)):
+    """names of the per-image figures of ``mc_passes``: the AUROC, then coverage, kept Dice and kept error rate per reported edge"""
+    names = ["cup_unc_auroc", "disc_unc_auroc"]
+    for e in report_edges:
+        names += ["%s_%s_%g" % (c, x, e) for x in ("cov", "dice", "err") for c in ("cup", "disc")]
+    return tuple(names)
+
+
+def extra_fields(hd95=False, tolerances=(), cdr=False, morphometry=False, calibration=False, mc_passes=0, report_edges=(0.04,)):
     """names of the per-image figures that ``evaluate`` adds for these arguments, in the order of its tables"""
     names = ["cup_hd95", "disc_hd95"] if hd95 else []
     for tau in tolerances:
         names += ["cup_nsd_%g" % tau, "disc_nsd_%g" % tau]
-    return tuple(names + (["vcdr_pred", "vcdr_gt", "cdr_error"] if cdr else [])) + (MORPHOMETRY_FIELDS if morphometry else ())
+    return (tuple(names + (["vcdr_pred", "vcdr_gt", "cdr_error"] if cdr else [])) + (MORPHOMETRY_FIELDS if morphometry else ()) +
+            (CALIBRATION_FIELDS if calibration else ()) + (uncertainty_fields(report_edges) if mc_passes else ()))
 
 
 def morphometry_columns(pred, gt, sectors=72):
@@ -64,8 +84,39 @@ def morphometry_columns(pred, gt, sectors=72):
     return cols
 
 
+def _edge_index(unc_edges, report_edges):
+    """positions of ``report_edges`` in ``unc_edges``, both compared as the float32 values the kernel bins with"""
+    have = [float(np.float32(e)) for e in unc_edges]
+    try:
+        return [have.index(float(np.float32(e))) for e in report_edges]
+    except ValueError:
+        raise ValueError("report_edges %r must be among unc_edges %r" % (tuple(report_edges), tuple(unc_edges))) from None
+
+
+def calibration_columns(rel):
+    """{name: [B] float64} of CALIBRATION_FIELDS from a [B,2,M,5] reliability table"""
+    c = metrics.calibration_from_table(rel)
+    return {"cup_ece": c["ece"][:, 0], "disc_ece": c["ece"][:, 1], "cup_brier": c["brier"][:, 0], "disc_brier": c["brier"][:, 1]}
+
+
+def uncertainty_columns(risk, unc_edges, report_edges=(0.04,)):
+    """{name: [B] float64} of ``uncertainty_fields(report_edges)`` from a [B,2,K,4] risk table"""
+    s = metrics.selective_from_table(risk, unc_edges)
+    cols = {"cup_unc_auroc": s["unc_auroc"][:, 0], "disc_unc_auroc": s["unc_auroc"][:, 1]}
+    for e, j in zip(report_edges, _edge_index(unc_edges, report_edges)):
+        for x, key in (("cov", "coverage"), ("dice", "dice"), ("err", "error")):
+            cols["cup_%s_%g" % (x, e)], cols["disc_%s_%g" % (x, e)] = s[key][:, 0, j], s[key][:, 1, j]
+    return cols
+
+
+def _lists(d):
+    """a dict of numpy arrays as nested lists (what ``write_json`` can dump)"""
+    return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in d.items()}
+
+
 def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=False, tolerances=(), cdr=False, morphometry=False,
-             sectors=72, save_dir=None):
+             sectors=72, calibration=False, bins=15, mc_passes=0, unc_edges=ops.DEFAULT_UNC_EDGES, report_edges=(0.04,), mc_logits=None,
+             save_dir=None):
     """Score ``model`` on every image of ``loader``.
 
     model       callable whose first output (or only output) is the [B,2,H,W] logits (cup, disc), e.g. ``DeepLab``
@@ -86,15 +137,35 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
                 (the thinnest rim-to-disc ratio) as '<x>_pred', '<x>_gt', '<x>_error' = |pred - gt|; 'rim_{up,left,down,right}_pred' /
                 '_gt' (mean rim-to-disc ratio per 90-degree quadrant); 'cup_offset_pred' (distance of the predicted cup's centroid from
                 the predicted disc's, pixels).  False (the default) makes no further call.
-    With any of the four set, per-image dicts and 'mean' carry the added names and the result lists them as 'extra_fields'.
+    calibration True: also, from ONE ``ops.selective_tables`` call per batch on ``prob`` against ``target > 0.5`` with ``bins``
+                confidence bins, '{cup,disc}_ece' and '{cup,disc}_brier' per image, and res['calibration']: the table summed over the
+                images ('rel' [2][bins][5]) with its pooled figures and reliability diagram (``metrics.calibration_from_table``)
+    mc_passes   T in 2..32: also T stochastic passes per batch (``mc_logits(image, T)`` -> [T,B,2,H,W] logits; default
+                ``model.mc_inference_logits``: running statistics, live dropout), ``ops.mc_uncertainty`` for the std over the passes of
+                sigmoid(x / 2), and in the SAME ``ops.selective_tables`` call the risk table of ``pred`` (the masks scored above) against
+                the labels per bin of that std (``unc_edges``).  Per image '{cup,disc}_unc_auroc' (do the errors sit where the std is
+                large?) and per edge e of ``report_edges`` (each one of ``unc_edges``; e as %g) '{cup,disc}_cov_<e>' (share of pixels with
+                std < e), '{cup,disc}_dice_<e>' and '{cup,disc}_err_<e>' (Dice and error rate over those pixels); res['risk_coverage']:
+                the table summed over the images ('risk' [2][K][4]) with its pooled figures (``metrics.selective_from_table``).
+                0 (the default) makes no pass and no call.
+    With any of the six set, per-image dicts and 'mean' carry the added names and the result lists them as 'extra_fields'.
 
     save_dir    a folder: per image also <save_dir>/overlay/<stem>.png (outlines of the display masks of ``prob``: disc green, cup blue,
                 ``Utils.save_per_img_batch``), original_image/<stem>.png and mask/<stem>.png (``pred``, the masks the figures above
-                were computed on: 0 = cup, 128 = disc only, 255 = background).  The returned result is the same with and without it;
-                None (the default) makes no further call."""
+                were computed on: 0 = cup, 128 = disc only, 255 = background).  The returned result is the same with and without it.
+                With ``mc_passes`` also uncertainty/<stem>.png, RGB (0, disc, cup) of min(255, floor(std * 1600)): the trainer's
+                threshold 0.04 is grey 64.  None (the default) makes no further call."""
     tolerances = tuple(float(t) for t in tolerances)
     profiled = extra_fields(hd95, tolerances, cdr)
-    extra = extra_fields(hd95, tolerances, cdr, morphometry)
+    mc_passes = int(mc_passes)
+    extra = extra_fields(hd95, tolerances, cdr, morphometry, calibration, mc_passes, report_edges)
+    if mc_passes:
+        _edge_index(unc_edges, report_edges)
+        if mc_logits is None:
+            mc_logits = getattr(model, "mc_inference_logits", None)
+        if mc_logits is None:
+            raise ValueError("mc_passes needs a model with mc_inference_logits (DeepLab) or an mc_logits callable")
+    pooled_rel = pooled_risk = None
     dev = torch.device("cuda") if torch.cuda.is_available() else None
     was_training = getattr(model, "training", False)
     if hasattr(model, "eval"):
@@ -134,10 +205,25 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
                     more.update(metrics.vertical_cdr_from_profile(profile))
                 if morphometry:
                     more.update(morphometry_columns(pred, target > 0.5, sectors))
+                unc = None
+                if mc_passes:
+                    unc = ops.mc_uncertainty(mc_logits(image, mc_passes), outputs=("std",),
+                                             u8_scale=UNCERTAINTY_U8_SCALE if save_dir is not None else None)
+                if calibration or mc_passes:                                         # both tables in one call, one copy
+                    tables = ops.selective_tables(prob if calibration else None, unc["std"] if mc_passes else None, pred, target > 0.5,
+                                                  bins=bins, edges=unc_edges)
+                    if calibration:
+                        more.update(calibration_columns(tables["rel"]))
+                        pooled_rel = tables["rel"].sum(0) + (0 if pooled_rel is None else pooled_rel)
+                    if mc_passes:
+                        more.update(uncertainty_columns(tables["risk"], unc_edges, report_edges))
+                        pooled_risk = tables["risk"].sum(0) + (0 if pooled_risk is None else pooled_risk)
                 names = _names(sample, dice.shape[0], len(per_image))
                 if save_dir is not None:
                     Utils.save_per_img_batch(image, save_dir, names, prob)
                     Utils.save_mask_batch(pred, save_dir, names)
+                    if mc_passes:
+                        Utils.save_uncertainty_batch(unc["std_u8"], save_dir, names)
                 for i, name in enumerate(names):
                     per_image.append({"img_name": name,
                                       "cup_dice": float(dice[i, 0]), "disc_dice": float(dice[i, 1]),
@@ -153,6 +239,11 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
            "n_undefined": {"cup": int(np.isnan(cols["cup_assd"]).sum()), "disc": int(np.isnan(cols["disc_assd"]).sum())}}
     if extra:
         res["extra_fields"] = extra
+    if calibration and pooled_rel is not None:
+        res["calibration"] = dict(_lists(metrics.calibration_from_table(pooled_rel)), rel=pooled_rel.tolist(), bins=int(bins))
+    if mc_passes and pooled_risk is not None:
+        res["risk_coverage"] = dict(_lists(metrics.selective_from_table(pooled_risk, unc_edges)), risk=pooled_risk.tolist(),
+                                    passes=mc_passes)
     return res
 
 
@@ -184,6 +275,10 @@ def build_parser():
     ap.add_argument("--cdr", action="store_true", help="vertical cup-to-disc ratio and its error")
     ap.add_argument("--morphometry", action="store_true", help="horizontal and area CDR, thinnest rim, rim per quadrant, cup offset")
     ap.add_argument("--sectors", type=int, default=72, metavar="K", help="sectors of the rim profile: a multiple of 8 in 8..360")
+    ap.add_argument("--calibration", action="store_true", help="ECE and Brier score per image, pooled reliability diagram")
+    ap.add_argument("--bins", type=int, default=15, metavar="N", help="confidence bins of the reliability diagram, 1..64")
+    ap.add_argument("--mc-passes", type=int, default=0, metavar="T",
+                    help="MC-dropout passes (2..32): uncertainty AUROC, coverage / Dice / error of the pixels with std < 0.04, risk-coverage table")
     ap.add_argument("--csv", default=None, metavar="PATH", help="one row per image")
     ap.add_argument("--json", default=None, metavar="PATH", help="the whole result")
     ap.add_argument("--save-dir", default=None, metavar="DIR", help="write overlay/, original_image/ and mask/ PNG files per image")
@@ -224,8 +319,8 @@ def load_generator(checkpoint, backbone="mobilenet", out_stride=16, use_TN=False
     return model.to(device) if device is not None else model
 
 
-def main(argv=None, model=None):
-    """The command line.  ``model``: a callable to score instead of the checkpoint's DeepLab (tests)."""
+def main(argv=None, model=None, mc_logits=None):
+    """The command line.  ``model``: a callable to score instead of the checkpoint's DeepLab, ``mc_logits``: its stochastic passes (tests)."""
     args = build_parser().parse_args(argv)
     from torch.utils.data import DataLoader
     from .dataloaders import custom_transforms as tr
@@ -240,7 +335,8 @@ def main(argv=None, model=None):
                                torch.device("cuda") if torch.cuda.is_available() else None)
     res = evaluate(model, loader, dataset=args.dataset, threshold=args.threshold, postprocess=not args.no_postprocess,
                    hd95=args.hd95, tolerances=tuple(args.tolerance), cdr=args.cdr, save_dir=args.save_dir,
-                   morphometry=args.morphometry, sectors=args.sectors)
+                   morphometry=args.morphometry, sectors=args.sectors, calibration=args.calibration, bins=args.bins,
+                   mc_passes=args.mc_passes, mc_logits=mc_logits)
     print(format_mean(res))
     if args.csv:
         write_csv(args.csv, res)

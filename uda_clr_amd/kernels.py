@@ -147,6 +147,8 @@ SYMBOLS = {
     "uda_surface_profile": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _U, _P]),
     "uda_disc_morphometry_workspace_bytes": (_U, [_I, _I, _I, _I]),
     "uda_disc_morphometry": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _U, _P]),
+    "uda_mc_uncertainty": (_I, [_P, _I, _L, _P, _P, _P, _P, _P, _F, _P]),
+    "uda_selective_tables": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _I, _P, _P, _P, _P]),
     "uda_normalize_tf_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_normalize_tf": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _U, _P]),
     "uda_field_smooth": (_I, [_P, _I, _I, _I, _P, _I, _D, _P, _P, _P]),
@@ -1362,6 +1364,62 @@ class HipKernels:
         self._ck(self.lib.uda_disc_morphometry(masks_u8.data_ptr(), B, H, W, sectors.data_ptr(), K, moments.data_ptr(), extent.data_ptr(),
                                                overlap.data_ptr(), radial.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         out = (moments, extent, overlap, radial)
+        return out + (packed,) if want_packed else out
+
+    def mc_uncertainty(self, logits, outputs=("mean", "std", "entropy", "mi"), u8_scale=None):
+        """f32 [T, ...] logits of T stochastic passes (2 <= T <= 32) -> {name: map of shape logits.shape[1:]} on the device, one read of
+        the logits (include/uda_clr_hip.h, uda_mc_uncertainty): 'mean' of sigmoid(x), 'std' = unbiased std of sigmoid(x / 2) (the
+        trainer's quantity), 'entropy' of the mean, 'mi' = entropy minus the mean entropy of the passes; with ``u8_scale`` also
+        'std_u8' = min(255, floor(std * u8_scale)) as uint8.  Only the maps named are computed and written."""
+        self._dev(logits)
+        names = ("mean", "std", "entropy", "mi")
+        outputs = tuple(outputs)
+        if any(o not in names for o in outputs) or not (outputs or u8_scale is not None):
+            raise ValueError("mc_uncertainty: outputs among %r (got %r)" % (names, outputs))
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() < 2:
+            raise ValueError("mc_uncertainty: contiguous float32 [T, ...] logits (got %s %s)" % (logits.dtype, tuple(logits.shape)))
+        T, shape = logits.shape[0], tuple(logits.shape[1:])
+        out = {o: torch.empty(shape, dtype=torch.float32, device=logits.device) for o in names if o in outputs}
+        if u8_scale is not None:
+            out["std_u8"] = torch.empty(shape, dtype=torch.uint8, device=logits.device)
+        self._ck(self.lib.uda_mc_uncertainty(logits.data_ptr(), T, logits[0].numel(), _ptr(out.get("mean")), _ptr(out.get("std")),
+                                             _ptr(out.get("entropy")), _ptr(out.get("mi")), _ptr(out.get("std_u8")),
+                                             0.0 if u8_scale is None else float(u8_scale), self._stream()))
+        return out
+
+    def selective_tables(self, prob, unc, pred_u8, gt_u8=None, bins=15, edges=(), want_packed=False):
+        """prob, unc f32 [B,2,H,W] (either None), pred, gt uint8 [B,2,H,W] (nonzero = set; gt None = pred), ``bins`` confidence bins,
+        ``edges`` K - 1 ascending host floats -> (rel i64 [B,2,bins,5] or None, risk i64 [B,2,K,4] or None, invalid i64 [B,2,2]) on the
+        device (include/uda_clr_hip.h, uda_selective_tables).  The three are views of one int64 buffer, handed back as a fourth value
+        with ``want_packed`` (one copy moves all)."""
+        masks = [pred_u8] + ([] if gt_u8 is None else [gt_u8])
+        for t in masks:
+            self._dev(t)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != 2:
+                raise ValueError("selective_tables: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (t.dtype, tuple(t.shape)))
+        for t in (prob, unc):
+            if t is not None:
+                self._dev(t)
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != pred_u8.shape:
+                    raise ValueError("selective_tables: contiguous float32 maps of the masks' shape (got %s %s)" % (t.dtype, tuple(t.shape)))
+        if gt_u8 is not None and gt_u8.shape != pred_u8.shape:
+            raise ValueError("selective_tables: shapes differ: %s and %s" % (tuple(pred_u8.shape), tuple(gt_u8.shape)))
+        if prob is None and unc is None:
+            raise ValueError("selective_tables: prob (reliability table), unc (risk table) or both")
+        B, _, H, W = pred_u8.shape
+        edges = [float(e) for e in edges]
+        M, K = int(bins), len(edges) + 1
+        sizes = (B * 2 * M * 5 if prob is not None else 0, B * 2 * K * 4 if unc is not None else 0, B * 4)
+        if not 1 <= M <= 64 or not K <= 64:
+            raise ValueError("selective_tables: 1..64 bins (got %d confidence, %d uncertainty)" % (M, K))
+        packed = torch.empty(sum(sizes), dtype=torch.int64, device=pred_u8.device)
+        rel, risk, invalid = torch.split(packed, sizes)
+        rel = rel.view(B, 2, M, 5) if prob is not None else None
+        risk = risk.view(B, 2, K, 4) if unc is not None else None
+        self._ck(self.lib.uda_selective_tables(_ptr(prob), _ptr(unc), pred_u8.data_ptr(), _ptr(gt_u8), B, H, W, M,
+                                               (C.c_float * max(len(edges), 1))(*edges), K, _ptr(rel), _ptr(risk), invalid.data_ptr(),
+                                               self._stream()))
+        out = (rel, risk, invalid.view(B, 2, 2))
         return out + (packed,) if want_packed else out
 
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):

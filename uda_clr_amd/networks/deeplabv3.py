@@ -230,6 +230,32 @@ class DeepLab(Holder):
                 outs.append(self(xr)[0])
         return torch.cat(outs, 0)
 
+    def mc_inference_logits(self, x, passes):
+        """[passes, N, 2, H, W] segmentation logits of ``passes`` no-grad forwards of ``x`` with the running statistics normalising
+        and dropout live: ``freeze_bn()`` under ``train()``, then ``mc_dropout_logits(x, passes, reps=1)`` - MC dropout on a trained
+        checkpoint, for ``ops.mc_uncertainty``.  Every pass is a whole forward.  The model is left as found: every module's
+        ``training`` flag, every buffer (frozen normalisation layers update none, ``num_batches_tracked`` included), the activations
+        kept for ``mc_dropout_logits`` and the position of the dropout stream - so the same call gives the same bits again, and
+        ``set_dropout_seed`` chooses them.  BatchNorm and TransNorm models alike: both kinds take their eval branch."""
+        flags = [(m, m.training) for m in self.modules()]
+        recent = self._recent
+        eng = self._engine_override or self._engine
+        offset = 0 if eng is None else eng.rng_offset
+        try:
+            for m, _ in flags:
+                m.training = True          # (not self.train(): that would drop the kept activations and the shared weight layouts)
+            self.freeze_bn()
+            self._recent = []              # a kept training forward replays batch statistics: not this call's
+            out = self.mc_dropout_logits(x, passes, reps=1)
+        finally:
+            for m, flag in flags:
+                m.training = flag
+            self._recent = recent
+            eng = self._engine_override or self._engine
+            if eng is not None:
+                eng.rng_offset = offset
+        return out.reshape((passes, x.shape[0]) + tuple(out.shape[1:]))
+
     def _flat_state(self):
         sd = {}
         for name, mod in (self._backbone_root(), ("aspp", self.aspp), ("decoder", self.decoder)):

@@ -516,3 +516,57 @@ def disc_morphometry(masks, sectors=72):
     moments, extent, overlap, radial = np.split(host, np.cumsum([B * 12, B * 8, B]))
     return {"moments": moments.reshape(B, 2, 6), "extent": extent.reshape(B, 2, 4), "overlap": overlap.reshape(B),
             "radial": radial.reshape(B, 2, K), "table": table}
+
+
+# uncertainty bins of the selective-prediction table: 0.04 is the trainer's trust threshold on the std of sigmoid(x / 2)
+# (reference utils/Utils.py:197-200)
+DEFAULT_UNC_EDGES = (0.005, 0.01, 0.02, 0.03, 0.04, 0.06, 0.08, 0.12, 0.16)
+
+
+def mc_uncertainty(logits, outputs=("mean", "std", "entropy", "mi"), u8_scale=None):
+    """[T,B,2,H,W] logits of T stochastic passes (2 <= T <= 32) -> {name: [B,2,H,W] device tensor} for the names in ``outputs``, one
+    read of the logits (uda_mc_uncertainty):
+        'mean'     mean over the passes of sigmoid(x)
+        'std'      unbiased std over the passes of sigmoid(x / 2): the quantity ``gen_prototype_retrify`` thresholds at 0.04
+        'entropy'  binary entropy of 'mean' in nats
+        'mi'       'entropy' minus the mean entropy of the passes (>= 0): the part of the entropy that the passes disagree about
+    and with ``u8_scale`` also 'std_u8' = min(255, floor(std * u8_scale)) as uint8, from the stored fp32 std.  A CPU tensor is moved
+    to the device."""
+    if logits.dim() < 2:
+        raise ValueError("expected [T, ...] logits, got %s" % (tuple(logits.shape),))
+    (logits,) = _to_device(logits)
+    return kernels().mc_uncertainty(logits.contiguous().float(), outputs, u8_scale)
+
+
+def selective_tables(prob, unc, pred, gt=None, bins=15, edges=DEFAULT_UNC_EDGES):
+    """The integer tables that calibration and selective-prediction figures are closed forms of, per image and class of a [B,2,H,W]
+    batch, on the host after ONE synchronising copy (uda_selective_tables):
+        prob   probabilities, or None (no reliability table)          unc    uncertainties >= 0, or None (no risk table)
+        pred   masks (uint8, bool or float; set means > 0.5)          gt     masks, or None: taken as ``pred``
+        bins   M confidence bins, 1..64                               edges  K - 1 ascending finite values, K <= 64
+    -> {'rel'     int64 [B,2,M,5]: per bin min(M - 1, floor(p * M)) (fp32): n, n with gt set, sum q, sum q over gt-set pixels, sum q^2,
+                  q = rint(p * 65536); None without ``prob``
+        'risk'    int64 [B,2,K,4]: per bin #{j: edges[j] <= u}: TP, FP, FN, TN of pred against gt; None without ``unc``
+        'invalid' int64 [B,2,2]: pixels with p NaN or outside [0, 1], pixels with u NaN or negative - left out of that table only
+        'edges'   float32 [K - 1]: the edges as the kernel compared them}
+    as numpy arrays (``utils.metrics.calibration_from_table`` / ``selective_from_table``).  CPU tensors are moved to the device."""
+    import numpy as np
+    e32 = np.asarray(list(edges), np.float32)
+    if not 1 <= int(bins) <= 64 or e32.size > 63:
+        raise ValueError("selective_tables: 1..64 bins (got %d confidence, %d uncertainty)" % (bins, e32.size + 1))
+    if not np.all(np.isfinite(e32)) or not np.all(e32[1:] > e32[:-1]):
+        raise ValueError("selective_tables: edges must be finite and strictly ascending as float32, got %r" % (tuple(edges),))
+    if prob is None and unc is None:
+        raise ValueError("selective_tables: prob (reliability table), unc (risk table) or both")
+    given = [t for t in (prob, unc, pred, gt) if t is not None]
+    moved = iter(_to_device(*given))
+    prob, unc, pred, gt = (None if t is None else next(moved) for t in (prob, unc, pred, gt))
+    f32 = lambda t: None if t is None else t.contiguous().float()
+    packed = kernels().selective_tables(f32(prob), f32(unc), _mask_u8(pred), None if gt is None else _mask_u8(gt), int(bins), e32.tolist(),
+                                        want_packed=True)[-1]
+    host = packed.cpu().numpy()                                                                          # the one copy (it synchronises)
+    B, M, K = pred.shape[0], int(bins), e32.size + 1
+    n_rel, n_risk = (B * 2 * M * 5 if prob is not None else 0), (B * 2 * K * 4 if unc is not None else 0)
+    rel, risk, invalid = np.split(host, [n_rel, n_rel + n_risk])
+    return {"rel": rel.reshape(B, 2, M, 5) if prob is not None else None, "risk": risk.reshape(B, 2, K, 4) if unc is not None else None,
+            "invalid": invalid.reshape(B, 2, 2), "edges": e32}

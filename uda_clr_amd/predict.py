@@ -12,10 +12,17 @@ An image whose height or width is not a multiple of 16 is refused by name: the g
 
     python -m uda_clr_amd.predict --images DIR --checkpoint FILE --out DIR [--backbone mobilenet] [--out-stride 16] [--use_TN]
                                   [--dataset Drishti-GS] [--threshold 0.75] [--batch-size 8] [--csv FILE] [--morphometry [--sectors 72]]
+                                  [--mc-passes 8]
 
 With ``--morphometry`` the CSV also carries, per image, hcdr_pred and acdr_pred (horizontal and area cup-to-disc ratio), rdr_min_pred and
 rim_{up,left,down,right}_pred (thinnest and per-quadrant rim-to-disc ratio), cup_offset_pred (pixels) and {cup,disc}_{major,minor,
 orientation} (ellipse axes in pixels, degrees counter-clockwise from "right"); without it the CSV is img_name, vcdr_pred.
+
+With ``--mc-passes T`` (2..32) every batch also runs T MC-dropout passes (``DeepLab.mc_inference_logits``: running statistics, live
+dropout) and ``ops.mc_uncertainty``: <out>/uncertainty/<stem>.png is RGB (0, disc, cup) of min(255, floor(std * 1600)) of the std over
+the passes of sigmoid(x / 2) - the quantity the trainer trusts a pseudo-label below 0.04 of, grey 64 here - and the CSV carries
+cup_unsure, disc_unsure (the share of the predicted structure's pixels with std >= 0.04, nan for an empty structure) and unsure_px
+(those pixels counted, cup plane plus disc plane).
 """
 import argparse
 import csv
@@ -27,7 +34,7 @@ import torch
 
 from . import ops
 from .engine import check_input_size
-from .evaluate import load_generator
+from .evaluate import UNCERTAINTY_U8_SCALE, load_generator
 from .utils import Utils, metrics
 
 EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
@@ -47,6 +54,8 @@ def build_parser():
     ap.add_argument("--csv", default=None, metavar="FILE", help="one row per image: img_name, vcdr_pred")
     ap.add_argument("--morphometry", action="store_true", help="the CSV also gets horizontal and area CDR, rim profile figures, cup offset, ellipse axes")
     ap.add_argument("--sectors", type=int, default=72, metavar="K", help="sectors of the rim profile: a multiple of 8 in 8..360")
+    ap.add_argument("--mc-passes", type=int, default=0, metavar="T",
+                    help="MC-dropout passes (2..32): writes uncertainty/ pictures, the CSV also gets cup_unsure, disc_unsure, unsure_px")
     return ap
 
 
@@ -100,13 +109,37 @@ def morphometry_columns(pred, sectors=72):
     return cols
 
 
-def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_size=8, morphometry=False, sectors=72):
+UNCERTAINTY_COLUMNS = ("cup_unsure", "disc_unsure", "unsure_px")
+UNSURE_STD = 0.04               # the trainer's trust threshold on the std of sigmoid(x / 2) (reference utils/Utils.py:197-200)
+
+
+def uncertainty_columns(unc, pred):
+    """{name: [B] float64} of UNCERTAINTY_COLUMNS for the [B,2,H,W] std map and predicted masks: one ``ops.selective_tables`` call with
+    the prediction as its own ground truth, so that the TP column counts the predicted structure's pixels per uncertainty bin"""
+    edges = ops.DEFAULT_UNC_EDGES
+    tp = ops.selective_tables(None, unc, pred, None, edges=edges)["risk"][..., 0]
+    first = [float(np.float32(e)) for e in edges].index(float(np.float32(UNSURE_STD))) + 1         # the first bin with std >= 0.04
+    unsure, n = tp[..., first:].sum(-1), tp.sum(-1)
+    share = metrics._ratio(unsure, n)
+    return {"cup_unsure": share[:, 0], "disc_unsure": share[:, 1], "unsure_px": unsure.sum(-1).astype(np.float64)}
+
+
+def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_size=8, morphometry=False, sectors=72, mc_passes=0,
+            mc_logits=None):
     """``images`` as ``read_images`` returns them -> [{'img_name', 'vcdr_pred'}] in batch order; writes the three folders.
     ``morphometry``: every row also carries MORPHOMETRY_COLUMNS (horizontal and area cup-to-disc ratio, the thinnest rim-to-disc ratio
     of ``sectors`` sectors and its quadrant means, the cup's decentration in pixels, full axes in pixels and orientation in degrees of
-    the ellipse with each structure's covariance), from one ``ops.disc_morphometry`` call per batch."""
+    the ellipse with each structure's covariance), from one ``ops.disc_morphometry`` call per batch.
+    ``mc_passes`` T in 2..32: per batch T stochastic passes (``mc_logits(x, T)`` -> [T,B,2,H,W] logits; default
+    ``model.mc_inference_logits``), ``ops.mc_uncertainty`` and one ``ops.selective_tables`` call; writes uncertainty/<stem>.png and
+    every row also carries UNCERTAINTY_COLUMNS.  0 (the default) makes no pass and no call."""
     if not torch.cuda.is_available():
         raise RuntimeError("uda_clr_amd computes only on the MI355X HIP kernels (there is no CPU fallback)")
+    mc_passes = int(mc_passes)
+    if mc_passes and mc_logits is None:
+        mc_logits = getattr(model, "mc_inference_logits", None)
+        if mc_logits is None:
+            raise ValueError("mc_passes needs a model with mc_inference_logits (DeepLab) or an mc_logits callable")
     dev = torch.device("cuda")
     was_training = getattr(model, "training", False)
     if hasattr(model, "eval"):
@@ -132,6 +165,12 @@ def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_
                     cols = morphometry_columns(pred, sectors)
                     for i in range(len(names)):
                         rows[first + i].update({k: float(cols[k][i]) for k in MORPHOMETRY_COLUMNS})
+                if mc_passes:
+                    unc = ops.mc_uncertainty(mc_logits(x, mc_passes), outputs=("std",), u8_scale=UNCERTAINTY_U8_SCALE)
+                    Utils.save_uncertainty_batch(unc["std_u8"], out_dir, names)
+                    cols = uncertainty_columns(unc["std"], pred)
+                    for i in range(len(names)):
+                        rows[first + i].update({k: float(cols[k][i]) for k in UNCERTAINTY_COLUMNS})
     finally:
         if was_training and hasattr(model, "train"):
             model.train()
@@ -139,8 +178,9 @@ def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_
 
 
 def write_csv(path, rows):
-    """img_name, vcdr_pred, and MORPHOMETRY_COLUMNS where the rows carry them"""
+    """img_name, vcdr_pred, and MORPHOMETRY_COLUMNS and UNCERTAINTY_COLUMNS where the rows carry them"""
     more = MORPHOMETRY_COLUMNS if rows and MORPHOMETRY_COLUMNS[0] in rows[0] else ()
+    more += UNCERTAINTY_COLUMNS if rows and UNCERTAINTY_COLUMNS[0] in rows[0] else ()
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(("img_name", "vcdr_pred") + more)
@@ -148,8 +188,8 @@ def write_csv(path, rows):
             w.writerow([r["img_name"], repr(r["vcdr_pred"])] + [repr(r[k]) for k in more])
 
 
-def main(argv=None, model=None):
-    """The command line.  ``model``: a callable to run instead of the checkpoint's DeepLab (tests)."""
+def main(argv=None, model=None, mc_logits=None):
+    """The command line.  ``model``: a callable to run instead of the checkpoint's DeepLab, ``mc_logits``: its stochastic passes (tests)."""
     args = build_parser().parse_args(argv)
     images = read_images(args.images, list_images(args.images))
     if model is None:
@@ -158,7 +198,7 @@ def main(argv=None, model=None):
         model = load_generator(args.checkpoint, args.backbone, args.out_stride, args.use_TN,
                                torch.device("cuda") if torch.cuda.is_available() else None)
     rows = predict(model, images, args.out, dataset=args.dataset, threshold=args.threshold, batch_size=args.batch_size,
-                   morphometry=args.morphometry, sectors=args.sectors)
+                   morphometry=args.morphometry, sectors=args.sectors, mc_passes=args.mc_passes, mc_logits=mc_logits)
     print("%d images -> %s" % (len(rows), args.out))
     if args.csv:
         write_csv(args.csv, rows)

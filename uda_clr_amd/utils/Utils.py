@@ -120,6 +120,14 @@ def save_mask_batch(pred, out_dir, names):
     return [_save_png(grey[i], os.path.join(out_dir, 'mask'), name) for i, name in enumerate(names)]
 
 
+def save_uncertainty_batch(std_u8, out_dir, names):
+    """``<out_dir>/uncertainty/<stem>.png`` per image: RGB (0, disc, cup) of the uint8 [B,2,H,W] (cup, disc) quantised MC-dropout std
+    (``ops.mc_uncertainty(..., u8_scale=...)['std_u8']``).  One copy of 3 B per pixel.  Returns the paths."""
+    import torch
+    rgb = torch.stack([torch.zeros_like(std_u8[:, 0]), std_u8[:, 1], std_u8[:, 0]], -1).cpu().numpy()
+    return [_save_png(rgb[i], os.path.join(out_dir, 'uncertainty'), name) for i, name in enumerate(names)]
+
+
 def save_per_img(patch_image, data_save_path, img_name, prob_map, mask_path=None, ext="bmp"):
     """``<data_save_path>/original_image/<stem>.png`` and ``<data_save_path>/overlay/<stem>.png`` of ONE image, as
     utils/Utils.py:515-585: ``patch_image`` [H, W, 3] in 0..255 (cast to uint8 by truncation, as there), ``prob_map`` [2, H, W]

@@ -225,3 +225,69 @@ def hd95_2label(pred_mask, gt_mask):
     table, _, profile = ops.surface_profile(pred_mask, gt_mask, percentiles=(95,))
     h = percentile_distance_from_profile(table, profile)["hd_p"][..., 0]
     return h[:, 0], h[:, 1]
+
+
+# ---- calibration and selective prediction: closed forms, in float64, of the integer tables of ops.selective_tables
+Q_ONE = 65536                # q = rint(p * Q_ONE): the fixed-point probability of the reliability table
+
+
+def _ratio(num, den):
+    """num / den in float64, NaN where den is 0"""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den != 0, num / np.where(den != 0, den, 1.0), np.nan)
+
+
+def calibration_from_table(rel):
+    """int64 [..., M, 5] reliability table (n, n_pos, sum q, sum q over gt-set pixels, sum q^2 per confidence bin; per (image, class),
+    or summed over images for pooled figures) -> {
+        'ece'         [...]  sum_b |n_pos - sum q / 65536| / sum n: the bins' |accuracy - confidence| weighted by their share
+        'mce'         [...]  the largest |accuracy - confidence| of a bin that holds a pixel
+        'brier'       [...]  mean (p - y)^2 = (sum q^2 - 2 * 65536 * sum q_pos + 65536^2 * n_pos) / (65536^2 * n), of the rounded p
+        'confidence'  [...]  mean p            'prevalence'  [...]  share of gt-set pixels
+        'bin_n' int64, 'bin_accuracy', 'bin_confidence'  [..., M]: the reliability diagram; NaN for an empty bin}
+    NaN throughout for a table without a pixel."""
+    rel = np.asarray(rel, np.int64)
+    n, n_pos, q, q_pos, qq = (rel[..., i] for i in range(5))
+    N = n.sum(-1)
+    gap = np.abs(n_pos.astype(np.float64) - q.astype(np.float64) / Q_ONE)
+    acc, conf = _ratio(n_pos, n), _ratio(q, n.astype(np.float64) * Q_ONE)
+    with np.errstate(invalid="ignore"):
+        mce = np.where(N > 0, np.max(np.where(n > 0, gap / np.maximum(n, 1), -np.inf), -1), np.nan)     # |acc - conf| without its cancellation
+    num = qq.sum(-1) - 2 * Q_ONE * q_pos.sum(-1) + Q_ONE * Q_ONE * n_pos.sum(-1)                # an exact integer
+    return {"ece": _ratio(gap.sum(-1), N), "mce": mce, "brier": _ratio(num, N.astype(np.float64) * (Q_ONE * Q_ONE)),
+            "confidence": _ratio(q.sum(-1), N.astype(np.float64) * Q_ONE), "prevalence": _ratio(n_pos.sum(-1), N),
+            "bin_n": n, "bin_accuracy": acc, "bin_confidence": conf}
+
+
+def selective_from_table(risk, edges):
+    """int64 [..., K, 4] risk table ((TP, FP, FN, TN) per uncertainty bin; per (image, class), or summed over images) and its K - 1
+    edges -> per edge e_j, keeping the pixels with u < e_j (bins 0..j):
+        'coverage' [..., K-1]  kept / all           'dice'   [..., K-1]  (2 TP + 1) / (2 TP + FP + FN + 1) over the kept pixels
+        'error'    [..., K-1]  (FP + FN) / kept, NaN where nothing is kept
+    and 'error_all' [...] the error rate of all pixels,
+        'aurc'      [...] area under the binned risk-coverage curve: the points (coverage, error) of the K prefixes bins 0..j, joined by
+                    trapezoids, the stretch from coverage 0 to the first point that keeps a pixel at that point's error
+        'unc_auroc' [...] probability that a wrong pixel is more uncertain than a right one, ties counted half (Mann-Whitney), from
+                    the two histograms: a pair inside one bin is a tie.  NaN when there is no wrong or no right pixel
+        'edges' as given."""
+    risk = np.asarray(risk, np.int64)
+    edges = np.asarray(edges, np.float64)
+    K = risk.shape[-2]
+    if edges.shape != (K - 1,):
+        raise ValueError("selective_from_table: %d bins need %d edges, got %s" % (K, K - 1, edges.shape))
+    cum = np.cumsum(risk, -2)                                                # prefix j = bins 0..j
+    tp, fp, fn, tn = (cum[..., i] for i in range(4))
+    kept, total = tp + fp + fn + tn, risk.sum((-1, -2))
+    wrong_k, right_k = risk[..., 1] + risk[..., 2], risk[..., 0] + risk[..., 3]
+    cover, err = _ratio(kept, total[..., None]), _ratio(fp + fn, kept)
+    # trapezoids over the K prefixes; a prefix that keeps nothing has zero width and takes the first defined error
+    first = np.argmax(kept > 0, -1)
+    e = np.where(kept > 0, err, np.take_along_axis(err, first[..., None], -1))
+    aurc = cover[..., 0] * e[..., 0] + ((cover[..., 1:] - cover[..., :-1]) * (e[..., 1:] + e[..., :-1]) / 2).sum(-1)
+    below = np.cumsum(right_k, -1) - right_k                                # right pixels in lower bins
+    two_u = (wrong_k * (2 * below + right_k)).sum(-1)
+    W, R = wrong_k.sum(-1), right_k.sum(-1)
+    return {"coverage": cover[..., :-1], "dice": _ratio(2 * tp + 1, 2 * tp + fp + fn + 1)[..., :-1], "error": err[..., :-1],
+            "error_all": _ratio(W, total), "aurc": np.where(total > 0, aurc, np.nan),
+            "unc_auroc": _ratio(two_u, 2.0 * W.astype(np.float64) * R.astype(np.float64)), "edges": edges}
