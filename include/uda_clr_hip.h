@@ -578,6 +578,45 @@ int uda_geometry_u8(const uint8_t* image_pool, const uint8_t* label_pool, const 
                     const int64_t* src_index, const int* records, int B, int S, uint8_t* image_out, uint8_t* label_out,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- whole-photograph prediction (uda_clr_amd/wholephoto.py): from a fundus photograph of any size to the S x S ROI the
+ * generator takes, and back.  The reference reads ROIs that were cut beforehand (dataloaders/fundus_dataloader.py:41 `ROIs/image`) and
+ * ships no such stage: every definition here is this project's, except the ROI resample, which is Pillow's.
+ *   pool uint8: the photographs' [H,W,3] images back to back, pool_pixels pixels in all; offsets int64 [n_sources]: first PIXEL of each;
+ *   sizes int32 [n_sources,2] = (H, W), 1 <= H, W <= 8192; src_index int64 [B]: the photographs of this batch.  1 <= B <= 8192; S a
+ *   multiple of 16 in 16..1024.  A source index outside [0, n_sources), or a table row that does not describe H x W pixels inside the
+ *   pool, counts as "no photograph".  Nothing outside [pool, pool + 3 * pool_pixels) is read.
+ *   Normalised outputs: f32 = fl(fl((float)v * fl(1 / 127.5f)) - 1.0f), product and difference each rounded to fp32, no fma: the bits of
+ *   torch's `u8.float() / 127.5 - 1.0` on the device (a product with the rounded reciprocal - for 126 of the 256 byte values not the
+ *   correctly rounded quotient that uda_normalize_tf stores).
+ *   No allocations, no workspace, no atomics; integers up to that last conversion: bit-identical from run to run, an image's output the
+ *   same alone and inside any batch.  A null pointer, B or S out of range returns the error before the launch and writes nothing.
+ * uda_photo_reduce_u8: the coarse canvas.  f = max(1, ceil(max(H, W) / S)), h = ceil(H / f), w = ceil(W / f); canvas pixel (r, c), r < h,
+ *   c < w, is per channel (sum + cnt / 2) / cnt in integers over rows [r f, min(H, (r + 1) f)) x columns [c f, min(W, (c + 1) f)), cnt the
+ *   pixels of that block; the rest of the S x S canvas is 0.  -> canvas_u8 uint8 [B,S,S,3], canvas_f32 f32 [B,3,S,S] (normalised as
+ *   above: -1 where the canvas is 0), either may be null, not both; factor int32 [B] = f.  Every byte is written exactly once.  No
+ *   photograph: an all-zero canvas and factor 0.
+ * uda_roi_cut_u8: boxes int32 [B,3] = (x0, y0, R), the R x R window with top-left (x0, y0) in photograph coordinates, any part of which
+ *   may lie outside the photograph and reads as 0; 8 <= R <= 2.5 S (at most 5 taps per axis, as uda_geometry_u8).  -> roi_u8 uint8
+ *   [B,S,S,3] = byte for byte Pillow's im.crop((x0, y0, x0 + R, y0 + R)).resize((S, S), Image.BILINEAR) (the 8-bit triangle filter with
+ *   its 22-bit integer weights, horizontal pass, then vertical pass over its uint8 result, R = S a plain copy), roi_f32 f32 [B,3,S,S]
+ *   normalised as above; either may be null, not both.  Only the rows and columns the window needs are read (to 16-byte words).  The
+ *   boxes are device memory and are not checked by the entry: no photograph, an R outside 8..2.5 S or |x0|, |y0| > 2^20 give an
+ *   all-zero ROI (callers with the boxes on the host check them there).
+ * uda_roi_paste_u8: masks uint8 [B,2,S,S] (cup, disc; nonzero = set; never written), boxes as above, sizes int32 [B,2] = (H, W) of THIS
+ *   batch's photographs, out_offsets int64 [B]: first byte of each photograph's [H,W] grey mask in out (out_bytes bytes in all).  BEAL
+ *   coding, that of utils.Utils.save_mask_batch: 0 = cup (also where the disc is not set), 128 = disc only, 255 = background; a pixel
+ *   outside the window is 255.  Window pixel (i, j), 0 <= i, j < R, takes each plane's bilinear upsample (half-pixel centres, edge clamp)
+ *   of the 0/1 mask, exactly: per axis with D = 2 R, a = clamp((2 i + 1) S - R, 0, (S - 1) D), i0 = a / D, fa = a - i0 D, i1 = min(i0 + 1,
+ *   S - 1), weights (D - fa, fa); v = sum over the 2 x 2 neighbours of m wy wx <= D^2 < 2^25; the plane is set iff 2 v > D^2 (a tie is
+ *   not set).  Every byte of each [H,W] mask is written exactly once and nothing else; a row of sizes / out_offsets that does not lie
+ *   inside out writes nothing; a box that uda_roi_cut_u8 would not take gives an all-255 mask. */
+int uda_photo_reduce_u8(const uint8_t* pool, int64_t pool_pixels, const int64_t* offsets, const int* sizes, int n_sources,
+                        const int64_t* src_index, int B, int S, uint8_t* canvas_u8, float* canvas_f32, int* factor, void* stream);
+int uda_roi_cut_u8(const uint8_t* pool, int64_t pool_pixels, const int64_t* offsets, const int* sizes, int n_sources,
+                   const int64_t* src_index, const int* boxes, int B, int S, uint8_t* roi_u8, float* roi_f32, void* stream);
+int uda_roi_paste_u8(const uint8_t* masks, const int* boxes, const int* sizes, const int64_t* out_offsets, int B, int S, uint8_t* out,
+                     int64_t out_bytes, void* stream);
+
 /* Trainer_prototype_full.py:335-355, 378-398 (EMA of the eight centroids, gradient through the current term only) + :428-444
  * (intra = sum_k MSE(src_k, tgt_k), inter = MSE(src_1, src_3) + MSE(src_0, src_2)) on two [4][C] centroid matrices in one
  * launch: new = prev ? keep * prev + decay * cur : cur (keep = 1 - decay as the caller's double expression rounds it);

@@ -21,23 +21,11 @@
 // scaled sample it runs the horizontal pass for the source rows its vertical taps need (<= ~70 rows at scale 0.5; the tile's 2 x 32 table entries are staged in LDS too) into LDS as
 // uint8 and the vertical pass from LDS; an unscaled sample is a plain gather.  Byte-load bound: at most the source window (4x
 // the crop at scale 0.5) plus 4 B per output pixel.
-#include "common.h"
-
-// the tables must see the doubles Pillow's C loops see (no fused multiply-add there)
-#pragma clang fp contract(off)
+#include "pil_resample.h"        // GeoEntry, geo_bilinear_entry, geo_clip8: the coefficient code shared with wholephoto.hip
 
 #define GEO_R 10              // record length, dataloaders.custom_transforms.GEOM_*
-#define GEO_TAPS 5            // in / out <= 2.5: at most 5 taps per axis (the transform scales by >= 0.5)
 #define GEO_T 32              // tile side
 #define GEO_ROWS 88           // source rows a tile's vertical taps can span: 31 * 2.5 + 1 + taps = 84 at in / out = 2.5, with room
-#define GEO_PREC 22
-
-struct GeoEntry {             // one position of the crop window along one axis
-    int x0;                   // first source index of the taps; -1: outside the scaled image (fill)
-    int n;                    // number of taps
-    int k[GEO_TAPS];          // integer weights, 0 past the last tap
-    int nn;                   // source index of the NEAREST resize
-};
 
 // grid (B, 2): axis 0 = columns (x), axis 1 = rows (y)
 __global__ __launch_bounds__(256) void geometry_tables_kernel(const int* __restrict__ sizes, int n_sources,
@@ -55,45 +43,16 @@ __global__ __launch_bounds__(256) void geometry_tables_kernel(const int* __restr
         for (int c = threadIdx.x; c < S; c += 256) { T[c].x0 = -1; T[c].n = 0; T[c].nn = 0; }
         return;
     }
-    const double scale = (double)n_in / (double)n_out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * fs, ss = 1.0 / fs;
     for (int c = threadIdx.x; c < S; c += 256) {
         GeoEntry e;
         const int xx = first + c;
-#pragma unroll
-        for (int t = 0; t < GEO_TAPS; ++t) e.k[t] = 0;
-        e.n = 0;
         if (xx < 0 || xx >= n_out) {
+#pragma unroll
+            for (int t = 0; t < GEO_TAPS; ++t) e.k[t] = 0;
             e.x0 = -1;
-        } else if (n_in == n_out) {
-            e.x0 = xx;
-            e.n = 1;
-            e.k[0] = 1 << GEO_PREC;
+            e.n = 0;
         } else {
-            const double center = ((double)xx + 0.5) * scale;
-            int xmin = (int)(center - support + 0.5);
-            if (xmin < 0) xmin = 0;
-            int xmax = (int)(center + support + 0.5);
-            if (xmax > n_in) xmax = n_in;
-            int n = xmax - xmin;
-            if (n > GEO_TAPS) n = GEO_TAPS;                     // cannot happen for in / out <= 2.5; keeps a bad record in bounds
-            if (n < 0) n = 0;
-            double w[GEO_TAPS], ww = 0.0;
-#pragma unroll
-            for (int t = 0; t < GEO_TAPS; ++t) {
-                double a = ((double)(t + xmin) - center + 0.5) * ss;
-                if (a < 0.0) a = -a;
-                w[t] = (t < n && a < 1.0) ? 1.0 - a : 0.0;
-                if (t < n) ww += w[t];
-            }
-#pragma unroll
-            for (int t = 0; t < GEO_TAPS; ++t) {
-                const double q = ww != 0.0 ? w[t] / ww : w[t];
-                e.k[t] = t < n ? (int)(0.5 + q * (double)(1 << GEO_PREC)) : 0;
-            }
-            e.x0 = xmin;
-            e.n = n;
+            geo_bilinear_entry(xx, n_in, n_out, e);
         }
         T[c].x0 = e.x0;
         T[c].n = e.n;
@@ -127,11 +86,6 @@ __device__ __forceinline__ void geo_crop_of(int oy, int ox, int S, int turns, in
         case 3: cy = S - 1 - ox; cx = oy; break;               // rot90(a, 3)[i][j] = a[S-1-j][i]
         default: cy = oy; cx = ox; break;
     }
-}
-
-__device__ __forceinline__ int geo_clip8(int acc) {
-    const int v = acc >> GEO_PREC;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
 __global__ __launch_bounds__(256) void geometry_kernel(const uint8_t* __restrict__ image_pool, const uint8_t* __restrict__ label_pool,

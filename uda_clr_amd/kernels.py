@@ -156,6 +156,9 @@ SYMBOLS = {
     "uda_photometric_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
     "uda_geometry_u8_workspace_bytes": (_U, [_I, _I]),
     "uda_geometry_u8": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _U, _P]),
+    "uda_photo_reduce_u8": (_I, [_P, _L, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "uda_roi_cut_u8": (_I, [_P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "uda_roi_paste_u8": (_I, [_P, _P, _P, _P, _I, _I, _P, _L, _P]),
 }
 
 
@@ -1212,6 +1215,79 @@ class HipKernels:
                                           src_index.data_ptr(), records.data_ptr(), B, S, io.data_ptr(), lo.data_ptr(),
                                           ws.data_ptr(), ws.numel(), self._stream()))
         return io, lo
+
+    # ------------------------------------------------------------------ whole photographs (csrc/wholephoto.hip)
+    @staticmethod
+    def _ck_photos(pool, offsets, sizes, src_index, S):
+        """the pool tables of uda_photo_reduce_u8 / uda_roi_cut_u8 -> (n_sources, B)"""
+        if not pool.is_cuda or pool.dtype != torch.uint8 or not pool.is_contiguous() or pool.dim() != 1 or pool.numel() % 3:
+            raise ValueError("a photograph pool is a flat contiguous uint8 device tensor of [H,W,3] images (got %s %s)" % (pool.dtype, tuple(pool.shape)))
+        for t in (offsets, sizes, src_index):
+            if not t.is_cuda or not t.is_contiguous():
+                raise UdaError("HIP kernels need contiguous device tensors; there is no CPU fallback")
+        n, B = offsets.numel(), src_index.numel()
+        if offsets.dtype != torch.int64 or src_index.dtype != torch.int64 or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2):
+            raise ValueError("offsets int64 [n], sizes int32 [n, 2], src_index int64 [B]")
+        if S % 16 or not 16 <= S <= 1024:
+            raise ValueError("size must be a multiple of 16 in 16..1024, got %d" % S)
+        if not 1 <= B <= 8192:
+            raise ValueError("batch of %d photographs outside 1..8192" % B)
+        return n, B
+
+    def photo_reduce(self, pool, offsets, sizes, src_index, S, outputs=("f32",)):
+        """the coarse S x S canvas of every selected photograph (uda_photo_reduce_u8) -> {'u8': uint8 [B,S,S,3], 'f32': f32 [B,3,S,S]}
+        for the names in ``outputs``, and 'factor': int32 [B]"""
+        n, B = self._ck_photos(pool, offsets, sizes, src_index, S)
+        if not outputs or set(outputs) - {"u8", "f32"}:
+            raise ValueError("outputs: 'u8', 'f32' or both, got %r" % (outputs,))
+        u8 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=pool.device) if "u8" in outputs else None
+        f32 = torch.empty(B, 3, S, S, dtype=torch.float32, device=pool.device) if "f32" in outputs else None
+        factor = torch.empty(B, dtype=torch.int32, device=pool.device)
+        self._ck(self.lib.uda_photo_reduce_u8(pool.data_ptr(), pool.numel() // 3, offsets.data_ptr(), sizes.data_ptr(), n, src_index.data_ptr(),
+                                              B, S, _ptr(u8), _ptr(f32), factor.data_ptr(), self._stream()))
+        out = {"factor": factor}
+        if u8 is not None:
+            out["u8"] = u8
+        if f32 is not None:
+            out["f32"] = f32
+        return out
+
+    def roi_cut(self, pool, offsets, sizes, src_index, boxes, S, outputs=("u8", "f32")):
+        """Pillow's crop(box).resize((S, S), BILINEAR) of every selected photograph (uda_roi_cut_u8); boxes int32 [B,3] = (x0, y0, R) on
+        the device -> {'u8': uint8 [B,S,S,3], 'f32': f32 [B,3,S,S]} for the names in ``outputs``"""
+        n, B = self._ck_photos(pool, offsets, sizes, src_index, S)
+        if not outputs or set(outputs) - {"u8", "f32"}:
+            raise ValueError("outputs: 'u8', 'f32' or both, got %r" % (outputs,))
+        if not boxes.is_cuda or boxes.dtype != torch.int32 or not boxes.is_contiguous() or tuple(boxes.shape) != (B, 3):
+            raise ValueError("boxes: contiguous int32 [%d, 3] on the device (got %s %s)" % (B, boxes.dtype, tuple(boxes.shape)))
+        u8 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=pool.device) if "u8" in outputs else None
+        f32 = torch.empty(B, 3, S, S, dtype=torch.float32, device=pool.device) if "f32" in outputs else None
+        self._ck(self.lib.uda_roi_cut_u8(pool.data_ptr(), pool.numel() // 3, offsets.data_ptr(), sizes.data_ptr(), n, src_index.data_ptr(),
+                                         boxes.data_ptr(), B, S, _ptr(u8), _ptr(f32), self._stream()))
+        out = {}
+        if u8 is not None:
+            out["u8"] = u8
+        if f32 is not None:
+            out["f32"] = f32
+        return out
+
+    def roi_paste(self, masks_u8, boxes, sizes, out_offsets, out_bytes):
+        """uint8 [B,2,S,S] masks, boxes int32 [B,3], sizes int32 [B,2] = (H, W), out_offsets int64 [B], all on the device -> one flat
+        uint8 [out_bytes] buffer holding every photograph's [H,W] grey mask (0 cup, 128 disc only, 255 background; uda_roi_paste_u8).
+        The buffer is not pre-filled: the offsets must tile it, as ``ops.roi_paste`` lays them out."""
+        self._dev(masks_u8)
+        if masks_u8.dtype != torch.uint8 or not masks_u8.is_contiguous() or masks_u8.dim() != 4 or masks_u8.shape[1] != 2 or masks_u8.shape[2] != masks_u8.shape[3]:
+            raise ValueError("roi_paste: contiguous uint8 [B, 2, S, S] masks (got %s %s)" % (masks_u8.dtype, tuple(masks_u8.shape)))
+        B, S = masks_u8.shape[0], masks_u8.shape[2]
+        for t, dt, shape in ((boxes, torch.int32, (B, 3)), (sizes, torch.int32, (B, 2)), (out_offsets, torch.int64, (B,))):
+            if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError("roi_paste: contiguous %s %s on the device (got %s %s)" % (dt, list(shape), t.dtype, tuple(t.shape)))
+        if S % 16 or not 16 <= S <= 1024:
+            raise ValueError("size must be a multiple of 16 in 16..1024, got %d" % S)
+        out = torch.empty(int(out_bytes), dtype=torch.uint8, device=masks_u8.device)
+        self._ck(self.lib.uda_roi_paste_u8(masks_u8.data_ptr(), boxes.data_ptr(), sizes.data_ptr(), out_offsets.data_ptr(), B, S, out.data_ptr(),
+                                           out.numel(), self._stream()))
+        return out
 
     def postprocess(self, pred, thr_cup, thr_disc, sweeps=None):
         """pred f32 [B,2,H,W] probabilities -> uint8 [B,2,H,W] masks after the reference's evaluation post-processing.

@@ -329,6 +329,105 @@ def geometry_u8(pool, src_index, records, size=None):
                                  src_index.to(dev).to(torch.int64).contiguous(), records.to(dev).to(torch.int32).contiguous(), S)
 
 
+class PhotoPool(object):
+    """Fundus photographs of any sizes resident on the device for ``photo_reduce`` / ``roi_cut`` / ``roi_paste``: every [H,W,3]
+    uint8 image in one flat buffer, an int64 table of first pixels and an int32 (H, W) table (``SourcePool`` without the masks).
+    3 B per pixel: one upload per batch of photographs."""
+    MAX_SIDE = 8192
+
+    def __init__(self, images, device):
+        import numpy as np
+        imgs = [np.ascontiguousarray(np.asarray(i, dtype=np.uint8)) for i in images]
+        if not imgs:
+            raise ValueError("PhotoPool needs at least one photograph")
+        for i in imgs:
+            if i.ndim != 3 or i.shape[2] != 3 or not (1 <= i.shape[0] <= self.MAX_SIDE and 1 <= i.shape[1] <= self.MAX_SIDE):
+                raise ValueError("PhotoPool: photographs are [H,W,3] with 1 <= H, W <= %d (got %s)" % (self.MAX_SIDE, i.shape))
+        self.sizes_host = np.array([i.shape[:2] for i in imgs], np.int32)
+        px = self.sizes_host[:, 0].astype(np.int64) * self.sizes_host[:, 1]
+        self.pool = torch.from_numpy(np.concatenate([i.reshape(-1) for i in imgs])).to(device)
+        self.offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(px)[:-1]]).astype(np.int64)).to(device)
+        self.sizes = torch.from_numpy(self.sizes_host).to(device)
+
+    def __len__(self):
+        return int(self.sizes_host.shape[0])
+
+
+def _photo_index(pool, index, who, allow_outside=False):
+    """``index`` (None = every photograph in order) as int64 on the pool's device; a host-resident index is range-checked"""
+    dev = pool.pool.device
+    if index is None:
+        return torch.arange(len(pool), dtype=torch.int64, device=dev)
+    index = torch.as_tensor(index).reshape(-1)
+    if not index.is_cuda and not allow_outside and index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(pool)):
+        raise ValueError("%s: photograph index outside the pool of %d" % (who, len(pool)))
+    return index.to(dev).to(torch.int64).contiguous()
+
+
+def _check_boxes(boxes, B, size, who):
+    """boxes [B,3] = (x0, y0, R) as contiguous int32; host-resident ones are range-checked (the kernels only keep a bad one in bounds)"""
+    boxes = torch.as_tensor(boxes)
+    if boxes.dim() != 2 or tuple(boxes.shape) != (B, 3):
+        raise ValueError("%s: boxes are [%d, 3] = (x0, y0, R), got %s" % (who, B, tuple(boxes.shape)))
+    if not boxes.is_cuda:
+        r = boxes[:, 2]
+        if int(r.min()) < 8 or 2 * int(r.max()) > 5 * size:
+            raise ValueError("%s: window side R must lie in 8..2.5 * size = %d (got %d..%d)" % (who, 5 * size // 2, int(r.min()), int(r.max())))
+        if int(boxes[:, :2].abs().max()) > 2 ** 20:
+            raise ValueError("%s: window origin beyond +-2^20" % who)
+    return boxes.to(torch.int32).contiguous()
+
+
+def photo_reduce(pool, index=None, size=512, outputs=("f32",)):
+    """The coarse canvas of whole photographs (uda_photo_reduce_u8): every photograph of ``pool`` (a PhotoPool) selected by ``index``
+    is reduced by the integer factor f = max(1, ceil(max(H, W) / size)) - block means, rounded half up in integers, edge blocks partial
+    - into the top-left of a size x size canvas, 0 elsewhere.  -> {'u8': uint8 [B,size,size,3], 'f32': f32 [B,3,size,size] (the bytes
+    normalised as ``predict`` normalises an image, so -1 where the canvas is 0)} for the names in ``outputs``, and 'factor': int32 [B],
+    all on the device.  An index outside the pool (possible only for a device-resident index) gives a zero canvas and factor 0."""
+    return kernels().photo_reduce(pool.pool, pool.offsets, pool.sizes, _photo_index(pool, index, "photo_reduce"), int(size), tuple(outputs))
+
+
+def roi_cut(pool, boxes, index=None, size=512, outputs=("u8", "f32")):
+    """The ROI of whole photographs (uda_roi_cut_u8): for photograph ``index[b]`` of ``pool`` and ``boxes[b]`` = (x0, y0, R), byte for byte
+    Pillow's ``im.crop((x0, y0, x0 + R, y0 + R)).resize((size, size), Image.BILINEAR)``; the window may hang over the photograph and
+    reads as 0 there; 8 <= R <= 2.5 * size.  -> {'u8': uint8 [B,size,size,3], 'f32': f32 [B,3,size,size] normalised as ``predict``
+    normalises an image} for the names in ``outputs``, on the device.  Host-resident boxes are range-checked here."""
+    idx = _photo_index(pool, index, "roi_cut")
+    boxes = _check_boxes(boxes, idx.numel(), int(size), "roi_cut")
+    return kernels().roi_cut(pool.pool, pool.offsets, pool.sizes, idx, boxes.to(pool.pool.device), int(size), tuple(outputs))
+
+
+def roi_paste(pool_or_sizes, masks, boxes, index=None):
+    """ROI masks back into photograph-sized grey masks (uda_roi_paste_u8): ``masks`` [B,2,S,S] (cup, disc; uint8, bool or float, set
+    means > 0.5) for the windows ``boxes`` [B,3] = (x0, y0, R) of photographs whose sizes are ``pool_or_sizes``: a PhotoPool (with
+    ``index`` selecting B of its photographs, None = all) or a host [B,2] array of (H, W).  -> a list of B uint8 [H,W] views into one flat
+    device buffer, BEAL coding (0 cup, 128 disc only, 255 background and everything outside the window): each plane is the bilinear
+    upsample (half-pixel centres, edge clamp) of the 0/1 mask thresholded at > 1/2 in exact integers, a tie not set."""
+    import numpy as np
+    if isinstance(pool_or_sizes, PhotoPool):
+        hw = pool_or_sizes.sizes_host
+        if index is not None:
+            idx = np.asarray(torch.as_tensor(index).cpu()).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= len(pool_or_sizes)):
+                raise ValueError("roi_paste: photograph index outside the pool of %d" % len(pool_or_sizes))
+            hw = hw[idx]
+    else:
+        hw = np.asarray(pool_or_sizes, np.int64).reshape(-1, 2)
+    if hw.min() < 1 or hw.max() > PhotoPool.MAX_SIDE:
+        raise ValueError("roi_paste: photograph sizes outside 1..%d" % PhotoPool.MAX_SIDE)
+    (masks,) = _to_device(masks)
+    masks = _mask_u8(masks)
+    B = masks.shape[0]
+    if hw.shape[0] != B:
+        raise ValueError("roi_paste: %d masks for %d photographs" % (B, hw.shape[0]))
+    boxes = _check_boxes(boxes, B, int(masks.shape[2]), "roi_paste").to(masks.device)
+    px = hw[:, 0].astype(np.int64) * hw[:, 1]
+    starts = np.concatenate([[0], np.cumsum(px)]).astype(np.int64)
+    flat = kernels().roi_paste(masks, boxes, torch.from_numpy(np.ascontiguousarray(hw, dtype=np.int32)).to(masks.device),
+                               torch.from_numpy(starts[:-1].copy()).to(masks.device), int(starts[-1]))
+    return [flat[int(starts[b]):int(starts[b + 1])].view(int(hw[b, 0]), int(hw[b, 1])) for b in range(B)]
+
+
 def photometric_augment(images, generator=None):
     """Device-side photometric augmentation of a [-1,1] image batch in the spirit of utils/Utils.py:33-43
     (brightness/contrast + saturation jitter with p=0.8, grayscale with p=0.2, 5x5 Gaussian blur with

@@ -9,10 +9,15 @@ with the images of its own size; per batch forward -> sigmoid -> ``postprocessin
     --csv FILE                        img_name, vcdr_pred: the predicted vertical cup-to-disc ratio (cup rows / disc rows, nan without a disc)
 
 An image whose height or width is not a multiple of 16 is refused by name: the generator takes no other size and no padding is invented.
+With ``--whole-photo`` the files are whole fundus photographs of any size instead (``uda_clr_amd.wholephoto``): per photograph the disc is
+located on a coarse canvas, a ``--roi-size`` window around it is cut and resampled to 512 x 512 as Pillow would, the steps above run on
+that ROI, and <out>/photo_mask/<stem>.png is the mask at the photograph's size; the CSV also carries roi_x0, roi_y0, roi_size, located,
+disc_cx, disc_cy.  ``--locator-checkpoint`` names a second generator for the coarse stage, ``--centres`` a CSV (img_name, cx, cy) that
+replaces it.
 
     python -m uda_clr_amd.predict --images DIR --checkpoint FILE --out DIR [--backbone mobilenet] [--out-stride 16] [--use_TN]
                                   [--dataset Drishti-GS] [--threshold 0.75] [--batch-size 8] [--csv FILE] [--morphometry [--sectors 72]]
-                                  [--mc-passes 8]
+                                  [--mc-passes 8] [--whole-photo [--roi-size 800] [--locator-checkpoint FILE] [--centres CSV]]
 
 With ``--morphometry`` the CSV also carries, per image, hcdr_pred and acdr_pred (horizontal and area cup-to-disc ratio), rdr_min_pred and
 rim_{up,left,down,right}_pred (thinnest and per-quadrant rim-to-disc ratio), cup_offset_pred (pixels) and {cup,disc}_{major,minor,
@@ -56,6 +61,12 @@ def build_parser():
     ap.add_argument("--sectors", type=int, default=72, metavar="K", help="sectors of the rim profile: a multiple of 8 in 8..360")
     ap.add_argument("--mc-passes", type=int, default=0, metavar="T",
                     help="MC-dropout passes (2..32): writes uncertainty/ pictures, the CSV also gets cup_unsure, disc_unsure, unsure_px")
+    ap.add_argument("--whole-photo", action="store_true",
+                    help="the files are whole photographs of any size: locate the disc, cut a --roi-size window, predict on it, paste the mask back")
+    ap.add_argument("--roi-size", type=int, default=800, metavar="R",
+                    help="side of the window cut around the disc, in photograph pixels (8..1280; 800 is the convention of the public ROI releases)")
+    ap.add_argument("--locator-checkpoint", default=None, metavar="FILE", help="a second generator for the coarse stage (default: the same one)")
+    ap.add_argument("--centres", default=None, metavar="CSV", help="img_name, cx, cy in photograph pixels: skips the coarse stage")
     return ap
 
 
@@ -66,17 +77,18 @@ def list_images(folder):
     return names
 
 
-def read_images(folder, names):
-    """-> [(name, uint8 [H,W,3])], every size checked before anything runs"""
+def read_images(folder, names, any_size=False):
+    """-> [(name, uint8 [H,W,3])], every size checked before anything runs (``any_size``: whole photographs, no check)"""
     from PIL import Image
     out = []
     for name in names:
         with Image.open(os.path.join(folder, name)) as im:
             a = np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
-        try:
-            check_input_size(a.shape[0], a.shape[1])
-        except ValueError as e:
-            raise ValueError("%s: %s" % (name, e)) from None
+        if not any_size:
+            try:
+                check_input_size(a.shape[0], a.shape[1])
+            except ValueError as e:
+                raise ValueError("%s: %s" % (name, e)) from None
         out.append((name, a))
     return out
 
@@ -124,6 +136,42 @@ def uncertainty_columns(unc, pred):
     return {"cup_unsure": share[:, 0], "disc_unsure": share[:, 1], "unsure_px": unsure.sum(-1).astype(np.float64)}
 
 
+def predict_batch(model, u8, x, names, out_dir, dataset="Drishti-GS", threshold=0.75, morphometry=False, sectors=72, mc_passes=0, mc_logits=None):
+    """The per-batch body that ``predict`` and ``wholephoto.predict_photos`` share: ``u8`` uint8 [B,H,W,3] and ``x`` f32 [B,3,H,W] (its
+    normalised form) on the device -> (rows, pred): forward -> sigmoid -> ``postprocessing_batch``, the three folders written, one
+    row per image as ``predict`` documents them, and the uint8 [B,2,H,W] evaluation masks on the device."""
+    out = model(x)
+    logits = out[0] if isinstance(out, (tuple, list)) else out
+    prob = torch.sigmoid(logits.float())
+    pred = Utils.postprocessing_batch(prob, threshold, dataset)
+    Utils.save_per_img_batch(u8, out_dir, names, prob)
+    Utils.save_mask_batch(pred, out_dir, names)
+    # the prediction as both masks: slot 1 of 'extent' is the prediction's first and last row per class
+    profile = ops.surface_profile(pred, pred, percentiles=(), tolerances=())[2]
+    vcdr = metrics.vertical_cdr_from_profile(profile)["vcdr_pred"]
+    rows = [{"img_name": n, "vcdr_pred": float(v)} for n, v in zip(names, vcdr)]
+    if morphometry:
+        cols = morphometry_columns(pred, sectors)
+        for i in range(len(names)):
+            rows[i].update({k: float(cols[k][i]) for k in MORPHOMETRY_COLUMNS})
+    if mc_passes:
+        unc = ops.mc_uncertainty(mc_logits(x, mc_passes), outputs=("std",), u8_scale=UNCERTAINTY_U8_SCALE)
+        Utils.save_uncertainty_batch(unc["std_u8"], out_dir, names)
+        cols = uncertainty_columns(unc["std"], pred)
+        for i in range(len(names)):
+            rows[i].update({k: float(cols[k][i]) for k in UNCERTAINTY_COLUMNS})
+    return rows, pred
+
+
+def resolve_mc_logits(model, mc_passes, mc_logits):
+    """the stochastic passes of ``mc_passes``: the callable given, else ``model.mc_inference_logits``"""
+    if int(mc_passes) and mc_logits is None:
+        mc_logits = getattr(model, "mc_inference_logits", None)
+        if mc_logits is None:
+            raise ValueError("mc_passes needs a model with mc_inference_logits (DeepLab) or an mc_logits callable")
+    return mc_logits
+
+
 def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_size=8, morphometry=False, sectors=72, mc_passes=0,
             mc_logits=None):
     """``images`` as ``read_images`` returns them -> [{'img_name', 'vcdr_pred'}] in batch order; writes the three folders.
@@ -136,10 +184,7 @@ def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_
     if not torch.cuda.is_available():
         raise RuntimeError("uda_clr_amd computes only on the MI355X HIP kernels (there is no CPU fallback)")
     mc_passes = int(mc_passes)
-    if mc_passes and mc_logits is None:
-        mc_logits = getattr(model, "mc_inference_logits", None)
-        if mc_logits is None:
-            raise ValueError("mc_passes needs a model with mc_inference_logits (DeepLab) or an mc_logits callable")
+    mc_logits = resolve_mc_logits(model, mc_passes, mc_logits)
     dev = torch.device("cuda")
     was_training = getattr(model, "training", False)
     if hasattr(model, "eval"):
@@ -150,37 +195,21 @@ def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_
             for names, u8 in batches(images, batch_size):
                 u8 = torch.from_numpy(u8).to(dev)
                 x = (u8.permute(0, 3, 1, 2).float() / 127.5 - 1.0).contiguous()          # Normalize_tf's image, ToTensor's layout
-                out = model(x)
-                logits = out[0] if isinstance(out, (tuple, list)) else out
-                prob = torch.sigmoid(logits.float())
-                pred = Utils.postprocessing_batch(prob, threshold, dataset)
-                Utils.save_per_img_batch(u8, out_dir, names, prob)
-                Utils.save_mask_batch(pred, out_dir, names)
-                # the prediction as both masks: slot 1 of 'extent' is the prediction's first and last row per class
-                profile = ops.surface_profile(pred, pred, percentiles=(), tolerances=())[2]
-                vcdr = metrics.vertical_cdr_from_profile(profile)["vcdr_pred"]
-                first = len(rows)
-                rows += [{"img_name": n, "vcdr_pred": float(v)} for n, v in zip(names, vcdr)]
-                if morphometry:
-                    cols = morphometry_columns(pred, sectors)
-                    for i in range(len(names)):
-                        rows[first + i].update({k: float(cols[k][i]) for k in MORPHOMETRY_COLUMNS})
-                if mc_passes:
-                    unc = ops.mc_uncertainty(mc_logits(x, mc_passes), outputs=("std",), u8_scale=UNCERTAINTY_U8_SCALE)
-                    Utils.save_uncertainty_batch(unc["std_u8"], out_dir, names)
-                    cols = uncertainty_columns(unc["std"], pred)
-                    for i in range(len(names)):
-                        rows[first + i].update({k: float(cols[k][i]) for k in UNCERTAINTY_COLUMNS})
+                rows += predict_batch(model, u8, x, names, out_dir, dataset, threshold, morphometry, sectors, mc_passes, mc_logits)[0]
     finally:
         if was_training and hasattr(model, "train"):
             model.train()
     return rows
 
 
+WHOLE_PHOTO_COLUMNS = ("roi_x0", "roi_y0", "roi_size", "located", "disc_cx", "disc_cy")
+
+
 def write_csv(path, rows):
-    """img_name, vcdr_pred, and MORPHOMETRY_COLUMNS and UNCERTAINTY_COLUMNS where the rows carry them"""
+    """img_name, vcdr_pred, and MORPHOMETRY_COLUMNS, UNCERTAINTY_COLUMNS and WHOLE_PHOTO_COLUMNS where the rows carry them"""
     more = MORPHOMETRY_COLUMNS if rows and MORPHOMETRY_COLUMNS[0] in rows[0] else ()
     more += UNCERTAINTY_COLUMNS if rows and UNCERTAINTY_COLUMNS[0] in rows[0] else ()
+    more += WHOLE_PHOTO_COLUMNS if rows and WHOLE_PHOTO_COLUMNS[0] in rows[0] else ()
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(("img_name", "vcdr_pred") + more)
@@ -188,17 +217,34 @@ def write_csv(path, rows):
             w.writerow([r["img_name"], repr(r["vcdr_pred"])] + [repr(r[k]) for k in more])
 
 
-def main(argv=None, model=None, mc_logits=None):
-    """The command line.  ``model``: a callable to run instead of the checkpoint's DeepLab, ``mc_logits``: its stochastic passes (tests)."""
+def read_centres(path):
+    """--centres: a CSV with the columns img_name, cx, cy (photograph pixels) -> {img_name: (cx, cy)}"""
+    with open(path, newline="") as f:
+        return {r["img_name"]: (int(round(float(r["cx"]))), int(round(float(r["cy"])))) for r in csv.DictReader(f)}
+
+
+def main(argv=None, model=None, mc_logits=None, locator=None, size=512):
+    """The command line.  ``model``: a callable to run instead of the checkpoint's DeepLab, ``mc_logits``: its stochastic passes,
+    ``locator``: a callable for the coarse stage of --whole-photo instead of --locator-checkpoint's DeepLab, ``size``: the input side
+    that --whole-photo resamples canvas and ROI to, for a generator that takes another one than the data sets' 512 (tests)."""
     args = build_parser().parse_args(argv)
-    images = read_images(args.images, list_images(args.images))
+    images = read_images(args.images, list_images(args.images), any_size=args.whole_photo)
     if model is None:
         if not args.checkpoint:
             raise SystemExit("--checkpoint is required")
         model = load_generator(args.checkpoint, args.backbone, args.out_stride, args.use_TN,
                                torch.device("cuda") if torch.cuda.is_available() else None)
-    rows = predict(model, images, args.out, dataset=args.dataset, threshold=args.threshold, batch_size=args.batch_size,
-                   morphometry=args.morphometry, sectors=args.sectors, mc_passes=args.mc_passes, mc_logits=mc_logits)
+    options = dict(dataset=args.dataset, threshold=args.threshold, batch_size=args.batch_size, morphometry=args.morphometry, sectors=args.sectors,
+                   mc_passes=args.mc_passes, mc_logits=mc_logits)
+    if args.whole_photo:
+        from . import wholephoto
+        if locator is None and args.locator_checkpoint:
+            locator = load_generator(args.locator_checkpoint, args.backbone, args.out_stride, args.use_TN,
+                                     torch.device("cuda") if torch.cuda.is_available() else None)
+        rows = wholephoto.predict_photos(model, images, args.out, roi_size=args.roi_size, size=size, locator=locator,
+                                         centres=read_centres(args.centres) if args.centres else None, **options)
+    else:
+        rows = predict(model, images, args.out, **options)
     print("%d images -> %s" % (len(rows), args.out))
     if args.csv:
         write_csv(args.csv, rows)
