@@ -539,6 +539,31 @@ int uda_mc_uncertainty(const float* logits, int T, int64_t n, float* mean_prob, 
 int uda_selective_tables(const float* prob, const float* unc, const uint8_t* pred, const uint8_t* gt, int B, int H, int W, int M,
                          const float* edges, int K, int64_t* rel, int64_t* risk, int64_t* invalid, void* stream);
 
+/* ---- test-time augmentation at evaluation (uda_clr_amd/tta.py): the image is predicted under V views, the predictions
+ * are mapped back to the image's frame and reduced per element by the statistics of uda_mc_uncertainty (the same code: equal logits
+ * give equal bits).  The reference evaluates one view (train_process/Trainer_prototype_full.py:358-368 are its only repeated
+ * passes); every definition here is this project's.
+ * A view is (g, h, w): g in 0..7, h and w multiples of 16 in 16..1024.  With R = bilinear(image -> (h, w)), align_corners=True (the
+ * index and weight arithmetic of uda_head_upsample_fwd, every product and sum of the lerp rounded on its own),
+ *     F[i][j] = R[(g & 2) ? h - 1 - i : i][(g & 1) ? w - 1 - j : j],   U = F if !(g & 4), else U[i][j] = F[j][i] (U is [w][h]):
+ *   0 identity, 1 left-right mirror, 2 top-bottom mirror, 3 half turn, 4 transpose, 5 and 6 the quarter turns
+ *   (torch.rot90(R, 1, (-2, -1)) and torch.rot90(R, -1, (-2, -1))), 7 anti-transpose.
+ *   The inverse of a view, applied to logits L of U's shape: F'[a][b] = (g & 4) ? L[b][a] : L[a][b], R'[a][b] = F' at the mirrored
+ *   indices as above, then bilinear(R' -> (H, W)), align_corners=True.
+ * uda_tta_view: image f32 [B][C][H][W] -> out f32 [B][C][h'][w'] = U, (h', w') = (g & 4) ? (w, h) : (h, w).  With h == H and w == W the
+ *   values are copied, no arithmetic.  16-byte stores along the rows of U; a transposed view goes through an LDS tile.
+ * uda_tta_fuse: HOST arrays logits[V] (device pointers), g[V], h[V], w[V], 2 <= V <= 32, read before the call returns and passed to the
+ *   kernel by value; tensor v is f32 [B][C][h_v'][w_v'], contiguous, 16-byte aligned.  For every element [b][c][y][x] of the H x W frame
+ *   z_v, v = 0..V-1 in order, is the stored logit itself where (h_v, w_v) == (H, W) and the 4-tap interpolation of the inverse-mapped
+ *   logits otherwise; the outputs are those of uda_mc_uncertainty on (z_0, ..., z_V-1): mean_prob, std_half, entropy, mutual_info f32
+ *   [B][C][H][W], std_u8 uint8 [B][C][H][W] with u8_scale; null = not written, at least one given; float outputs 16-byte aligned,
+ *   std_u8 4-byte aligned.  An element's outputs depend on its own taps only: an image alone and inside a batch gives the same bits.
+ * 1 <= B <= 8192, 1 <= C <= 4, H and W multiples of 16 in 16..1024.  A null pointer (a null logits[v] included), V, g, a size, B or C
+ * out of range returns the error before any launch and writes nothing.  No workspace, no atomics. */
+int uda_tta_view(const float* image, int B, int C, int H, int W, int g, int h, int w, float* out, void* stream);
+int uda_tta_fuse(const float* const* logits, const int* g, const int* h, const int* w, int V, int B, int C, int H, int W,
+                 float* mean_prob, float* std_half, float* entropy, float* mutual_info, uint8_t* std_u8, float u8_scale, void* stream);
+
 /* ---- device-side tail of the input pipeline. The reference's dataloader workers run these per sample
  * on the CPU with scipy.ndimage; here they run per uint8 BATCH on the GPU, bit-identical to the scipy calls.
  * uda_normalize_tf: dataloaders/custom_transforms.py:432-466 (Normalize_tf), :414-429 (GetBoundary), :504-507 (ToTensor).

@@ -1,0 +1,4 @@
+// uda_tta_fuse for TTA_FUSE_B_LAST + 1..UNC_TMAX views (tta_fuse.h says why there are three of these)
+#include "tta_fuse.h"
+
+TTA_FUSE_PIECE(tta_fuse_launch_c, TTA_FUSE_B_LAST + 1, UNC_TMAX)

@@ -16,11 +16,16 @@ probabilities against the labels (ECE, Brier score, reliability diagram) and, fr
 quantity the trainer thresholds at 0.04 (reference utils/Utils.py:165-166, :197-200): what share of the pixels that mask keeps, how
 clean the kept labels are, and how well the uncertainty ranks the errors (AUROC, risk-coverage curve).
 
+``tta`` scores the mean over several views of the image - mirrorings, quarter turns, a few scales - instead of one forward
+(``uda_clr_amd.tta``: ``ops.tta_view``, one forward per distinct view shape, ``ops.tta_fuse``); ``tta_uncertainty`` reads the std over
+those views where ``mc_passes`` reads the std over dropout passes.
+
 With ``save_dir`` every image also leaves three PNG files there: ``overlay/`` (the reference's contour picture, utils/Utils.py:515-585),
 ``original_image/`` and ``mask/`` (the evaluation masks the metrics were computed on, BEAL grey coding).
 
     python -m uda_clr_amd.evaluate --data-dir DIR --dataset Drishti-GS --checkpoint FILE [--hd95] [--tolerance 2 ...] [--cdr]
                                    [--morphometry [--sectors 72]] [--calibration [--bins 15]] [--mc-passes 8]
+                                   [--tta flips,id@0.75,id@1.25 [--tta-uncertainty]]
                                    [--csv per_image.csv] [--json result.json] [--save-dir DIR]
 """
 import argparse
@@ -60,13 +65,15 @@ def uncertainty_fields(report_edges=(0.04,)):
     return tuple(names)
 
 
-def extra_fields(hd95=False, tolerances=(), cdr=False, morphometry=False, calibration=False, mc_passes=0, report_edges=(0.04,)):
-    """names of the per-image figures that ``evaluate`` adds for these arguments, in the order of its tables"""
+def extra_fields(hd95=False, tolerances=(), cdr=False, morphometry=False, calibration=False, mc_passes=0, report_edges=(0.04,),
+                 tta_uncertainty=False):
+    """names of the per-image figures that ``evaluate`` adds for these arguments, in the order of its tables (``tta_uncertainty`` adds
+    the names of ``mc_passes``: the same figures from the std over the views)"""
     names = ["cup_hd95", "disc_hd95"] if hd95 else []
     for tau in tolerances:
         names += ["cup_nsd_%g" % tau, "disc_nsd_%g" % tau]
     return (tuple(names + (["vcdr_pred", "vcdr_gt", "cdr_error"] if cdr else [])) + (MORPHOMETRY_FIELDS if morphometry else ()) +
-            (CALIBRATION_FIELDS if calibration else ()) + (uncertainty_fields(report_edges) if mc_passes else ()))
+            (CALIBRATION_FIELDS if calibration else ()) + (uncertainty_fields(report_edges) if mc_passes or tta_uncertainty else ()))
 
 
 def morphometry_columns(pred, gt, sectors=72):
@@ -116,7 +123,7 @@ def _lists(d):
 
 def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=False, tolerances=(), cdr=False, morphometry=False,
              sectors=72, calibration=False, bins=15, mc_passes=0, unc_edges=ops.DEFAULT_UNC_EDGES, report_edges=(0.04,), mc_logits=None,
-             save_dir=None):
+             tta=None, tta_uncertainty=False, save_dir=None):
     """Score ``model`` on every image of ``loader``.
 
     model       callable whose first output (or only output) is the [B,2,H,W] logits (cup, disc), e.g. ``DeepLab``
@@ -154,13 +161,35 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
                 ``Utils.save_per_img_batch``), original_image/<stem>.png and mask/<stem>.png (``pred``, the masks the figures above
                 were computed on: 0 = cup, 128 = disc only, 255 = background).  The returned result is the same with and without it.
                 With ``mc_passes`` also uncertainty/<stem>.png, RGB (0, disc, cup) of min(255, floor(std * 1600)): the trainer's
-                threshold 0.04 is grey 64.  None (the default) makes no further call."""
+                threshold 0.04 is grey 64.  None (the default) makes no further call.
+
+    tta         a view list - a string such as 'flips,id@0.75,id@1.25' (``tta.parse_views``) or a list of (g, h, w): ``prob`` is the
+                mean over the views of the probabilities mapped back to the image's frame (``tta.tta_predict``: ``ops.tta_view``, one
+                forward per distinct view shape, ``ops.tta_fuse``), and everything downstream - post-processing, metrics, calibration,
+                pictures - uses it.  The result records the checked list as res['tta'] (that of the first batch).  None (the default):
+                one forward of the image, as before.
+    tta_uncertainty  True (needs ``tta``, excludes ``mc_passes``): the unbiased std over the views of sigmoid(x / 2) takes the place
+                of the MC-dropout std: the same ``ops.selective_tables`` call, the same '{cup,disc}_unc_auroc', '_cov_<e>', '_dice_<e>',
+                '_err_<e>' names, res['risk_coverage'] with 'views' in the place of 'passes', uncertainty/<stem>.png from its
+                'std_u8'."""
     tolerances = tuple(float(t) for t in tolerances)
     profiled = extra_fields(hd95, tolerances, cdr)
     mc_passes = int(mc_passes)
-    extra = extra_fields(hd95, tolerances, cdr, morphometry, calibration, mc_passes, report_edges)
-    if mc_passes:
+    tta_uncertainty = bool(tta_uncertainty)
+    if tta_uncertainty and mc_passes:
+        raise ValueError("tta_uncertainty=True and mc_passes=%d: one uncertainty fills the risk table, not both" % mc_passes)
+    if tta_uncertainty and tta is None:
+        raise ValueError("tta_uncertainty=True needs tta, a view list (got tta=None)")
+    if tta is not None:
+        from . import tta as tta_views
+        if not isinstance(tta, str):
+            tta = tta_views.normalise_views(tta, None, None)
+    used_views = None
+    with_unc = bool(mc_passes) or tta_uncertainty
+    extra = extra_fields(hd95, tolerances, cdr, morphometry, calibration, mc_passes, report_edges, tta_uncertainty)
+    if with_unc:
         _edge_index(unc_edges, report_edges)
+    if mc_passes:
         if mc_logits is None:
             mc_logits = getattr(model, "mc_inference_logits", None)
         if mc_logits is None:
@@ -179,9 +208,17 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
                 image, target = sample['image'], sample['map']
                 if dev is not None:
                     image, target = image.to(dev), target.to(dev)
-                out = model(image)
-                logits = out[0] if isinstance(out, (tuple, list)) else out
-                prob = torch.sigmoid(logits.float())
+                fused = None
+                if tta is None:
+                    out = model(image)
+                    logits = out[0] if isinstance(out, (tuple, list)) else out
+                    prob = torch.sigmoid(logits.float())
+                else:
+                    views = tta_views.normalise_views(tta, image.shape[-2], image.shape[-1])
+                    used_views = views if used_views is None else used_views
+                    fused = tta_views.tta_predict(model, image, views, outputs=("mean", "std") if tta_uncertainty else ("mean",),
+                                                  u8_scale=UNCERTAINTY_U8_SCALE if tta_uncertainty and save_dir is not None else None)
+                    prob = fused["mean"]
                 if postprocess:
                     pred = Utils.postprocessing_batch(prob, threshold, dataset)
                 else:
@@ -209,20 +246,22 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
                 if mc_passes:
                     unc = ops.mc_uncertainty(mc_logits(image, mc_passes), outputs=("std",),
                                              u8_scale=UNCERTAINTY_U8_SCALE if save_dir is not None else None)
-                if calibration or mc_passes:                                         # both tables in one call, one copy
-                    tables = ops.selective_tables(prob if calibration else None, unc["std"] if mc_passes else None, pred, target > 0.5,
+                if tta_uncertainty:
+                    unc = fused
+                if calibration or with_unc:                                          # both tables in one call, one copy
+                    tables = ops.selective_tables(prob if calibration else None, unc["std"] if with_unc else None, pred, target > 0.5,
                                                   bins=bins, edges=unc_edges)
                     if calibration:
                         more.update(calibration_columns(tables["rel"]))
                         pooled_rel = tables["rel"].sum(0) + (0 if pooled_rel is None else pooled_rel)
-                    if mc_passes:
+                    if with_unc:
                         more.update(uncertainty_columns(tables["risk"], unc_edges, report_edges))
                         pooled_risk = tables["risk"].sum(0) + (0 if pooled_risk is None else pooled_risk)
                 names = _names(sample, dice.shape[0], len(per_image))
                 if save_dir is not None:
                     Utils.save_per_img_batch(image, save_dir, names, prob)
                     Utils.save_mask_batch(pred, save_dir, names)
-                    if mc_passes:
+                    if with_unc:
                         Utils.save_uncertainty_batch(unc["std_u8"], save_dir, names)
                 for i, name in enumerate(names):
                     per_image.append({"img_name": name,
@@ -244,6 +283,11 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
     if mc_passes and pooled_risk is not None:
         res["risk_coverage"] = dict(_lists(metrics.selective_from_table(pooled_risk, unc_edges)), risk=pooled_risk.tolist(),
                                     passes=mc_passes)
+    if tta_uncertainty and pooled_risk is not None:
+        res["risk_coverage"] = dict(_lists(metrics.selective_from_table(pooled_risk, unc_edges)), risk=pooled_risk.tolist(),
+                                    views=len(used_views))
+    if tta is not None:
+        res["tta"] = [list(v) for v in used_views] if used_views is not None else []
     return res
 
 
@@ -279,6 +323,10 @@ def build_parser():
     ap.add_argument("--bins", type=int, default=15, metavar="N", help="confidence bins of the reliability diagram, 1..64")
     ap.add_argument("--mc-passes", type=int, default=0, metavar="T",
                     help="MC-dropout passes (2..32): uncertainty AUROC, coverage / Dice / error of the pixels with std < 0.04, risk-coverage table")
+    ap.add_argument("--tta", default=None, metavar="SPEC",
+                    help="test-time augmentation: views id hflip vflip rot180 transpose rot90 rot270 antitranspose, flips, d4, each optionally @scale, "
+                         "e.g. flips,id@0.75,id@1.25; the mean over the views is what is scored")
+    ap.add_argument("--tta-uncertainty", action="store_true", help="with --tta: the std over the views fills the columns and pictures of --mc-passes")
     ap.add_argument("--csv", default=None, metavar="PATH", help="one row per image")
     ap.add_argument("--json", default=None, metavar="PATH", help="the whole result")
     ap.add_argument("--save-dir", default=None, metavar="DIR", help="write overlay/, original_image/ and mask/ PNG files per image")
@@ -336,7 +384,7 @@ def main(argv=None, model=None, mc_logits=None):
     res = evaluate(model, loader, dataset=args.dataset, threshold=args.threshold, postprocess=not args.no_postprocess,
                    hd95=args.hd95, tolerances=tuple(args.tolerance), cdr=args.cdr, save_dir=args.save_dir,
                    morphometry=args.morphometry, sectors=args.sectors, calibration=args.calibration, bins=args.bins,
-                   mc_passes=args.mc_passes, mc_logits=mc_logits)
+                   mc_passes=args.mc_passes, mc_logits=mc_logits, tta=args.tta, tta_uncertainty=args.tta_uncertainty)
     print(format_mean(res))
     if args.csv:
         write_csv(args.csv, res)

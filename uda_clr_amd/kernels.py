@@ -149,6 +149,8 @@ SYMBOLS = {
     "uda_disc_morphometry": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _U, _P]),
     "uda_mc_uncertainty": (_I, [_P, _I, _L, _P, _P, _P, _P, _P, _F, _P]),
     "uda_selective_tables": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _I, _P, _P, _P, _P]),
+    "uda_tta_view": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "uda_tta_fuse": (_I, [C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P]),
     "uda_normalize_tf_workspace_bytes": (_U, [_I, _I, _I]),
     "uda_normalize_tf": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _U, _P]),
     "uda_field_smooth": (_I, [_P, _I, _I, _I, _P, _I, _D, _P, _P, _P]),
@@ -1497,6 +1499,84 @@ class HipKernels:
                                                self._stream()))
         out = (rel, risk, invalid.view(B, 2, 2))
         return out + (packed,) if want_packed else out
+
+    @staticmethod
+    def _ck_tta_view(who, v, view):
+        """a view (g, h, w) as include/uda_clr_hip.h defines it -> (g, h, w) as ints"""
+        try:
+            g, h, w = (int(a) for a in view)
+        except (TypeError, ValueError):
+            raise ValueError("%s: view %d must be (g, h, w), got %r" % (who, v, view)) from None
+        if not 0 <= g <= 7:
+            raise ValueError("%s: view %d: code %d outside 0..7" % (who, v, g))
+        if h % 16 or w % 16 or not (16 <= h <= 1024 and 16 <= w <= 1024):
+            raise ValueError("%s: view %d: size %d x %d, each side must be a multiple of 16 in 16..1024" % (who, v, h, w))
+        return g, h, w
+
+    @staticmethod
+    def _ck_tta_frame(who, B, Cc, H, W):
+        if not 1 <= B <= 8192:
+            raise ValueError("%s: batch %d outside 1..8192" % (who, B))
+        if not 1 <= Cc <= 4:
+            raise ValueError("%s: %d channels outside 1..4" % (who, Cc))
+        if H % 16 or W % 16 or not (16 <= H <= 1024 and 16 <= W <= 1024):
+            raise ValueError("%s: frame %d x %d, each side must be a multiple of 16 in 16..1024" % (who, H, W))
+
+    def tta_view(self, image, view):
+        """f32 [B,C,H,W] image, view (g, h, w) -> the view's input f32 [B,C,h,w] ([B,C,w,h] for a transposed code g & 4) on the device
+        (include/uda_clr_hip.h, uda_tta_view): resampled to (h, w) with align_corners=True, mirrored, transposed; a view of the
+        image's own size is a permutation of its values."""
+        self._dev(image)
+        if image.dtype != torch.float32 or not image.is_contiguous() or image.dim() != 4:
+            raise ValueError("tta_view: contiguous float32 [B, C, H, W] image (got %s %s)" % (image.dtype, tuple(image.shape)))
+        g, h, w = self._ck_tta_view("tta_view", 0, view)
+        B, Cc, H, W = image.shape
+        self._ck_tta_frame("tta_view", B, Cc, H, W)
+        out = torch.empty((B, Cc, w, h) if g & 4 else (B, Cc, h, w), dtype=torch.float32, device=image.device)
+        self._ck(self.lib.uda_tta_view(image.data_ptr(), B, Cc, H, W, g, h, w, out.data_ptr(), self._stream()))
+        return out
+
+    def tta_fuse(self, view_logits, views, size, outputs=("mean",), u8_scale=None):
+        """V f32 [B,C,h_v',w_v'] logit tensors of the views (g, h, w) of an H x W frame, ``size`` = (H, W) -> {name: [B,C,H,W] map} on
+        the device, one read of the logits (include/uda_clr_hip.h, uda_tta_fuse): every view mapped back to the frame, then the maps
+        of ``mc_uncertainty`` over the views: 'mean', 'std', 'entropy', 'mi' and with ``u8_scale`` 'std_u8'."""
+        names = ("mean", "std", "entropy", "mi")
+        outputs = tuple(outputs)
+        if any(o not in names for o in outputs) or not (outputs or u8_scale is not None):
+            raise ValueError("tta_fuse: outputs among %r (got %r)" % (names, outputs))
+        view_logits, views = list(view_logits), list(views)
+        V = len(views)
+        if not 2 <= V <= 32:
+            raise ValueError("tta_fuse: %d views outside 2..32" % V)
+        if len(view_logits) != V:
+            raise ValueError("tta_fuse: %d logit tensors for %d views" % (len(view_logits), V))
+        try:
+            H, W = (int(a) for a in size)
+        except (TypeError, ValueError):
+            raise ValueError("tta_fuse: size must be (H, W), got %r" % (size,)) from None
+        views = [self._ck_tta_view("tta_fuse", v, view) for v, view in enumerate(views)]
+        if view_logits[0] is None or view_logits[0].dim() != 4:
+            raise ValueError("tta_fuse: view 0: contiguous float32 [B, C, h, w] logits (got %r)" %
+                             (None if view_logits[0] is None else tuple(view_logits[0].shape),))
+        B, Cc = view_logits[0].shape[:2]
+        self._ck_tta_frame("tta_fuse", B, Cc, H, W)
+        for v, (t, (g, h, w)) in enumerate(zip(view_logits, views)):
+            if t is None:
+                raise ValueError("tta_fuse: view %d: no logits (None)" % v)
+            self._dev(t)
+            want = (B, Cc, w, h) if g & 4 else (B, Cc, h, w)
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != want or t.data_ptr() % 16:
+                raise ValueError("tta_fuse: view %d (g %d, %d x %d): contiguous 16-byte aligned float32 logits of shape %s (got %s %s)"
+                                 % (v, g, h, w, want, t.dtype, tuple(t.shape)))
+        dev = view_logits[0].device
+        out = {o: torch.empty((B, Cc, H, W), dtype=torch.float32, device=dev) for o in names if o in outputs}
+        if u8_scale is not None:
+            out["std_u8"] = torch.empty((B, Cc, H, W), dtype=torch.uint8, device=dev)
+        ints = lambda k: (C.c_int * V)(*[view[k] for view in views])
+        self._ck(self.lib.uda_tta_fuse((C.c_void_p * V)(*[t.data_ptr() for t in view_logits]), ints(0), ints(1), ints(2), V, B, Cc, H, W,
+                                       _ptr(out.get("mean")), _ptr(out.get("std")), _ptr(out.get("entropy")), _ptr(out.get("mi")),
+                                       _ptr(out.get("std_u8")), 0.0 if u8_scale is None else float(u8_scale), self._stream()))
+        return out
 
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
         for t in (params, grads, exp_avg, exp_avg_sq):

@@ -669,3 +669,35 @@ def selective_tables(prob, unc, pred, gt=None, bins=15, edges=DEFAULT_UNC_EDGES)
     rel, risk, invalid = np.split(host, [n_rel, n_rel + n_risk])
     return {"rel": rel.reshape(B, 2, M, 5) if prob is not None else None, "risk": risk.reshape(B, 2, K, 4) if unc is not None else None,
             "invalid": invalid.reshape(B, 2, 2), "edges": e32}
+
+
+def tta_view(image, view):
+    """The input of one test-time-augmentation view of a [B,C,H,W] image (1 <= C <= 4; H, W multiples of 16 in 16..1024), on the
+    device (uda_tta_view).  ``view`` = (g, h, w), h and w multiples of 16 in 16..1024:
+        R = F.interpolate(image, (h, w), mode='bilinear', align_corners=True)          (the image itself where (h, w) == (H, W))
+        g & 1  mirrored left-right, g & 2 mirrored top-bottom, then g & 4 transposed:  0 identity, 1 hflip, 2 vflip, 3 rot180,
+        4 transpose, 5 torch.rot90(R, 1, (-2, -1)), 6 torch.rot90(R, -1, (-2, -1)), 7 anti-transpose
+    -> float32 [B,C,h,w], or [B,C,w,h] for g & 4.  A CPU tensor is moved to the device."""
+    if image.dim() != 4:
+        raise ValueError("tta_view: expected a [B, C, H, W] image, got %s" % (tuple(image.shape),))
+    (image,) = _to_device(image)
+    return kernels().tta_view(image.contiguous().float(), view)
+
+
+def tta_fuse(view_logits, views, size, outputs=("mean",), u8_scale=None):
+    """The logits of V views (2 <= V <= 32) of one [B,C,H,W] batch, mapped back to the image's frame and reduced over the views, in one
+    read of the logits (uda_tta_fuse):
+        view_logits  V tensors, the model's logits on ``tta_view(image, views[v])``: [B,C,h,w], or [B,C,w,h] for a transposed view
+        views        V triples (g, h, w) as ``tta_view`` takes them          size  (H, W) of the frame
+    Per view the transpose is undone, then the mirrorings, then (h, w) is resampled to (H, W) with align_corners=True (a view of the
+    frame's size is read as it is stored).  -> {name: [B,C,H,W] device tensor} for the names in ``outputs``, the maps of
+    ``mc_uncertainty`` with the views in the place of the passes: 'mean' (the fused probability), 'std' (of sigmoid(x / 2) over the
+    views), 'entropy', 'mi', and with ``u8_scale`` 'std_u8'.  CPU tensors are moved to the device."""
+    import math
+    view_logits = list(view_logits)
+    if u8_scale is not None and not (0.0 < float(u8_scale) < math.inf):
+        raise ValueError("tta_fuse: u8_scale must be a positive finite number, got %r" % (u8_scale,))
+    given = [t for t in view_logits if t is not None]
+    moved = iter(_to_device(*given)) if given else iter(())
+    view_logits = [None if t is None else next(moved).contiguous().float() for t in view_logits]
+    return kernels().tta_fuse(view_logits, views, size, outputs, u8_scale)

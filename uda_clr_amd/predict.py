@@ -17,7 +17,8 @@ replaces it.
 
     python -m uda_clr_amd.predict --images DIR --checkpoint FILE --out DIR [--backbone mobilenet] [--out-stride 16] [--use_TN]
                                   [--dataset Drishti-GS] [--threshold 0.75] [--batch-size 8] [--csv FILE] [--morphometry [--sectors 72]]
-                                  [--mc-passes 8] [--whole-photo [--roi-size 800] [--locator-checkpoint FILE] [--centres CSV]]
+                                  [--mc-passes 8] [--tta flips,id@0.75,id@1.25 [--tta-uncertainty]]
+                                  [--whole-photo [--roi-size 800] [--locator-checkpoint FILE] [--centres CSV]]
 
 With ``--morphometry`` the CSV also carries, per image, hcdr_pred and acdr_pred (horizontal and area cup-to-disc ratio), rdr_min_pred and
 rim_{up,left,down,right}_pred (thinnest and per-quadrant rim-to-disc ratio), cup_offset_pred (pixels) and {cup,disc}_{major,minor,
@@ -28,6 +29,11 @@ dropout) and ``ops.mc_uncertainty``: <out>/uncertainty/<stem>.png is RGB (0, dis
 the passes of sigmoid(x / 2) - the quantity the trainer trusts a pseudo-label below 0.04 of, grey 64 here - and the CSV carries
 cup_unsure, disc_unsure (the share of the predicted structure's pixels with std >= 0.04, nan for an empty structure) and unsure_px
 (those pixels counted, cup plane plus disc plane).
+
+With ``--tta SPEC`` every batch is predicted under the views of SPEC (``uda_clr_amd.tta``: mirrorings, quarter turns, scales) and the mean
+over the views, mapped back to the image's frame, is what the masks, pictures and figures come from; ``--tta-uncertainty`` writes the
+uncertainty pictures and the three columns above from the std over the views instead of dropout passes.  With ``--whole-photo`` the views
+are those of the cut ROI: the coarse stage that locates the disc stays single-view.
 """
 import argparse
 import csv
@@ -61,6 +67,11 @@ def build_parser():
     ap.add_argument("--sectors", type=int, default=72, metavar="K", help="sectors of the rim profile: a multiple of 8 in 8..360")
     ap.add_argument("--mc-passes", type=int, default=0, metavar="T",
                     help="MC-dropout passes (2..32): writes uncertainty/ pictures, the CSV also gets cup_unsure, disc_unsure, unsure_px")
+    ap.add_argument("--tta", default=None, metavar="SPEC",
+                    help="test-time augmentation: views id hflip vflip rot180 transpose rot90 rot270 antitranspose, flips, d4, each optionally @scale, "
+                         "e.g. flips,id@0.75,id@1.25; masks and pictures come from the mean over the views")
+    ap.add_argument("--tta-uncertainty", action="store_true",
+                    help="with --tta: uncertainty/ pictures and cup_unsure, disc_unsure, unsure_px from the std over the views")
     ap.add_argument("--whole-photo", action="store_true",
                     help="the files are whole photographs of any size: locate the disc, cut a --roi-size window, predict on it, paste the mask back")
     ap.add_argument("--roi-size", type=int, default=800, metavar="R",
@@ -136,13 +147,23 @@ def uncertainty_columns(unc, pred):
     return {"cup_unsure": share[:, 0], "disc_unsure": share[:, 1], "unsure_px": unsure.sum(-1).astype(np.float64)}
 
 
-def predict_batch(model, u8, x, names, out_dir, dataset="Drishti-GS", threshold=0.75, morphometry=False, sectors=72, mc_passes=0, mc_logits=None):
+def predict_batch(model, u8, x, names, out_dir, dataset="Drishti-GS", threshold=0.75, morphometry=False, sectors=72, mc_passes=0, mc_logits=None,
+                  tta=None, tta_uncertainty=False):
     """The per-batch body that ``predict`` and ``wholephoto.predict_photos`` share: ``u8`` uint8 [B,H,W,3] and ``x`` f32 [B,3,H,W] (its
     normalised form) on the device -> (rows, pred): forward -> sigmoid -> ``postprocessing_batch``, the three folders written, one
-    row per image as ``predict`` documents them, and the uint8 [B,2,H,W] evaluation masks on the device."""
-    out = model(x)
-    logits = out[0] if isinstance(out, (tuple, list)) else out
-    prob = torch.sigmoid(logits.float())
+    row per image as ``predict`` documents them, and the uint8 [B,2,H,W] evaluation masks on the device.  With ``tta`` (a view list,
+    ``uda_clr_amd.tta``) the probabilities are the mean over the views, and with ``tta_uncertainty`` the std over the views fills the
+    uncertainty picture and columns."""
+    fused = None
+    if tta is None:
+        out = model(x)
+        logits = out[0] if isinstance(out, (tuple, list)) else out
+        prob = torch.sigmoid(logits.float())
+    else:
+        from . import tta as tta_views
+        fused = tta_views.tta_predict(model, x, tta, outputs=("mean", "std") if tta_uncertainty else ("mean",),
+                                      u8_scale=UNCERTAINTY_U8_SCALE if tta_uncertainty else None)
+        prob = fused["mean"]
     pred = Utils.postprocessing_batch(prob, threshold, dataset)
     Utils.save_per_img_batch(u8, out_dir, names, prob)
     Utils.save_mask_batch(pred, out_dir, names)
@@ -154,13 +175,21 @@ def predict_batch(model, u8, x, names, out_dir, dataset="Drishti-GS", threshold=
         cols = morphometry_columns(pred, sectors)
         for i in range(len(names)):
             rows[i].update({k: float(cols[k][i]) for k in MORPHOMETRY_COLUMNS})
-    if mc_passes:
-        unc = ops.mc_uncertainty(mc_logits(x, mc_passes), outputs=("std",), u8_scale=UNCERTAINTY_U8_SCALE)
+    if mc_passes or tta_uncertainty:
+        unc = fused if tta_uncertainty else ops.mc_uncertainty(mc_logits(x, mc_passes), outputs=("std",), u8_scale=UNCERTAINTY_U8_SCALE)
         Utils.save_uncertainty_batch(unc["std_u8"], out_dir, names)
         cols = uncertainty_columns(unc["std"], pred)
         for i in range(len(names)):
             rows[i].update({k: float(cols[k][i]) for k in UNCERTAINTY_COLUMNS})
     return rows, pred
+
+
+def check_tta(tta, tta_uncertainty, mc_passes):
+    """the argument errors of ``tta`` / ``tta_uncertainty``, as ``evaluate`` raises them"""
+    if tta_uncertainty and int(mc_passes):
+        raise ValueError("tta_uncertainty=True and mc_passes=%d: one uncertainty fills the columns, not both" % int(mc_passes))
+    if tta_uncertainty and tta is None:
+        raise ValueError("tta_uncertainty=True needs tta, a view list (got tta=None)")
 
 
 def resolve_mc_logits(model, mc_passes, mc_logits):
@@ -173,14 +202,18 @@ def resolve_mc_logits(model, mc_passes, mc_logits):
 
 
 def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_size=8, morphometry=False, sectors=72, mc_passes=0,
-            mc_logits=None):
+            mc_logits=None, tta=None, tta_uncertainty=False):
     """``images`` as ``read_images`` returns them -> [{'img_name', 'vcdr_pred'}] in batch order; writes the three folders.
     ``morphometry``: every row also carries MORPHOMETRY_COLUMNS (horizontal and area cup-to-disc ratio, the thinnest rim-to-disc ratio
     of ``sectors`` sectors and its quadrant means, the cup's decentration in pixels, full axes in pixels and orientation in degrees of
     the ellipse with each structure's covariance), from one ``ops.disc_morphometry`` call per batch.
     ``mc_passes`` T in 2..32: per batch T stochastic passes (``mc_logits(x, T)`` -> [T,B,2,H,W] logits; default
     ``model.mc_inference_logits``), ``ops.mc_uncertainty`` and one ``ops.selective_tables`` call; writes uncertainty/<stem>.png and
-    every row also carries UNCERTAINTY_COLUMNS.  0 (the default) makes no pass and no call."""
+    every row also carries UNCERTAINTY_COLUMNS.  0 (the default) makes no pass and no call.
+    ``tta`` a view list (a string such as 'flips,id@0.75' or a list of (g, h, w), ``uda_clr_amd.tta``): the masks and pictures come from
+    the mean over the views; ``tta_uncertainty`` (needs ``tta``, excludes ``mc_passes``): uncertainty/<stem>.png and UNCERTAINTY_COLUMNS
+    from the std over the views."""
+    check_tta(tta, tta_uncertainty, mc_passes)
     if not torch.cuda.is_available():
         raise RuntimeError("uda_clr_amd computes only on the MI355X HIP kernels (there is no CPU fallback)")
     mc_passes = int(mc_passes)
@@ -195,7 +228,8 @@ def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_
             for names, u8 in batches(images, batch_size):
                 u8 = torch.from_numpy(u8).to(dev)
                 x = (u8.permute(0, 3, 1, 2).float() / 127.5 - 1.0).contiguous()          # Normalize_tf's image, ToTensor's layout
-                rows += predict_batch(model, u8, x, names, out_dir, dataset, threshold, morphometry, sectors, mc_passes, mc_logits)[0]
+                rows += predict_batch(model, u8, x, names, out_dir, dataset, threshold, morphometry, sectors, mc_passes, mc_logits,
+                                      tta, tta_uncertainty)[0]
     finally:
         if was_training and hasattr(model, "train"):
             model.train()
@@ -235,7 +269,7 @@ def main(argv=None, model=None, mc_logits=None, locator=None, size=512):
         model = load_generator(args.checkpoint, args.backbone, args.out_stride, args.use_TN,
                                torch.device("cuda") if torch.cuda.is_available() else None)
     options = dict(dataset=args.dataset, threshold=args.threshold, batch_size=args.batch_size, morphometry=args.morphometry, sectors=args.sectors,
-                   mc_passes=args.mc_passes, mc_logits=mc_logits)
+                   mc_passes=args.mc_passes, mc_logits=mc_logits, tta=args.tta, tta_uncertainty=args.tta_uncertainty)
     if args.whole_photo:
         from . import wholephoto
         if locator is None and args.locator_checkpoint:

@@ -68,13 +68,14 @@ def boxes(centres, sizes, roi_size):
 
 
 def predict_photos(model, photos, out_dir, roi_size=800, size=512, locator=None, centres=None, dataset="Drishti-GS", threshold=0.75,
-                   batch_size=8, morphometry=False, sectors=72, mc_passes=0, mc_logits=None):
+                   batch_size=8, morphometry=False, sectors=72, mc_passes=0, mc_logits=None, tta=None, tta_uncertainty=False):
     """``photos`` [(name, uint8 [H,W,3])] of any sizes -> the rows of ``predict.predict`` on each photograph's ROI, in order, and
     its folders at ROI scale (overlay/, original_image/, mask/, uncertainty/), plus <out_dir>/photo_mask/<stem>.png: the grey mask at
     the photograph's size (0 cup, 128 disc only, 255 elsewhere).
         roi_size  R, side of the window in photograph pixels, 8 <= R <= 2.5 * size        size  the generator's input side
         locator   the generator of the coarse stage (default: ``model``)
         centres   {name: (cx, cy)} in photograph pixels: the coarse stage is skipped (located = 1)
+        tta, tta_uncertainty   as ``predict.predict``: the views are those of the cut ROI; the coarse stage stays single-view
     Every row also carries roi_x0, roi_y0, roi_size, located (1: the coarse stage found a disc; 0: the window sits on the photograph's
     centre) and disc_cx, disc_cy: the centroid of the final disc mask in photograph pixels, x0 + (mean column + 0.5) * R / size (nan
     without a disc); the morphometry columns that are lengths in pixels (PIXEL_COLUMNS) are multiplied by R / size."""
@@ -90,6 +91,7 @@ def predict_photos(model, photos, out_dir, roi_size=800, size=512, locator=None,
     if not torch.cuda.is_available():
         raise RuntimeError("uda_clr_amd computes only on the MI355X HIP kernels (there is no CPU fallback)")
     mc_passes = int(mc_passes)
+    predict.check_tta(tta, tta_uncertainty, mc_passes)
     mc_logits = predict.resolve_mc_logits(model, mc_passes, mc_logits)
     locator = model if locator is None else locator
     dev = torch.device("cuda")
@@ -112,7 +114,7 @@ def predict_photos(model, photos, out_dir, roi_size=800, size=512, locator=None,
                 bx = boxes(cen, pool.sizes_host, R)
                 roi = ops.roi_cut(pool, torch.from_numpy(bx), size=S, outputs=("u8", "f32"))
                 part_rows, pred = predict.predict_batch(model, roi["u8"], roi["f32"], names, out_dir, dataset, threshold, morphometry, sectors,
-                                                        mc_passes, mc_logits)
+                                                        mc_passes, mc_logits, tta, tta_uncertainty)
                 masks = ops.roi_paste(pool, pred, torch.from_numpy(bx))
                 host = torch.cat([m.reshape(-1) for m in masks]).cpu().numpy()         # the one copy of the photograph-sized masks
                 mom = ops.disc_morphometry(pred, 8)["moments"][:, 1, :3]
