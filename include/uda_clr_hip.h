@@ -364,7 +364,8 @@ int uda_seg_counts(const float* logits, const float* target, int B, int C, int64
                    uint64_t* counts, void* stream);
 
 /* ---- category prototypes (utils/Utils.py:108-131, 159-225) */
-/* preds [T][n] logits -> unbiased std over T of sigmoid(x/2), mean over T of sigmoid(x)  (T = 8) */
+/* preds [T][n] logits -> unbiased std over T of sigmoid(x/2), mean over T of sigmoid(x)  (T = 8).
+ * T identical passes give a std of exactly 0 (the mean of the T values is a pairwise sum), as torch.std does. */
 int uda_mc_stats(const float* preds, int T, int64_t n, float* std_map, float* mean_map, void* stream);
 /* wts [P][4] for the classes (cup obj, disc obj, cup bck, disc bck);
  * mode 0: from a [B,2,H,W] map, nearest-resized to h x w;  mode 1: from sigmoid of [P,2] logits;
@@ -373,7 +374,10 @@ int uda_proto_weights(int mode, int B, int h, int w, int H, int W, const float* 
                       int64_t ldl, const float* std_map, const float* mean_map, float* wts, float* mask0,
                       float* mask1, void* stream);
 uint64_t uda_proto_workspace_bytes(int64_t P, int C);
-/* sums (double[4][C+1], ADDED into): weighted channel sums, then the weight total, per class */
+/* sums (double[4][C+1], ADDED into): weighted channel sums, then the weight total, per class.
+ * Supported widths: 1 <= C <= 1024, every one of them (the kernel's LDS plan is csrc/proto_plan.h); any P >= 1.  feat and wts
+ * 16-byte aligned, ldf % 4 == 0 and ldf >= C rounded up to 4 (the lanes from C up to that multiple are read and discarded).  The
+ * combine runs in a fixed order: the same inputs give the same bits. */
 int uda_proto_reduce(const float* feat, int64_t ldf, int64_t P, int C, const float* wts, double* sums,
                      float* workspace, uint64_t workspace_bytes, void* stream);
 int uda_proto_finalize(const double* sums, int C, float* centroids /* [4][C] */, void* stream);

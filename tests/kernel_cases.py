@@ -5,6 +5,7 @@ Used by tests/test_kernels_gpu.py (asserting) and tests/gpu_report.py (printing 
 from __future__ import annotations
 
 import functools
+import math
 
 import torch
 
@@ -876,16 +877,58 @@ def case_seg_loss(B, S, seed=10):
     return run
 
 
-def case_seg_counts(B, S, seed=11):
+UNDECIDED = 1e-5       # a thresholded output is decided where the float64 statement is further than this from the threshold
+
+
+def case_seg_counts(B, S, seed=11, C=2, W=None, edge=False):
+    """Exact counts.  The input holds no undecided element: a logit whose float64 sigmoid lies within UNDECIDED of the threshold
+    is moved away by 1e-2 (asserted).  Every channel with room gets two logits just outside that band (4e-5 in probability on
+    either side of the threshold, three hundred times the fp32 sigmoid's error), so that a shifted threshold shows at every
+    shape.  edge: one target plane of zeros, one of ones, and fractional / tiny / negative-zero targets for the ``!= 0``."""
+    W = S if W is None else W
+    thr = 0.75
+
     def run(dev):
         g = gen(seed)
-        lg = 2 * torch.randn(B, 2, S, S, generator=g) + 1.0
-        tg = (torch.rand(B, 2, S, S, generator=g) > 0.6).float()
-        c_r = SPEC.seg_counts(lg, tg, 0.75)
-        c_h = hip().seg_counts(lg.to(dev), tg.to(dev), 0.75)
-        # a logit within one ulp of the threshold may flip: allow a handful of pixels
-        return float((c_h.cpu() - c_r).abs().max()) / 4.0, 1.0
+        lg = 2 * torch.randn(B, C, S, W, generator=g) + 1.0
+        tg = (torch.rand(B, C, S, W, generator=g) > 0.6).float()
+        flat = lg.permute(1, 0, 2, 3).reshape(C, -1)             # (copies: written back below)
+        t0 = math.log(thr / (1 - thr))
+        if flat.shape[1] >= 2:
+            flat[:, 0], flat[:, 1] = t0 + 2e-4, t0 - 2e-4
+        else:
+            flat[0::2, 0], flat[1::2, 0] = t0 + 2e-4, t0 - 2e-4
+        lg = flat.reshape(C, B, S, W).permute(1, 0, 2, 3).contiguous()
+        if edge:
+            kind = torch.randint(0, 8, tg.shape, generator=g)
+            for k, v in ((0, 0.5), (1, 1e-30), (2, -0.0), (3, -1.0)):
+                tg[kind == k] = v
+            tg[0, 0] = 0.0
+            tg[B - 1, C - 1] = 1.0
+        near = (torch.sigmoid(lg.double()) - thr).abs() <= UNDECIDED
+        lg[near] += 1e-2
+        assert not bool(((torch.sigmoid(lg.double()) - thr).abs() <= UNDECIDED).any()), "undecided logit in the test input"
+        c_r = SPEC.seg_counts(lg.double(), tg.double(), thr)
+        assert torch.equal(c_r, SPEC.seg_counts(lg, tg, thr))           # (decided in float64 = decided in fp32)
+        c_h = hip().seg_counts(ro_dev(lg, dev), ro_dev(tg, dev), thr)
+        return float((c_h.cpu() - c_r).abs().max()), 0.0
     return run
+
+
+def retrify_errors(B, h, w, lg, std_map, mean_map, w_h, m0_h, m1_h):
+    """Mode 2 has two thresholded factors, sigmoid(logit) > 0.75 and bilinear(std) < 0.04.  A pixel is decided where the float64
+    statement keeps all four of them (two channels each) further than UNDECIDED from the threshold.  Input condition, asserted
+    here on the CPU: at most 0.5 % of the pixels are undecided.  -> [mask mismatches on decided pixels, weight error on decided
+    pixels against the float64 statement]; undecided pixels are left out, the device results are taken as they are."""
+    F = torch.nn.functional
+    p = torch.sigmoid(lg.double()).reshape(B, h, w, 2)
+    sd = F.interpolate(std_map.double(), size=(h, w), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    und = (((p - 0.75).abs() <= UNDECIDED) | ((sd - 0.04).abs() <= UNDECIDED)).any(-1).reshape(-1)
+    assert float(und.double().mean()) <= 0.005, "%d of %d pixels undecided in the test input" % (int(und.sum()), und.numel())
+    dec = ~und
+    w64, m0_64, m1_64 = SPEC.proto_weights(2, B, h, w, logits=lg.double(), std_map=std_map.double(), mean_map=mean_map.double())
+    wrong = int((m0_h.cpu().double() != m0_64)[dec].sum() + (m1_h.cpu().double() != m1_64)[dec].sum())
+    return [float(wrong), rel(w_h.cpu()[dec], w64[dec])]
 
 
 def case_proto(B, h, C, mode, seed=12):
@@ -916,14 +959,12 @@ def case_proto(B, h, C, mode, seed=12):
             lg = padded(P, 2, g)
             lg.copy_(lgn.permute(0, 2, 3, 1).reshape(P, 2))
             w_r, m0_r, m1_r = SPEC.proto_weights(2, B, h, h, logits=lg, std_map=sd_r, mean_map=mn_r)
-            # feed the HIP weights kernel the reference std/mean so that threshold flips cannot differ
-            w_h, m0_h, m1_h = K.proto_weights(2, B, h, h, logits=to_dev(lg, dev), std_map=sd_r.to(dev), mean_map=mn_r.to(dev))
-            flips = int((m0_h.cpu() != m0_r).sum() + (m1_h.cpu() != m1_r).sum())
-            assert flips <= 4, "reliability mask differs on %d pixels" % flips
-            if flips:
-                w_h = w_r.to(dev)
+            # the HIP weights kernel reads the reference std / mean maps: one input, one float64 statement of it
+            w_h, m0_h, m1_h = K.proto_weights(2, B, h, h, logits=to_dev(lg, dev), std_map=ro_dev(sd_r, dev), mean_map=ro_dev(mn_r, dev))
+            errs += retrify_errors(B, h, h, lg, sd_r, mn_r, w_h, m0_h, m1_h)
             assert 0.05 < float(m0_r.mean()) / 2 < 0.999, "degenerate mask in the test input"
-        errs.append(rel(w_h, w_r))
+        if mode != 2:
+            errs.append(rel(w_h, w_r))
         s_r = torch.zeros(4, C + 1, dtype=torch.float64)
         SPEC.proto_reduce(feat, w_r, s_r)
         s_h = out_dev((4, C + 1), torch.float64, dev, fill=0)
@@ -1822,6 +1863,240 @@ WINDOW_CASES = [
     ("coefficient window [1024, 1280) of [4][1280]", case_window_coef(1024)),
 ]
 WINDOW_CASES = [(name, footprinted(fn)) for name, fn in WINDOW_CASES]
+
+
+# ---------------------------------------------------------------- losses_proto.hip at its edges
+# The training-step glue at the shapes where its kernels change behaviour: every LDS split of the prototype reduce (C = 1 .. 1024,
+# PP = 256 .. 1 pixel lanes), a workgroup filled exactly and by one pixel more, the grid-stride step of the backward kernel
+# (P > 32768), h != w and non-integral H / h in the weights, inputs below one workgroup and one wave in the block sums.  The
+# reference is the float64 evaluation of the statement: SpecKernels' torch expressions on double copies of the fp32 inputs
+# (proto_reduce / proto_bwd / feat_* are float64 there already).  Tolerances are those of the families' first cases.
+def _f64(*ts):
+    return tuple(None if t is None else t.double() for t in ts)
+
+
+def _factor(P):
+    """B, h, w with B * h * w = P and h != w where P allows it (the weights need a pixel grid)"""
+    for B in (3, 2, 5, 1):
+        if P % B == 0:
+            n = P // B
+            h = max(d for d in range(1, int(n ** 0.5) + 1) if n % d == 0)
+            return B, h, n // h
+    raise AssertionError(P)
+
+
+def proto_edge_weights(P, g):
+    """reference weights [P, 4] of the three modes on a B x h x w grid of P pixels (inputs of the reduce, not compared)"""
+    B, h, w = _factor(P)
+    H, W = 2 * h + 1, w + 3
+    mp = (torch.rand(B, 2, H, W, generator=g) > 0.6).float()
+    lg = 2.0 * torch.randn(P, 2, generator=g) + 1.1              # sigmoid > 0.75 on about half of the pixels
+    sd, mn = 0.06 * torch.rand(B, 2, H, W, generator=g), torch.rand(B, 2, H, W, generator=g)
+    return [SPEC.proto_weights(0, B, h, w, map_=mp)[0], SPEC.proto_weights(1, B, h, w, logits=lg)[0],
+            SPEC.proto_weights(2, B, h, w, logits=lg, std_map=sd, mean_map=mn)[0]]
+
+
+def case_proto_edge(P, C, seed=90):
+    """uda_proto_reduce / finalize / bwd at one (P, C), with the reference weights of all three modes: sums with the count column,
+    centroids, d_feat accumulated into live data and written over NaN, d_w."""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        feat = padded(P, C, g)
+        feat += 0.25                                             # centroids away from 0: every class has a scale of its own
+        fh = ro_dev(feat, dev)
+        errs = []
+        for mode, w_r in enumerate(proto_edge_weights(P, g)):
+            s_r = torch.zeros(4, C + 1, dtype=torch.float64)
+            SPEC.proto_reduce(feat, w_r, s_r)
+            assert float(s_r[:, C].min()) >= 1.0, "a class without weight in the test input (mode %d)" % mode
+            s_h = out_dev((4, C + 1), torch.float64, dev, fill=0, name="sums mode %d" % mode)
+            wh = ro_dev(w_r, dev)
+            K.proto_reduce(fh, wh, s_h)
+            errs += [rel(s_h[:, :C], s_r[:, :C]), rel(s_h[:, C], s_r[:, C]), rel(K.proto_finalize(s_h), SPEC.proto_finalize(s_r))]
+            dC = torch.randn(4, C, generator=g)
+            base = padded(P, C, g)
+            df_r = base.clone()
+            dw_r = SPEC.proto_bwd(feat, w_r, s_r, dC, df_r, True, True)
+            df_h = to_dev(base, dev)
+            dw_h = K.proto_bwd(fh, wh, ro_dev(s_r, dev), ro_dev(dC, dev), df_h, True, True)
+            errs += [rel(df_h, df_r), rel(dw_h, dw_r)]
+            over = padded(P, C, g)
+            over.fill_(float("nan"))                             # overwriting: nothing of the old content may survive
+            df_r = torch.empty(P, C)
+            SPEC.proto_bwd(feat, w_r, s_r, dC, df_r, False, False)
+            df_h = to_dev(over, dev)
+            K.proto_bwd(fh, wh, ro_dev(s_r, dev), ro_dev(dC, dev), df_h, False, False)
+            errs.append(rel(df_h, df_r))
+        DETAIL.clear()
+        DETAIL.update({"errs": ["%.1e" % e for e in errs]})
+        return max(errs), 3e-5
+    return run
+
+
+def case_proto_weights(mode, B, H, W, h, w, seed=91):
+    """uda_proto_weights on an (H, W) -> (h, w) geometry.  Mode 0: F.interpolate(mode="nearest"), exact.  Mode 1: [P, 2] logits
+    in a matrix of row stride 12.  Mode 2: align_corners bilinear of i.i.d. std / mean maps, compared on decided pixels."""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        P = B * h * w
+        if mode == 0:
+            mp = (torch.rand(B, 2, H, W, generator=g) > 0.5).float()
+            w_r, _, _ = SPEC.proto_weights(0, B, h, w, map_=mp)
+            w_h, _, _ = K.proto_weights(0, B, h, w, map_=ro_dev(mp, dev))
+            return float((w_h.cpu() - w_r).abs().max()), 0.0
+        lg = padded(P, 6, g, scale=2.0)[:, :2]
+        if mode == 1:
+            w_r, _, _ = SPEC.proto_weights(1, B, h, w, logits=lg.double())
+            w_h, _, _ = K.proto_weights(1, B, h, w, logits=ro_dev(lg, dev))
+            return rel(w_h, w_r), 3e-5
+        sd, mn = 0.08 * torch.rand(B, 2, H, W, generator=g), torch.rand(B, 2, H, W, generator=g)
+        w_h, m0_h, m1_h = K.proto_weights(2, B, h, w, logits=ro_dev(lg, dev), std_map=ro_dev(sd, dev), mean_map=ro_dev(mn, dev))
+        errs = retrify_errors(B, h, w, lg, sd, mn, w_h, m0_h, m1_h)
+        m0 = SPEC.proto_weights(2, B, h, w, logits=lg, std_map=sd, mean_map=mn)[1]
+        assert 0.05 < float(m0.mean()) / 2 < 0.999, "degenerate mask in the test input"
+        return max(errs), 3e-5
+    return run
+
+
+SEG_SATURATED = ((40., 0.), (-40., 1.), (110., 0.), (-110., 1.),      # wrong and certain: the -100 clamp of the log, the 1e-12 floor
+                 (17., 1.), (-17., 0.), (90., 1.), (-90., 0.),        # right and certain: the clamped log meets the factor 0
+                 (40., 1.), (-40., 0.), (110., 1.), (-110., 0.))
+# (|logit| = 17 and 90 come with the target on their side only: there fp32 rounds the sigmoid to exactly 1 resp. 0 while float64
+# does not, so with the opposite target the fp32 statement itself says 100 where float64 says 17 resp. 90)
+
+
+def case_seg_loss_edge(B, S, seed=92):
+    """uda_seg_loss_fwd / bwd below one workgroup (1 x 2 x 5 x 5) and on a ragged size, saturated logits with targets of exactly
+    0 and 1, against the float64 statement."""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        o = 3 * torch.randn(B, 2, S, S, generator=g)
+        b = 2 * torch.randn(B, 1, S, S, generator=g)
+        tm = (torch.rand(B, 2, S, S, generator=g) > 0.5).float()
+        tb = torch.rand(B, 1, S, S, generator=g)
+        sat = torch.tensor(SEG_SATURATED)
+        o.view(-1)[:len(sat)], tm.view(-1)[:len(sat)] = sat[:, 0], sat[:, 1]
+        b.view(-1)[:4], tb.view(-1)[:4] = torch.tensor([60., -60., 60., -60.]), torch.tensor([0., 1., 1., 0.])
+        gs = torch.tensor([0.37])
+        l_r = SPEC.seg_loss_fwd(*_f64(o, tm, b, tb))
+        do_r, db_r = SPEC.seg_loss_bwd(*_f64(o, tm, b, tb, gs))
+        args = [ro_dev(t, dev) for t in (o, tm, b, tb)]
+        l_h = K.seg_loss_fwd(*args)
+        do_h, db_h = K.seg_loss_bwd(*args, ro_dev(gs, dev))
+        return max(rel(l_h, l_r), rel(do_h, do_r), rel(db_h, db_r)), 2e-5
+    return run
+
+
+def case_mc_stats_edge(B, H, W, seed=93):
+    """uda_mc_stats on n = B * 2 * H * W (no multiple of the 1024 elements of a workgroup's step): a third of the pixels with
+    eight identical passes (std exactly 0), logits of +-100 both constant and alternating over the passes."""
+    def run(dev):
+        T = 8
+        g = gen(seed)
+        base = 3.0 * torch.randn(1, B, 2, H, W, generator=g)
+        same = torch.rand(1, B, 2, H, W, generator=g) < 1.0 / 3
+        p = base + 1.5 * torch.randn(T, B, 2, H, W, generator=g) * (~same).float()
+        sign = torch.tensor([1., -1.] * (T // 2)).view(T, 1)
+        pf = p.view(T, -1)
+        pf[:, 0:2], pf[:, 2:4] = torch.tensor([100., -100.]), 100. * sign
+        same.view(-1)[0:2], same.view(-1)[2:4] = True, False
+        preds = p.reshape(T * B, 2, H, W)
+        assert preds.shape[0] * 2 * H * W // T % 1024 != 0
+        sd_r, mn_r = SPEC.mc_stats(preds.double(), T)
+        sd_h, mn_h = hip().mc_stats(ro_dev(preds, dev), T)
+        flat = sd_h.cpu()[same[0]]
+        exact = bool((flat == 0).all())                          # (NaN and the tiny std of a mean that misses h by an ulp both fail this)
+        return max(rel(sd_h, sd_r), rel(mn_h, mn_r), 0.0 if exact else float("inf")), 3e-5
+    return run
+
+
+def case_adv_loss_edge(n1, n2, label, scale, seed=94):
+    """uda_adv_loss_fwd / bwd with one element per map and with one below / one above a workgroup, against float64"""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        d1, d2 = 3 * torch.randn(n1, generator=g), 3 * torch.randn(n2, generator=g)
+        sat = torch.tensor([40., -40., 100., -100.])
+        d1[-4:], d2[:4] = sat[:n1], sat[:n2]
+        gi = torch.tensor([1.7])
+        l_r = SPEC.adv_loss_fwd(d1.double(), d2.double(), label, scale)
+        a_r, b_r = SPEC.adv_loss_bwd(d1.double(), d2.double(), label, scale, gi.double())
+        dh = ro_dev(d1, dev), ro_dev(d2, dev)
+        l_h = K.adv_loss_fwd(*dh, label, scale)
+        a_h, b_h = K.adv_loss_bwd(*dh, label, scale, ro_dev(gi, dev))
+        return max(rel(l_h, l_r), rel(a_h, a_r), rel(b_h, b_r)), 2e-6
+    return run
+
+
+def case_proto_align_edge(C, seed=95):
+    """uda_proto_align_fwd / bwd at one channel, at a full workgroup and one more, and at four strides: the EMA bit for bit (the
+    fp32 expression is the statement), the losses and gradients against float64 on that EMA."""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        cs, ct, ps, pt = (torch.randn(4, C, generator=g) for _ in range(4))
+        ns_r, nt_r, _ = SPEC.proto_align_fwd(cs, ct, ps, pt, 0.9)
+        _, _, l_r = SPEC.proto_align_fwd(ns_r.double(), nt_r.double(), None, None, 0.9)
+        gi = torch.tensor([0.37])
+        a_r, b_r = SPEC.proto_align_bwd(ns_r.double(), nt_r.double(), gi.double(), 0.9, 0.9)
+        ns_h, nt_h, l_h = K.proto_align_fwd(*(ro_dev(t, dev) for t in (cs, ct, ps, pt)), 0.9)
+        a_h, b_h = K.proto_align_bwd(ns_h, nt_h, ro_dev(gi, dev), 0.9, 0.9)
+        exact = torch.equal(ns_h.cpu(), ns_r) and torch.equal(nt_h.cpu(), nt_r)
+        return max(rel(l_h, l_r), rel(a_h, a_r), rel(b_h, b_r), 0.0 if exact else 1.0), 2e-6
+    return run
+
+
+def case_adam_edge(n, seed=96):
+    """uda_adam_step below and just above one workgroup, steps 1, 2 and 100000 (both bias corrections round to 1), against float64.
+    The last max(1, n // 4) elements (n > 1) have g = m = v = 0: their update must be exactly 0, not 0 / 0."""
+    def run(dev):
+        g = gen(seed)
+        p, gr = 0.05 * torch.randn(n, generator=g), torch.randn(n, generator=g)
+        m, v = 0.1 * torch.randn(n, generator=g), torch.rand(n, generator=g) * 0.01
+        z = slice(n - max(1, n // 4), n) if n > 1 else slice(0, 0)
+        gr[z] = m[z] = v[z] = 0.0
+        p0 = p.clone()
+        ph, mh, vh, gh = out_like(p, dev), out_like(m, dev), out_like(v, dev), ro_dev(gr, dev)
+        p, gr, m, v = _f64(p, gr, m, v)
+        for step in (1, 2, 100000):
+            SPEC.adam_step(p, gr, m, v, 1e-3, 0.9, 0.99, 1e-8, step)
+            hip().adam_step(ph, gh, mh, vh, 1e-3, 0.9, 0.99, 1e-8, step)
+        still = torch.equal(ph.cpu()[z], p0[z]) and not bool(mh.cpu()[z].any()) and not bool(vh.cpu()[z].any())
+        return max(rel(ph, p), rel(mh, m), rel(vh, v), 0.0 if still else float("inf")), 1e-5
+    return run
+
+
+TAIL_P = 32768 + 37         # proto_bwd_kernel: 8192 workgroups x 4 waves, one pixel per wave and step; 37 pixels take a second step
+LOSS_PROTO_EDGE_CASES = [("proto edge P=%d C=%d (PP=%d)" % (P, C, 256 // ((C + 3) // 4)), case_proto_edge(P, C))
+                         for P, C in ((300, 1), (300, 4), (300, 7), (1000, 60), (1000, 61), (96, 305), (97, 305), (40, 1024))]
+LOSS_PROTO_EDGE_CASES += [
+    ("proto edge P=%d C=12 (PP=85, grid-stride tail)" % TAIL_P, case_proto_edge(TAIL_P, 12)),
+    ("feat dot4/rank4 P=%d C=12 (grid-stride tail)" % TAIL_P, case_feat4(TAIL_P, 12)),
+    ("proto weights hard 50x37 -> 13x9", case_proto_weights(0, 2, 50, 37, 13, 9)),
+    ("proto weights hard 7x5 -> 7x5", case_proto_weights(0, 2, 7, 5, 7, 5)),
+    ("proto weights hard 3x5 -> 8x8 (upsampling)", case_proto_weights(0, 2, 3, 5, 8, 8)),
+    ("proto weights hard 9x9 -> 1x1", case_proto_weights(0, 2, 9, 9, 1, 1)),
+    ("proto weights soft 13x9 ldl=12", case_proto_weights(1, 3, 0, 0, 13, 9)),
+    ("proto weights retrify 50x37 -> 13x9", case_proto_weights(2, 3, 50, 37, 13, 9)),
+    ("proto weights retrify 20x20 -> 1x6", case_proto_weights(2, 3, 20, 20, 1, 6)),
+    ("proto weights retrify 20x20 -> 6x1", case_proto_weights(2, 3, 20, 20, 6, 1)),
+    ("seg loss 1x5 (below one workgroup)", case_seg_loss_edge(1, 5)),
+    ("seg loss 3x33", case_seg_loss_edge(3, 33)),
+    ("seg counts C=1 3x97x53", case_seg_counts(3, 97, C=1, W=53, edge=True, seed=97)),
+    ("seg counts C=2 3x97x53", case_seg_counts(3, 97, C=2, W=53, edge=True, seed=98)),
+    ("seg counts C=64 3x1x1", case_seg_counts(3, 1, C=64, edge=True, seed=99)),
+    ("seg counts C=64 1x1x1", case_seg_counts(1, 1, C=64, edge=True, seed=100)),
+    ("mc stats 3x2x37x29", case_mc_stats_edge(3, 37, 29)),
+    ("adv_loss 1 + 1", case_adv_loss_edge(1, 1, 1.0, 0.01)),
+    ("adv_loss 255 + 257", case_adv_loss_edge(255, 257, 0.0, 1.0)),
+] + [("proto_align C=%d EMA (float64)" % C, case_proto_align_edge(C)) for C in (1, 256, 257, 1000)] \
+  + [("adam n=%d steps 1, 2, 100000" % n, case_adam_edge(n)) for n in (1, 3, 255, 257)]
+CASES += LOSS_PROTO_EDGE_CASES
+# the two older cases that this section's rules rewrote: exact counts, device masks and weights taken as they are
+LOSS_PROTO_CHANGED = ("seg counts 3x96", "proto retrify C=305 h=32")
 
 
 # every case begins with a cleared footprint registry and runs with guarded workspaces (footprint_violations() after it)

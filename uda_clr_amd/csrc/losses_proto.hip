@@ -13,6 +13,7 @@
 //                  (the reference reads the feature 8 times)                  utils/Utils.py:114-130,207-223
 //   proto backward d feature / d weights of centroid = sum / count
 #include "common.h"
+#include "proto_plan.h"
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -139,16 +140,22 @@ __global__ __launch_bounds__(256) void mc_stats_kernel(const float* __restrict__
                                                        float* __restrict__ mean_map) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-        float h[T];
-        float m1 = 0.f, mh = 0.f;
+        float h[T], s[T];
+        float m1 = 0.f;
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const float x = preds[(int64_t)t * n + e];
             m1 += sigmoidf_(x);
-            h[t] = sigmoidf_(x * 0.5f);
-            mh += h[t];
+            h[t] = s[t] = sigmoidf_(x * 0.5f);
         }
-        mh /= (float)T;
+        // mean of h by pairwise sums: T equal values add up to exactly T * h (every step doubles), so the deviations and the
+        // std of identical passes are exactly 0 like torch.std's; a running sum h, 2h, 3h, ... rounds at 3h and misses h by an ulp
+        static_assert((T & (T - 1)) == 0, "mc_stats_kernel: pairwise mean needs T a power of two");
+#pragma unroll
+        for (int w = T / 2; w > 0; w >>= 1)
+#pragma unroll
+            for (int i = 0; i < w; ++i) s[i] = s[2 * i] + s[2 * i + 1];
+        const float mh = s[0] / (float)T;
         float ss = 0.f;
 #pragma unroll
         for (int t = 0; t < T; ++t) ss += (h[t] - mh) * (h[t] - mh);
@@ -248,8 +255,9 @@ extern "C" int uda_proto_weights(int mode, int B, int h, int w, int H, int W, co
 #define PR_ITER 32
 __global__ __launch_bounds__(256) void proto_reduce_kernel(const float* __restrict__ f, int64_t ldf, int64_t P, int C,
                                                            const float* __restrict__ wts, float* __restrict__ part) {
-    __shared__ float red[4 * 1024 + 64];
-    const int G = (C + 3) >> 2, PP = 256 / G;                 // C = 305: G = 77, PP = 3
+    // channel sums, then the weight totals: sized for every C in [1, PR_MAX_C] (proto_plan.h holds the arithmetic and asserts it)
+    __shared__ float red[PR_LDS_SUM_FLOATS + PR_LDS_CNT_FLOATS];
+    const int G = (C + 3) >> 2, PP = PR_THREADS / G;          // C = 305: G = 77, PP = 3
     const int tid = threadIdx.x, cg = tid % G, pl = tid / G;
     const bool active = pl < PP;
     const int c0 = cg * 4;
@@ -280,7 +288,7 @@ __global__ __launch_bounds__(256) void proto_reduce_kernel(const float* __restri
         for (int k = 0; k < 4; ++k) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) red[(k * PP + pl) * Cp + c0 + j] = acc[k][j];
-            if (cg == 0) red[4 * 1024 + k * PP + pl] = cnt[k];
+            if (cg == 0) red[PR_LDS_SUM_FLOATS + k * PP + pl] = cnt[k];
         }
     }
     __syncthreads();
@@ -289,7 +297,7 @@ __global__ __launch_bounds__(256) void proto_reduce_kernel(const float* __restri
         const int k = e / C1, c = e % C1;
         float t = 0.f;
         if (c < C) for (int p = 0; p < PP; ++p) t += red[(k * PP + p) * Cp + c];
-        else for (int p = 0; p < PP; ++p) t += red[4 * 1024 + k * PP + p];
+        else for (int p = 0; p < PP; ++p) t += red[PR_LDS_SUM_FLOATS + k * PP + p];
         part[((int64_t)blockIdx.x * 4 + k) * C1 + c] = t;
     }
 }
@@ -302,7 +310,7 @@ extern "C" uint64_t uda_proto_workspace_bytes(int64_t P, int C) { return (uint64
 extern "C" int uda_proto_reduce(const float* feat, int64_t ldf, int64_t P, int C, const float* wts, double* sums,
                                 float* workspace, uint64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    UDA_REQUIRE(feat && uda_aligned16(feat) && ldf % 4 == 0 && ldf >= ((C + 3) / 4) * 4 && C > 0 && C <= 1024 && P > 0 && wts &&
+    UDA_REQUIRE(feat && uda_aligned16(feat) && ldf % 4 == 0 && ldf >= ((C + 3) / 4) * 4 && C > 0 && C <= PR_MAX_C && P > 0 && wts &&
                     uda_aligned16(wts) && sums, "uda_proto_reduce: bad args");
     UDA_REQUIRE(workspace && workspace_bytes >= uda_proto_workspace_bytes(P, C), "uda_proto_reduce: workspace too small");
     const int nwg = proto_nwg(P, C);
