@@ -36,7 +36,8 @@ import sys
 import numpy as np
 import torch
 
-from . import ops
+from . import inference, ops
+from .inference import UNCERTAINTY_U8_SCALE  # noqa: F401  (``predict`` and the tests take it from here)
 from .utils import Utils, metrics
 
 FIELDS = ("cup_dice", "disc_dice", "cup_assd", "disc_assd", "cup_hd", "disc_hd")
@@ -54,7 +55,6 @@ MORPHOMETRY_FIELDS = tuple("%s_%s" % (x, s) for x in ("hcdr", "acdr", "rdr_min")
 
 
 CALIBRATION_FIELDS = ("cup_ece", "disc_ece", "cup_brier", "disc_brier")
-UNCERTAINTY_U8_SCALE = 1600.0       # uncertainty/<stem>.png: grey = min(255, floor(std * 1600)), the trainer's 0.04 at grey 64
 
 
 def uncertainty_fields(report_edges=(0.04,)):
@@ -176,10 +176,7 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
     profiled = extra_fields(hd95, tolerances, cdr)
     mc_passes = int(mc_passes)
     tta_uncertainty = bool(tta_uncertainty)
-    if tta_uncertainty and mc_passes:
-        raise ValueError("tta_uncertainty=True and mc_passes=%d: one uncertainty fills the risk table, not both" % mc_passes)
-    if tta_uncertainty and tta is None:
-        raise ValueError("tta_uncertainty=True needs tta, a view list (got tta=None)")
+    inference.check_uncertainty_args(tta, tta_uncertainty, mc_passes)
     if tta is not None:
         from . import tta as tta_views
         if not isinstance(tta, str):
@@ -189,89 +186,64 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
     extra = extra_fields(hd95, tolerances, cdr, morphometry, calibration, mc_passes, report_edges, tta_uncertainty)
     if with_unc:
         _edge_index(unc_edges, report_edges)
-    if mc_passes:
-        if mc_logits is None:
-            mc_logits = getattr(model, "mc_inference_logits", None)
-        if mc_logits is None:
-            raise ValueError("mc_passes needs a model with mc_inference_logits (DeepLab) or an mc_logits callable")
+    mc_logits = inference.resolve_mc_logits(model, mc_passes, mc_logits)
     pooled_rel = pooled_risk = None
     dev = torch.device("cuda") if torch.cuda.is_available() else None
-    was_training = getattr(model, "training", False)
-    if hasattr(model, "eval"):
-        model.eval()
     per_image = []
-    try:
-        with torch.no_grad():
-            for sample in loader:
-                if 'image' not in sample or 'map' not in sample:
-                    raise ValueError("evaluate() takes decoded float batches {'image', 'map'} (UDA_CLR_DEVICE_INPUT unset or 0)")
-                image, target = sample['image'], sample['map']
-                if dev is not None:
-                    image, target = image.to(dev), target.to(dev)
-                fused = None
-                if tta is None:
-                    out = model(image)
-                    logits = out[0] if isinstance(out, (tuple, list)) else out
-                    prob = torch.sigmoid(logits.float())
-                else:
-                    views = tta_views.normalise_views(tta, image.shape[-2], image.shape[-1])
-                    used_views = views if used_views is None else used_views
-                    fused = tta_views.tta_predict(model, image, views, outputs=("mean", "std") if tta_uncertainty else ("mean",),
-                                                  u8_scale=UNCERTAINTY_U8_SCALE if tta_uncertainty and save_dir is not None else None)
-                    prob = fused["mean"]
-                if postprocess:
-                    pred = Utils.postprocessing_batch(prob, threshold, dataset)
-                else:
-                    thr_cup, thr_disc = (0.1, 0.5) if dataset[0] == 'D' else (threshold, threshold)
-                    pred = torch.stack([prob[:, 0] > thr_cup, prob[:, 1] > thr_disc], 1)
-                if profiled:                                                         # the batch's one copy to the host, either way
-                    table, counts, profile = ops.surface_profile(pred, target > 0.5, percentiles=(95,) if hd95 else (), tolerances=tolerances)
-                else:
-                    table, counts = ops.surface_distances(pred, target > 0.5)
-                dice = metrics.dice_per_image(counts)
-                sm = metrics.surface_metrics_from_table(table)
-                more = {}
-                if hd95:
-                    h = metrics.percentile_distance_from_profile(table, profile)["hd_p"][..., 0]
-                    more["cup_hd95"], more["disc_hd95"] = h[:, 0], h[:, 1]
-                if tolerances:
-                    nsd = metrics.surface_dice_from_profile(table, profile)
-                    for t, tau in enumerate(tolerances):
-                        more["cup_nsd_%g" % tau], more["disc_nsd_%g" % tau] = nsd[:, 0, t], nsd[:, 1, t]
-                if cdr:
-                    more.update(metrics.vertical_cdr_from_profile(profile))
-                if morphometry:
-                    more.update(morphometry_columns(pred, target > 0.5, sectors))
-                unc = None
-                if mc_passes:
-                    unc = ops.mc_uncertainty(mc_logits(image, mc_passes), outputs=("std",),
-                                             u8_scale=UNCERTAINTY_U8_SCALE if save_dir is not None else None)
-                if tta_uncertainty:
-                    unc = fused
-                if calibration or with_unc:                                          # both tables in one call, one copy
-                    tables = ops.selective_tables(prob if calibration else None, unc["std"] if with_unc else None, pred, target > 0.5,
-                                                  bins=bins, edges=unc_edges)
-                    if calibration:
-                        more.update(calibration_columns(tables["rel"]))
-                        pooled_rel = tables["rel"].sum(0) + (0 if pooled_rel is None else pooled_rel)
-                    if with_unc:
-                        more.update(uncertainty_columns(tables["risk"], unc_edges, report_edges))
-                        pooled_risk = tables["risk"].sum(0) + (0 if pooled_risk is None else pooled_risk)
-                names = _names(sample, dice.shape[0], len(per_image))
-                if save_dir is not None:
-                    Utils.save_per_img_batch(image, save_dir, names, prob)
-                    Utils.save_mask_batch(pred, save_dir, names)
-                    if with_unc:
-                        Utils.save_uncertainty_batch(unc["std_u8"], save_dir, names)
-                for i, name in enumerate(names):
-                    per_image.append({"img_name": name,
-                                      "cup_dice": float(dice[i, 0]), "disc_dice": float(dice[i, 1]),
-                                      "cup_assd": float(sm["assd"][i, 0]), "disc_assd": float(sm["assd"][i, 1]),
-                                      "cup_hd": float(sm["hd"][i, 0]), "disc_hd": float(sm["hd"][i, 1])})
-                    per_image[-1].update({k: float(more[k][i]) for k in extra})
-    finally:
-        if was_training and hasattr(model, "train"):
-            model.train()
+    with inference.eval_mode(model):
+        for sample in loader:
+            if 'image' not in sample or 'map' not in sample:
+                raise ValueError("evaluate() takes decoded float batches {'image', 'map'} (UDA_CLR_DEVICE_INPUT unset or 0)")
+            image, target = sample['image'], sample['map']
+            if dev is not None:
+                image, target = image.to(dev), target.to(dev)
+            views = None if tta is None else tta_views.normalise_views(tta, image.shape[-2], image.shape[-1])
+            used_views = views if used_views is None else used_views
+            prob, unc = inference.probabilities(model, image, views, tta_uncertainty, mc_passes, mc_logits, std_u8=save_dir is not None)
+            if postprocess:
+                pred = Utils.postprocessing_batch(prob, threshold, dataset)
+            else:
+                thr_cup, thr_disc = (0.1, 0.5) if dataset[0] == 'D' else (threshold, threshold)
+                pred = torch.stack([prob[:, 0] > thr_cup, prob[:, 1] > thr_disc], 1)
+            if profiled:                                                         # the batch's one copy to the host, either way
+                table, counts, profile = ops.surface_profile(pred, target > 0.5, percentiles=(95,) if hd95 else (), tolerances=tolerances)
+            else:
+                table, counts = ops.surface_distances(pred, target > 0.5)
+            dice = metrics.dice_per_image(counts)
+            sm = metrics.surface_metrics_from_table(table)
+            more = {}
+            if hd95:
+                h = metrics.percentile_distance_from_profile(table, profile)["hd_p"][..., 0]
+                more["cup_hd95"], more["disc_hd95"] = h[:, 0], h[:, 1]
+            if tolerances:
+                nsd = metrics.surface_dice_from_profile(table, profile)
+                for t, tau in enumerate(tolerances):
+                    more["cup_nsd_%g" % tau], more["disc_nsd_%g" % tau] = nsd[:, 0, t], nsd[:, 1, t]
+            if cdr:
+                more.update(metrics.vertical_cdr_from_profile(profile))
+            if morphometry:
+                more.update(morphometry_columns(pred, target > 0.5, sectors))
+            if calibration or with_unc:                                          # both tables in one call, one copy
+                tables = ops.selective_tables(prob if calibration else None, unc["std"] if with_unc else None, pred, target > 0.5,
+                                              bins=bins, edges=unc_edges)
+                if calibration:
+                    more.update(calibration_columns(tables["rel"]))
+                    pooled_rel = tables["rel"].sum(0) + (0 if pooled_rel is None else pooled_rel)
+                if with_unc:
+                    more.update(uncertainty_columns(tables["risk"], unc_edges, report_edges))
+                    pooled_risk = tables["risk"].sum(0) + (0 if pooled_risk is None else pooled_risk)
+            names = _names(sample, dice.shape[0], len(per_image))
+            if save_dir is not None:
+                Utils.save_per_img_batch(image, save_dir, names, prob)
+                Utils.save_mask_batch(pred, save_dir, names)
+                if with_unc:
+                    Utils.save_uncertainty_batch(unc["std_u8"], save_dir, names)
+            for i, name in enumerate(names):
+                per_image.append({"img_name": name,
+                                  "cup_dice": float(dice[i, 0]), "disc_dice": float(dice[i, 1]),
+                                  "cup_assd": float(sm["assd"][i, 0]), "disc_assd": float(sm["assd"][i, 1]),
+                                  "cup_hd": float(sm["hd"][i, 0]), "disc_hd": float(sm["hd"][i, 1])})
+                per_image[-1].update({k: float(more[k][i]) for k in extra})
     cols = {k: np.array([r[k] for r in per_image], np.float64) for k in FIELDS + extra}
     mean = {k: (float(np.nanmean(v)) if np.isfinite(v).any() else float("nan")) for k, v in cols.items()}
     res = {"per_image": per_image, "mean": mean, "n_images": len(per_image),
@@ -280,12 +252,9 @@ def evaluate(model, loader, dataset='G', threshold=0.75, postprocess=True, hd95=
         res["extra_fields"] = extra
     if calibration and pooled_rel is not None:
         res["calibration"] = dict(_lists(metrics.calibration_from_table(pooled_rel)), rel=pooled_rel.tolist(), bins=int(bins))
-    if mc_passes and pooled_risk is not None:
+    if pooled_risk is not None:
         res["risk_coverage"] = dict(_lists(metrics.selective_from_table(pooled_risk, unc_edges)), risk=pooled_risk.tolist(),
-                                    passes=mc_passes)
-    if tta_uncertainty and pooled_risk is not None:
-        res["risk_coverage"] = dict(_lists(metrics.selective_from_table(pooled_risk, unc_edges)), risk=pooled_risk.tolist(),
-                                    views=len(used_views))
+                                    **({"passes": mc_passes} if mc_passes else {"views": len(used_views)}))
     if tta is not None:
         res["tta"] = [list(v) for v in used_views] if used_views is not None else []
     return res

@@ -8,6 +8,7 @@ raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -212,6 +213,50 @@ def _mat(t: torch.Tensor, name="tensor"):
     return t.data_ptr(), t.stride(0)
 
 
+def check_side(what, *sides):
+    """every side a multiple of 16 in 16..1024: the sizes the generator and the resampling kernels take"""
+    if any(n % 16 or not 16 <= n <= 1024 for n in sides):
+        raise ValueError("%s %s: each side must be a multiple of 16 in 16..1024" % (what, " x ".join("%d" % n for n in sides)))
+
+
+# ---------------------------------------------------------------------- packed tables of the evaluation kernels
+# A kernel that fills several small tables gets them as views of ONE buffer of 8-byte words, so that one copy brings all of them to the
+# host.  A layout is the ordered list of (name, dtype, shape) of those views; ``packed_views`` carves the device buffer for the binding
+# and ``unpack_host`` carves its host copy for ``ops``, both from the same list.
+_I64, _F64 = torch.int64, torch.float64
+
+
+def surface_layout(B):
+    return [("table", _F64, (B, 2, 2, 3)), ("counts", _I64, (B, 2, 3))]
+
+
+def profile_layout(B, Q, T):
+    return surface_layout(B) + [("order", _I64, (B, 2, 3, Q, 2)), ("within", _I64, (B, 2, 2, T)), ("extent", _I64, (B, 2, 2, 2))]
+
+
+def morphometry_layout(B, K):
+    return [("moments", _I64, (B, 2, 6)), ("extent", _I64, (B, 2, 4)), ("overlap", _I64, (B,)), ("radial", _I64, (B, 2, K))]
+
+
+def selective_layout(B, M, K, prob=True, unc=True):
+    """``rel`` only with probabilities, ``risk`` only with uncertainties"""
+    return [("rel", _I64, (B, 2, M, 5))] * bool(prob) + [("risk", _I64, (B, 2, K, 4))] * bool(unc) + [("invalid", _I64, (B, 2, 2))]
+
+
+def packed_views(layout, device):
+    """-> (int64 buffer on ``device``, {name: its view of the layout's dtype and shape})"""
+    sizes = [math.prod(shape) for _, _, shape in layout]
+    packed = torch.empty(sum(sizes), dtype=_I64, device=device)
+    return packed, {name: part.view(dtype).view(shape) for (name, dtype, shape), part in zip(layout, torch.split(packed, sizes))}
+
+
+def unpack_host(layout, host):
+    """the host copy of a packed buffer (numpy int64) -> {name: numpy view}"""
+    import numpy as np
+    parts = np.split(host, np.cumsum([math.prod(shape) for _, _, shape in layout])[:-1])
+    return {name: part.view(str(dtype).split(".")[1]).reshape(shape) for (name, dtype, shape), part in zip(layout, parts)}
+
+
 class HipKernels:
     name = "hip"
 
@@ -270,6 +315,59 @@ class HipKernels:
     @staticmethod
     def _ws(like, nbytes):
         return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=like.device)
+
+    def _ck_masks(self, who, *masks):
+        """contiguous uint8 [B,2,H,W] device masks, all of one shape -> (B, H, W)"""
+        for t in masks:
+            self._dev(t)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != 2:
+                raise ValueError("%s: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (who, t.dtype, tuple(t.shape)))
+            if t.shape != masks[0].shape:
+                raise ValueError("%s: shapes differ: %s and %s" % (who, tuple(masks[0].shape), tuple(t.shape)))
+        B, _, H, W = masks[0].shape
+        return B, H, W
+
+    @staticmethod
+    def _named_maps(who, outputs, u8_scale, shape, device):
+        """the maps of ``mc_uncertainty`` / ``tta_fuse``: {name: f32 tensor of ``shape``} for the names in ``outputs``, with ``u8_scale``
+        also the uint8 'std_u8'; ``.get(name)`` is None for a map that was not asked for"""
+        names = ("mean", "std", "entropy", "mi")
+        outputs = tuple(outputs)
+        if any(o not in names for o in outputs) or not (outputs or u8_scale is not None):
+            raise ValueError("%s: outputs among %r (got %r)" % (who, names, outputs))
+        out = {o: torch.empty(shape, dtype=torch.float32, device=device) for o in names if o in outputs}
+        if u8_scale is not None:
+            out["std_u8"] = torch.empty(shape, dtype=torch.uint8, device=device)
+        return out
+
+    @staticmethod
+    def _u8_f32(outputs, B, S, device):
+        """the outputs of ``photo_reduce`` / ``roi_cut``: {'u8': uint8 [B,S,S,3], 'f32': f32 [B,3,S,S]} for the names in ``outputs``"""
+        if not outputs or set(outputs) - {"u8", "f32"}:
+            raise ValueError("outputs: 'u8', 'f32' or both, got %r" % (outputs,))
+        out = {}
+        if "u8" in outputs:
+            out["u8"] = torch.empty(B, S, S, 3, dtype=torch.uint8, device=device)
+        if "f32" in outputs:
+            out["f32"] = torch.empty(B, 3, S, S, dtype=torch.float32, device=device)
+        return out
+
+    def _propagate(self, name, n_flags, x, thresholds, sweeps):
+        """The entry ``name`` (uda_postprocess, uda_display_masks) on f32 [B,2,H,W] ``x`` -> uint8 [B,2,H,W].  Runs the tile-wise
+        propagations for ``sweeps`` launches and repeats with twice as many, up to six attempts, while the device reports unfinished
+        tiles in one of its ``n_flags`` flags; then raises."""
+        B, _, H, W = x.shape
+        out = torch.empty(B, 2, H, W, dtype=torch.uint8, device=x.device)
+        flags = torch.zeros(n_flags, dtype=torch.int32, device=x.device)
+        ws = self._ws(x, getattr(self.lib, name + "_workspace_bytes")(B, H, W))
+        n = int(sweeps) if sweeps else 2 * ((H + 31) // 32 + (W + 31) // 32) + 4
+        for _ in range(6):
+            self._ck(getattr(self.lib, name)(x.data_ptr(), B, H, W, *thresholds, n, out.data_ptr(), flags.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), self._stream()))
+            if int(flags.sum()) == 0:            # host sync: evaluation path only
+                return out
+            n *= 2
+        raise UdaError("%s: label propagation did not converge after %d sweeps" % (name, n // 2))   # the last attempt's
 
     # ------------------------------------------------------------------ weight layouts
     def relayout_ohwi(self, w):
@@ -1230,8 +1328,7 @@ class HipKernels:
         n, B = offsets.numel(), src_index.numel()
         if offsets.dtype != torch.int64 or src_index.dtype != torch.int64 or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2):
             raise ValueError("offsets int64 [n], sizes int32 [n, 2], src_index int64 [B]")
-        if S % 16 or not 16 <= S <= 1024:
-            raise ValueError("size must be a multiple of 16 in 16..1024, got %d" % S)
+        check_side("size", S)
         if not 1 <= B <= 8192:
             raise ValueError("batch of %d photographs outside 1..8192" % B)
         return n, B
@@ -1240,52 +1337,34 @@ class HipKernels:
         """the coarse S x S canvas of every selected photograph (uda_photo_reduce_u8) -> {'u8': uint8 [B,S,S,3], 'f32': f32 [B,3,S,S]}
         for the names in ``outputs``, and 'factor': int32 [B]"""
         n, B = self._ck_photos(pool, offsets, sizes, src_index, S)
-        if not outputs or set(outputs) - {"u8", "f32"}:
-            raise ValueError("outputs: 'u8', 'f32' or both, got %r" % (outputs,))
-        u8 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=pool.device) if "u8" in outputs else None
-        f32 = torch.empty(B, 3, S, S, dtype=torch.float32, device=pool.device) if "f32" in outputs else None
+        out = self._u8_f32(outputs, B, S, pool.device)
         factor = torch.empty(B, dtype=torch.int32, device=pool.device)
         self._ck(self.lib.uda_photo_reduce_u8(pool.data_ptr(), pool.numel() // 3, offsets.data_ptr(), sizes.data_ptr(), n, src_index.data_ptr(),
-                                              B, S, _ptr(u8), _ptr(f32), factor.data_ptr(), self._stream()))
-        out = {"factor": factor}
-        if u8 is not None:
-            out["u8"] = u8
-        if f32 is not None:
-            out["f32"] = f32
-        return out
+                                              B, S, _ptr(out.get("u8")), _ptr(out.get("f32")), factor.data_ptr(), self._stream()))
+        return dict(factor=factor, **out)
 
     def roi_cut(self, pool, offsets, sizes, src_index, boxes, S, outputs=("u8", "f32")):
         """Pillow's crop(box).resize((S, S), BILINEAR) of every selected photograph (uda_roi_cut_u8); boxes int32 [B,3] = (x0, y0, R) on
         the device -> {'u8': uint8 [B,S,S,3], 'f32': f32 [B,3,S,S]} for the names in ``outputs``"""
         n, B = self._ck_photos(pool, offsets, sizes, src_index, S)
-        if not outputs or set(outputs) - {"u8", "f32"}:
-            raise ValueError("outputs: 'u8', 'f32' or both, got %r" % (outputs,))
+        out = self._u8_f32(outputs, B, S, pool.device)
         if not boxes.is_cuda or boxes.dtype != torch.int32 or not boxes.is_contiguous() or tuple(boxes.shape) != (B, 3):
             raise ValueError("boxes: contiguous int32 [%d, 3] on the device (got %s %s)" % (B, boxes.dtype, tuple(boxes.shape)))
-        u8 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=pool.device) if "u8" in outputs else None
-        f32 = torch.empty(B, 3, S, S, dtype=torch.float32, device=pool.device) if "f32" in outputs else None
         self._ck(self.lib.uda_roi_cut_u8(pool.data_ptr(), pool.numel() // 3, offsets.data_ptr(), sizes.data_ptr(), n, src_index.data_ptr(),
-                                         boxes.data_ptr(), B, S, _ptr(u8), _ptr(f32), self._stream()))
-        out = {}
-        if u8 is not None:
-            out["u8"] = u8
-        if f32 is not None:
-            out["f32"] = f32
+                                         boxes.data_ptr(), B, S, _ptr(out.get("u8")), _ptr(out.get("f32")), self._stream()))
         return out
 
     def roi_paste(self, masks_u8, boxes, sizes, out_offsets, out_bytes):
         """uint8 [B,2,S,S] masks, boxes int32 [B,3], sizes int32 [B,2] = (H, W), out_offsets int64 [B], all on the device -> one flat
         uint8 [out_bytes] buffer holding every photograph's [H,W] grey mask (0 cup, 128 disc only, 255 background; uda_roi_paste_u8).
         The buffer is not pre-filled: the offsets must tile it, as ``ops.roi_paste`` lays them out."""
-        self._dev(masks_u8)
-        if masks_u8.dtype != torch.uint8 or not masks_u8.is_contiguous() or masks_u8.dim() != 4 or masks_u8.shape[1] != 2 or masks_u8.shape[2] != masks_u8.shape[3]:
-            raise ValueError("roi_paste: contiguous uint8 [B, 2, S, S] masks (got %s %s)" % (masks_u8.dtype, tuple(masks_u8.shape)))
-        B, S = masks_u8.shape[0], masks_u8.shape[2]
+        B, S, W = self._ck_masks("roi_paste", masks_u8)
+        if S != W:
+            raise ValueError("roi_paste: square [B, 2, S, S] masks (got %s)" % (tuple(masks_u8.shape),))
         for t, dt, shape in ((boxes, torch.int32, (B, 3)), (sizes, torch.int32, (B, 2)), (out_offsets, torch.int64, (B,))):
             if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
                 raise ValueError("roi_paste: contiguous %s %s on the device (got %s %s)" % (dt, list(shape), t.dtype, tuple(t.shape)))
-        if S % 16 or not 16 <= S <= 1024:
-            raise ValueError("size must be a multiple of 16 in 16..1024, got %d" % S)
+        check_side("size", S)
         out = torch.empty(int(out_bytes), dtype=torch.uint8, device=masks_u8.device)
         self._ck(self.lib.uda_roi_paste_u8(masks_u8.data_ptr(), boxes.data_ptr(), sizes.data_ptr(), out_offsets.data_ptr(), B, S, out.data_ptr(),
                                            out.numel(), self._stream()))
@@ -1300,18 +1379,7 @@ class HipKernels:
         blob, a ring.  A spiral wall of three turns on 256 x 256 needs 50 launches against 36 and takes the second attempt."""
         self._dev(pred)
         assert pred.dtype == torch.float32 and pred.is_contiguous() and pred.dim() == 4 and pred.shape[1] == 2
-        B, _, H, W = pred.shape
-        out = torch.empty(B, 2, H, W, dtype=torch.uint8, device=pred.device)
-        flags = torch.zeros(2, dtype=torch.int32, device=pred.device)
-        ws = self._ws(pred, self.lib.uda_postprocess_workspace_bytes(B, H, W))
-        n = int(sweeps) if sweeps else 2 * ((H + 31) // 32 + (W + 31) // 32) + 4
-        for _ in range(6):
-            self._ck(self.lib.uda_postprocess(pred.data_ptr(), B, H, W, float(thr_cup), float(thr_disc), n, out.data_ptr(),
-                                              flags.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
-            if int(flags.sum()) == 0:            # host sync: evaluation path only
-                return out
-            n *= 2
-        raise UdaError("uda_postprocess: label propagation did not converge after %d sweeps" % (n // 2))   # the last attempt's
+        return self._propagate("uda_postprocess", 2, pred, (float(thr_cup), float(thr_disc)), sweeps)
 
     def display_masks(self, prob, threshold=0.75, sweeps=None):
         """prob f32 [B,2,H,W] probabilities (left unchanged) -> uint8 [B,2,H,W] display masks of the reference's ``save_per_img``
@@ -1320,18 +1388,7 @@ class HipKernels:
         self._dev(prob)
         if prob.dtype != torch.float32 or not prob.is_contiguous() or prob.dim() != 4 or prob.shape[1] != 2:
             raise ValueError("display_masks: contiguous float32 [B, 2, H, W] probabilities (got %s %s)" % (prob.dtype, tuple(prob.shape)))
-        B, _, H, W = prob.shape
-        out = torch.empty(B, 2, H, W, dtype=torch.uint8, device=prob.device)
-        flags = torch.zeros(3, dtype=torch.int32, device=prob.device)
-        ws = self._ws(prob, self.lib.uda_display_masks_workspace_bytes(B, H, W))
-        n = int(sweeps) if sweeps else 2 * ((H + 31) // 32 + (W + 31) // 32) + 4
-        for _ in range(6):
-            self._ck(self.lib.uda_display_masks(prob.data_ptr(), B, H, W, float(threshold), n, out.data_ptr(), flags.data_ptr(),
-                                                ws.data_ptr(), ws.numel(), self._stream()))
-            if int(flags.sum()) == 0:            # host sync: evaluation path only
-                return out
-            n *= 2
-        raise UdaError("uda_display_masks: label propagation did not converge after %d sweeps" % (n // 2))   # the last attempt's
+        return self._propagate("uda_display_masks", 3, prob, (float(threshold),), sweeps)
 
     def overlay_u8(self, image_u8, masks_u8, out=None):
         """image uint8 [B,H,W,3], masks uint8 [B,2,H,W] (nonzero = set) -> uint8 [B,H,W,3]: channel 1's outline in (0, 255, 0),
@@ -1364,25 +1421,18 @@ class HipKernels:
         self._ck(self.lib.uda_image_u8(x.data_ptr(), B, H, W, out.data_ptr(), self._stream()))
         return out
 
-    def surface_distance(self, pred_u8, gt_u8, want_d2=False):
+    def surface_distance(self, pred_u8, gt_u8, want_d2=False, want_packed=False):
         """uint8 [B,2,H,W] masks (nonzero = set) -> (table f64 [B,2,2,3], counts i64 [B,2,3][, d2 i32 [B,2,2,H,W]]) on the
         device: per image and class the directed entries (n, sum of distances, max squared distance) pred -> gt and gt -> pred
-        between the masks' borders, and the Dice counts (include/uda_clr_hip.h, uda_surface_distance)."""
-        for t in (pred_u8, gt_u8):
-            self._dev(t)
-            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != 2:
-                raise ValueError("surface_distance: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (t.dtype, tuple(t.shape)))
-        if pred_u8.shape != gt_u8.shape:
-            raise ValueError("surface_distance: shapes differ: %s and %s" % (tuple(pred_u8.shape), tuple(gt_u8.shape)))
-        B, _, H, W = pred_u8.shape
-        dev = pred_u8.device
-        table = torch.empty(B, 2, 2, 3, dtype=torch.float64, device=dev)
-        counts = torch.empty(B, 2, 3, dtype=torch.int64, device=dev)
-        d2 = torch.empty(B, 2, 2, H, W, dtype=torch.int32, device=dev) if want_d2 else None
+        between the masks' borders, and the Dice counts (include/uda_clr_hip.h, uda_surface_distance).  Table and counts are views of
+        one buffer of 8-byte words (``surface_layout``), handed back as the last value with ``want_packed`` (one copy moves both)."""
+        B, H, W = self._ck_masks("surface_distance", pred_u8, gt_u8)
+        packed, v = packed_views(surface_layout(B), pred_u8.device)
+        d2 = torch.empty(B, 2, 2, H, W, dtype=torch.int32, device=pred_u8.device) if want_d2 else None
         ws = self._ws(pred_u8, self.lib.uda_surface_distance_workspace_bytes(B, H, W))
-        self._ck(self.lib.uda_surface_distance(pred_u8.data_ptr(), gt_u8.data_ptr(), B, H, W, table.data_ptr(), counts.data_ptr(),
+        self._ck(self.lib.uda_surface_distance(pred_u8.data_ptr(), gt_u8.data_ptr(), B, H, W, v["table"].data_ptr(), v["counts"].data_ptr(),
                                                _ptr(d2), ws.data_ptr(), ws.numel(), self._stream()))
-        return (table, counts, d2) if want_d2 else (table, counts)
+        return (v["table"], v["counts"]) + ((d2,) if want_d2 else ()) + ((packed,) if want_packed else ())
 
     def surface_profile(self, pred_u8, gt_u8, quantiles, tol2, want_packed=False):
         """uint8 [B,2,H,W] masks -> (table f64 [B,2,2,3], counts i64 [B,2,3], order i64 [B,2,3,Q,2], within i64 [B,2,2,T],
@@ -1390,12 +1440,7 @@ class HipKernels:
         ``surface_distance``; per set (pred -> gt, gt -> pred, both pooled) and quantile the two squared distances a percentile
         interpolates between; per direction the border pixels within each squared tolerance; per mask its first and last row.
         The five are views of one buffer of 8-byte words, handed back as a sixth value with ``want_packed`` (one copy moves all)."""
-        for t in (pred_u8, gt_u8):
-            self._dev(t)
-            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != 2:
-                raise ValueError("surface_profile: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (t.dtype, tuple(t.shape)))
-        if pred_u8.shape != gt_u8.shape:
-            raise ValueError("surface_profile: shapes differ: %s and %s" % (tuple(pred_u8.shape), tuple(gt_u8.shape)))
+        B, H, W = self._ck_masks("surface_profile", pred_u8, gt_u8)
         q = [float(v) for v in quantiles]
         t2 = [int(v) for v in tol2]
         if any(not 0.0 <= v <= 1.0 for v in q):                   # also true for NaN
@@ -1403,19 +1448,12 @@ class HipKernels:
         if any(v < 0 or v > 2 ** 31 - 1 for v in t2):
             raise ValueError("surface_profile: squared tolerances must lie in 0..2^31-1, got %r" % (t2,))
         Q, T = len(q), len(t2)
-        B, _, H, W = pred_u8.shape
-        sizes = (B * 12, B * 6, B * 12 * Q, B * 4 * T, B * 8)
-        packed = torch.empty(sum(sizes), dtype=torch.int64, device=pred_u8.device)
-        table, counts, order, within, extent = torch.split(packed, sizes)
-        table = table.view(torch.float64).view(B, 2, 2, 3)
-        counts, order, within, extent = counts.view(B, 2, 3), order.view(B, 2, 3, Q, 2), within.view(B, 2, 2, T), extent.view(B, 2, 2, 2)
+        packed, v = packed_views(profile_layout(B, Q, T), pred_u8.device)
         cq, ct = (C.c_double * max(Q, 1))(*q), (C.c_int32 * max(T, 1))(*t2)
         ws = self._ws(pred_u8, self.lib.uda_surface_profile_workspace_bytes(B, H, W))
         self._ck(self.lib.uda_surface_profile(pred_u8.data_ptr(), gt_u8.data_ptr(), B, H, W, C.addressof(cq), Q, C.addressof(ct), T,
-                                              table.data_ptr(), counts.data_ptr(), order.data_ptr(), within.data_ptr(), extent.data_ptr(),
-                                              None, ws.data_ptr(), ws.numel(), self._stream()))
-        out = (table, counts, order, within, extent)
-        return out + (packed,) if want_packed else out
+                                              *[t.data_ptr() for t in v.values()], None, ws.data_ptr(), ws.numel(), self._stream()))
+        return tuple(v.values()) + ((packed,) if want_packed else ())
 
     def disc_morphometry(self, masks_u8, sectors, want_packed=False):
         """uint8 [B,2,H,W] masks (0 cup, 1 disc; nonzero = set), sectors int64 [K,2] on the device (``utils.metrics.sector_table``)
@@ -1423,9 +1461,7 @@ class HipKernels:
         uda_disc_morphometry): per class n, sum r, sum c, sum r^2, sum c^2, sum r*c; first and last row and column; the pixels set
         in both planes; per sector about the disc centroid the largest squared distance scaled by n_disc^2, -1 for an empty sector.
         The four are views of one int64 buffer, handed back as a fifth value with ``want_packed`` (one copy moves all)."""
-        self._dev(masks_u8)
-        if masks_u8.dtype != torch.uint8 or not masks_u8.is_contiguous() or masks_u8.dim() != 4 or masks_u8.shape[1] != 2:
-            raise ValueError("disc_morphometry: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (masks_u8.dtype, tuple(masks_u8.shape)))
+        B, H, W = self._ck_masks("disc_morphometry", masks_u8)
         if not sectors.is_cuda:
             raise UdaError("HIP kernels need device tensors (got %s); there is no CPU fallback" % sectors.device)
         if sectors.dtype != torch.int64 or not sectors.is_contiguous() or sectors.dim() != 2 or sectors.shape[1] != 2:
@@ -1433,16 +1469,11 @@ class HipKernels:
         K = sectors.shape[0]
         if K % 8 or not 8 <= K <= 360:
             raise ValueError("disc_morphometry: the number of sectors must be a multiple of 8 in 8..360, got %d" % K)
-        B, _, H, W = masks_u8.shape
-        sizes = (B * 12, B * 8, B, B * 2 * K)
-        packed = torch.empty(sum(sizes), dtype=torch.int64, device=masks_u8.device)
-        moments, extent, overlap, radial = torch.split(packed, sizes)
-        moments, extent, radial = moments.view(B, 2, 6), extent.view(B, 2, 4), radial.view(B, 2, K)
+        packed, v = packed_views(morphometry_layout(B, K), masks_u8.device)
         ws = self._ws(masks_u8, self.lib.uda_disc_morphometry_workspace_bytes(B, H, W, K))
-        self._ck(self.lib.uda_disc_morphometry(masks_u8.data_ptr(), B, H, W, sectors.data_ptr(), K, moments.data_ptr(), extent.data_ptr(),
-                                               overlap.data_ptr(), radial.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
-        out = (moments, extent, overlap, radial)
-        return out + (packed,) if want_packed else out
+        self._ck(self.lib.uda_disc_morphometry(masks_u8.data_ptr(), B, H, W, sectors.data_ptr(), K, *[t.data_ptr() for t in v.values()],
+                                               ws.data_ptr(), ws.numel(), self._stream()))
+        return tuple(v.values()) + ((packed,) if want_packed else ())
 
     def mc_uncertainty(self, logits, outputs=("mean", "std", "entropy", "mi"), u8_scale=None):
         """f32 [T, ...] logits of T stochastic passes (2 <= T <= 32) -> {name: map of shape logits.shape[1:]} on the device, one read of
@@ -1450,17 +1481,10 @@ class HipKernels:
         trainer's quantity), 'entropy' of the mean, 'mi' = entropy minus the mean entropy of the passes; with ``u8_scale`` also
         'std_u8' = min(255, floor(std * u8_scale)) as uint8.  Only the maps named are computed and written."""
         self._dev(logits)
-        names = ("mean", "std", "entropy", "mi")
-        outputs = tuple(outputs)
-        if any(o not in names for o in outputs) or not (outputs or u8_scale is not None):
-            raise ValueError("mc_uncertainty: outputs among %r (got %r)" % (names, outputs))
         if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() < 2:
             raise ValueError("mc_uncertainty: contiguous float32 [T, ...] logits (got %s %s)" % (logits.dtype, tuple(logits.shape)))
-        T, shape = logits.shape[0], tuple(logits.shape[1:])
-        out = {o: torch.empty(shape, dtype=torch.float32, device=logits.device) for o in names if o in outputs}
-        if u8_scale is not None:
-            out["std_u8"] = torch.empty(shape, dtype=torch.uint8, device=logits.device)
-        self._ck(self.lib.uda_mc_uncertainty(logits.data_ptr(), T, logits[0].numel(), _ptr(out.get("mean")), _ptr(out.get("std")),
+        out = self._named_maps("mc_uncertainty", outputs, u8_scale, tuple(logits.shape[1:]), logits.device)
+        self._ck(self.lib.uda_mc_uncertainty(logits.data_ptr(), logits.shape[0], logits[0].numel(), _ptr(out.get("mean")), _ptr(out.get("std")),
                                              _ptr(out.get("entropy")), _ptr(out.get("mi")), _ptr(out.get("std_u8")),
                                              0.0 if u8_scale is None else float(u8_scale), self._stream()))
         return out
@@ -1470,35 +1494,23 @@ class HipKernels:
         ``edges`` K - 1 ascending host floats -> (rel i64 [B,2,bins,5] or None, risk i64 [B,2,K,4] or None, invalid i64 [B,2,2]) on the
         device (include/uda_clr_hip.h, uda_selective_tables).  The three are views of one int64 buffer, handed back as a fourth value
         with ``want_packed`` (one copy moves all)."""
-        masks = [pred_u8] + ([] if gt_u8 is None else [gt_u8])
-        for t in masks:
-            self._dev(t)
-            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != 2:
-                raise ValueError("selective_tables: contiguous uint8 [B, 2, H, W] masks (got %s %s)" % (t.dtype, tuple(t.shape)))
+        B, H, W = self._ck_masks("selective_tables", pred_u8, *(() if gt_u8 is None else (gt_u8,)))
         for t in (prob, unc):
             if t is not None:
                 self._dev(t)
                 if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != pred_u8.shape:
                     raise ValueError("selective_tables: contiguous float32 maps of the masks' shape (got %s %s)" % (t.dtype, tuple(t.shape)))
-        if gt_u8 is not None and gt_u8.shape != pred_u8.shape:
-            raise ValueError("selective_tables: shapes differ: %s and %s" % (tuple(pred_u8.shape), tuple(gt_u8.shape)))
         if prob is None and unc is None:
             raise ValueError("selective_tables: prob (reliability table), unc (risk table) or both")
-        B, _, H, W = pred_u8.shape
         edges = [float(e) for e in edges]
         M, K = int(bins), len(edges) + 1
-        sizes = (B * 2 * M * 5 if prob is not None else 0, B * 2 * K * 4 if unc is not None else 0, B * 4)
         if not 1 <= M <= 64 or not K <= 64:
             raise ValueError("selective_tables: 1..64 bins (got %d confidence, %d uncertainty)" % (M, K))
-        packed = torch.empty(sum(sizes), dtype=torch.int64, device=pred_u8.device)
-        rel, risk, invalid = torch.split(packed, sizes)
-        rel = rel.view(B, 2, M, 5) if prob is not None else None
-        risk = risk.view(B, 2, K, 4) if unc is not None else None
+        packed, v = packed_views(selective_layout(B, M, K, prob is not None, unc is not None), pred_u8.device)
         self._ck(self.lib.uda_selective_tables(_ptr(prob), _ptr(unc), pred_u8.data_ptr(), _ptr(gt_u8), B, H, W, M,
-                                               (C.c_float * max(len(edges), 1))(*edges), K, _ptr(rel), _ptr(risk), invalid.data_ptr(),
-                                               self._stream()))
-        out = (rel, risk, invalid.view(B, 2, 2))
-        return out + (packed,) if want_packed else out
+                                               (C.c_float * max(len(edges), 1))(*edges), K, _ptr(v.get("rel")), _ptr(v.get("risk")),
+                                               v["invalid"].data_ptr(), self._stream()))
+        return (v.get("rel"), v.get("risk"), v["invalid"]) + ((packed,) if want_packed else ())
 
     @staticmethod
     def _ck_tta_view(who, v, view):
@@ -1509,8 +1521,7 @@ class HipKernels:
             raise ValueError("%s: view %d must be (g, h, w), got %r" % (who, v, view)) from None
         if not 0 <= g <= 7:
             raise ValueError("%s: view %d: code %d outside 0..7" % (who, v, g))
-        if h % 16 or w % 16 or not (16 <= h <= 1024 and 16 <= w <= 1024):
-            raise ValueError("%s: view %d: size %d x %d, each side must be a multiple of 16 in 16..1024" % (who, v, h, w))
+        check_side("%s: view %d: size" % (who, v), h, w)
         return g, h, w
 
     @staticmethod
@@ -1519,8 +1530,7 @@ class HipKernels:
             raise ValueError("%s: batch %d outside 1..8192" % (who, B))
         if not 1 <= Cc <= 4:
             raise ValueError("%s: %d channels outside 1..4" % (who, Cc))
-        if H % 16 or W % 16 or not (16 <= H <= 1024 and 16 <= W <= 1024):
-            raise ValueError("%s: frame %d x %d, each side must be a multiple of 16 in 16..1024" % (who, H, W))
+        check_side("%s: frame" % who, H, W)
 
     def tta_view(self, image, view):
         """f32 [B,C,H,W] image, view (g, h, w) -> the view's input f32 [B,C,h,w] ([B,C,w,h] for a transposed code g & 4) on the device
@@ -1540,10 +1550,6 @@ class HipKernels:
         """V f32 [B,C,h_v',w_v'] logit tensors of the views (g, h, w) of an H x W frame, ``size`` = (H, W) -> {name: [B,C,H,W] map} on
         the device, one read of the logits (include/uda_clr_hip.h, uda_tta_fuse): every view mapped back to the frame, then the maps
         of ``mc_uncertainty`` over the views: 'mean', 'std', 'entropy', 'mi' and with ``u8_scale`` 'std_u8'."""
-        names = ("mean", "std", "entropy", "mi")
-        outputs = tuple(outputs)
-        if any(o not in names for o in outputs) or not (outputs or u8_scale is not None):
-            raise ValueError("tta_fuse: outputs among %r (got %r)" % (names, outputs))
         view_logits, views = list(view_logits), list(views)
         V = len(views)
         if not 2 <= V <= 32:
@@ -1568,10 +1574,7 @@ class HipKernels:
             if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != want or t.data_ptr() % 16:
                 raise ValueError("tta_fuse: view %d (g %d, %d x %d): contiguous 16-byte aligned float32 logits of shape %s (got %s %s)"
                                  % (v, g, h, w, want, t.dtype, tuple(t.shape)))
-        dev = view_logits[0].device
-        out = {o: torch.empty((B, Cc, H, W), dtype=torch.float32, device=dev) for o in names if o in outputs}
-        if u8_scale is not None:
-            out["std_u8"] = torch.empty((B, Cc, H, W), dtype=torch.uint8, device=dev)
+        out = self._named_maps("tta_fuse", outputs, u8_scale, (B, Cc, H, W), view_logits[0].device)
         ints = lambda k: (C.c_int * V)(*[view[k] for view in views])
         self._ck(self.lib.uda_tta_fuse((C.c_void_p * V)(*[t.data_ptr() for t in view_logits]), ints(0), ints(1), ints(2), V, B, Cc, H, W,
                                        _ptr(out.get("mean")), _ptr(out.get("std")), _ptr(out.get("entropy")), _ptr(out.get("mi")),

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import torch
 
+from . import kernels as hip
 from .acts import nchw_view, round4
 from .parallel import all_reduce_sum_
 
@@ -487,7 +488,7 @@ def _mask_u8(m):
 def _to_device(*tensors):
     """the tensors on one device: that of the first device tensor among them, else cuda (CPU tensors are moved there)"""
     if not any(t.is_cuda for t in tensors) and not torch.cuda.is_available():
-        raise RuntimeError("uda_clr_amd pictures compute only on the MI355X HIP kernels (there is no CPU fallback)")
+        raise RuntimeError("uda_clr_amd computes only on the MI355X HIP kernels (there is no CPU fallback)")
     dev = next((t.device for t in tensors if t.is_cuda), torch.device("cuda"))
     return [t.detach().to(dev) for t in tensors]
 
@@ -540,13 +541,10 @@ def surface_distances(pred_mask, gt_mask):
         counts int64 [B,2,3]: |pred & gt|, |pred|, |gt|
     as numpy arrays (``utils.metrics.surface_metrics_from_table`` / ``dice_per_image`` turn them into ASD, ASSD, HD and Dice).
     Runs on the device (uda_surface_distance); CPU tensors are moved there."""
-    if not (pred_mask.is_cuda and gt_mask.is_cuda) and not torch.cuda.is_available():
-        raise RuntimeError("uda_clr_amd surface distances compute only on the MI355X HIP kernels (there is no CPU fallback)")
-    dev = pred_mask.device if pred_mask.is_cuda else (gt_mask.device if gt_mask.is_cuda else torch.device("cuda"))
-    table, counts = kernels().surface_distance(_mask_u8(pred_mask.detach().to(dev)), _mask_u8(gt_mask.detach().to(dev)))
-    B = table.shape[0]
-    packed = torch.cat([table.reshape(-1), counts.view(torch.float64).reshape(-1)]).cpu().numpy()      # the one copy (it synchronises)
-    return packed[:B * 12].reshape(B, 2, 2, 3), packed[B * 12:].view("int64").reshape(B, 2, 3)
+    pred_mask, gt_mask = _to_device(pred_mask, gt_mask)
+    packed = kernels().surface_distance(_mask_u8(pred_mask), _mask_u8(gt_mask), want_packed=True)[-1]
+    t = hip.unpack_host(hip.surface_layout(pred_mask.shape[0]), packed.cpu().numpy())                  # the one copy (it synchronises)
+    return t["table"], t["counts"]
 
 
 def surface_profile(pred_mask, gt_mask, percentiles=(95,), tolerances=()):
@@ -571,17 +569,10 @@ def surface_profile(pred_mask, gt_mask, percentiles=(95,), tolerances=()):
     if not np.all((tol >= 0) & (tol * tol < 2.0 ** 31)):
         raise ValueError("surface_profile: tolerances must be non-negative pixel distances, got %r" % (tuple(tolerances),))
     tol2 = np.floor(tol * tol).astype(np.int64)
-    if not (pred_mask.is_cuda and gt_mask.is_cuda) and not torch.cuda.is_available():
-        raise RuntimeError("uda_clr_amd surface distances compute only on the MI355X HIP kernels (there is no CPU fallback)")
-    dev = pred_mask.device if pred_mask.is_cuda else (gt_mask.device if gt_mask.is_cuda else torch.device("cuda"))
-    packed = kernels().surface_profile(_mask_u8(pred_mask.detach().to(dev)), _mask_u8(gt_mask.detach().to(dev)), quantiles.tolist(),
-                                       tol2.tolist(), want_packed=True)[-1]
-    host = packed.cpu().numpy()                                                                          # the one copy (it synchronises)
-    B, Q, T = pred_mask.shape[0], len(quantiles), len(tol)
-    table, counts, order, within, extent = np.split(host, np.cumsum([B * 12, B * 6, B * 12 * Q, B * 4 * T]))
-    profile = {"order": order.reshape(B, 2, 3, Q, 2), "within": within.reshape(B, 2, 2, T), "extent": extent.reshape(B, 2, 2, 2),
-               "quantiles": quantiles, "tolerances": tol, "tol2": tol2}
-    return table.view(np.float64).reshape(B, 2, 2, 3), counts.reshape(B, 2, 3), profile
+    pred_mask, gt_mask = _to_device(pred_mask, gt_mask)
+    packed = kernels().surface_profile(_mask_u8(pred_mask), _mask_u8(gt_mask), quantiles.tolist(), tol2.tolist(), want_packed=True)[-1]
+    t = hip.unpack_host(hip.profile_layout(pred_mask.shape[0], len(quantiles), len(tol)), packed.cpu().numpy())   # the one copy (it synchronises)
+    return t.pop("table"), t.pop("counts"), dict(t, quantiles=quantiles, tolerances=tol, tol2=tol2)
 
 
 def disc_morphometry(masks, sectors=72):
@@ -606,15 +597,10 @@ def disc_morphometry(masks, sectors=72):
         raise ValueError("disc_morphometry: sector table entries must lie within +-2^30")
     if masks.dim() != 4 or masks.shape[1] != 2:
         raise ValueError("expected a [B, 2, H, W] mask, got %s" % (tuple(masks.shape),))
-    if not masks.is_cuda and not torch.cuda.is_available():
-        raise RuntimeError("uda_clr_amd morphometry computes only on the MI355X HIP kernels (there is no CPU fallback)")
-    dev = masks.device if masks.is_cuda else torch.device("cuda")
-    packed = kernels().disc_morphometry(_mask_u8(masks.detach().to(dev)), torch.from_numpy(table).to(dev), want_packed=True)[-1]
-    host = packed.cpu().numpy()                                                                          # the one copy (it synchronises)
-    B, K = masks.shape[0], table.shape[0]
-    moments, extent, overlap, radial = np.split(host, np.cumsum([B * 12, B * 8, B]))
-    return {"moments": moments.reshape(B, 2, 6), "extent": extent.reshape(B, 2, 4), "overlap": overlap.reshape(B),
-            "radial": radial.reshape(B, 2, K), "table": table}
+    (masks,) = _to_device(masks)
+    packed = kernels().disc_morphometry(_mask_u8(masks), torch.from_numpy(table).to(masks.device), want_packed=True)[-1]
+    t = hip.unpack_host(hip.morphometry_layout(masks.shape[0], table.shape[0]), packed.cpu().numpy())   # the one copy (it synchronises)
+    return dict(t, table=table)
 
 
 # uncertainty bins of the selective-prediction table: 0.04 is the trainer's trust threshold on the std of sigmoid(x / 2)
@@ -663,12 +649,9 @@ def selective_tables(prob, unc, pred, gt=None, bins=15, edges=DEFAULT_UNC_EDGES)
     f32 = lambda t: None if t is None else t.contiguous().float()
     packed = kernels().selective_tables(f32(prob), f32(unc), _mask_u8(pred), None if gt is None else _mask_u8(gt), int(bins), e32.tolist(),
                                         want_packed=True)[-1]
-    host = packed.cpu().numpy()                                                                          # the one copy (it synchronises)
-    B, M, K = pred.shape[0], int(bins), e32.size + 1
-    n_rel, n_risk = (B * 2 * M * 5 if prob is not None else 0), (B * 2 * K * 4 if unc is not None else 0)
-    rel, risk, invalid = np.split(host, [n_rel, n_rel + n_risk])
-    return {"rel": rel.reshape(B, 2, M, 5) if prob is not None else None, "risk": risk.reshape(B, 2, K, 4) if unc is not None else None,
-            "invalid": invalid.reshape(B, 2, 2), "edges": e32}
+    layout = hip.selective_layout(pred.shape[0], int(bins), e32.size + 1, prob is not None, unc is not None)
+    t = hip.unpack_host(layout, packed.cpu().numpy())                                                    # the one copy (it synchronises)
+    return {"rel": t.get("rel"), "risk": t.get("risk"), "invalid": t["invalid"], "edges": e32}
 
 
 def tta_view(image, view):

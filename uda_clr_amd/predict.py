@@ -43,9 +43,10 @@ import sys
 import numpy as np
 import torch
 
-from . import ops
+from . import inference, ops
 from .engine import check_input_size
-from .evaluate import UNCERTAINTY_U8_SCALE, load_generator
+from .evaluate import load_generator
+from .inference import check_uncertainty_args as check_tta, resolve_mc_logits  # noqa: F401  (their names before they moved)
 from .utils import Utils, metrics
 
 EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
@@ -154,16 +155,7 @@ def predict_batch(model, u8, x, names, out_dir, dataset="Drishti-GS", threshold=
     row per image as ``predict`` documents them, and the uint8 [B,2,H,W] evaluation masks on the device.  With ``tta`` (a view list,
     ``uda_clr_amd.tta``) the probabilities are the mean over the views, and with ``tta_uncertainty`` the std over the views fills the
     uncertainty picture and columns."""
-    fused = None
-    if tta is None:
-        out = model(x)
-        logits = out[0] if isinstance(out, (tuple, list)) else out
-        prob = torch.sigmoid(logits.float())
-    else:
-        from . import tta as tta_views
-        fused = tta_views.tta_predict(model, x, tta, outputs=("mean", "std") if tta_uncertainty else ("mean",),
-                                      u8_scale=UNCERTAINTY_U8_SCALE if tta_uncertainty else None)
-        prob = fused["mean"]
+    prob, unc = inference.probabilities(model, x, tta, tta_uncertainty, mc_passes, mc_logits, std_u8=True)
     pred = Utils.postprocessing_batch(prob, threshold, dataset)
     Utils.save_per_img_batch(u8, out_dir, names, prob)
     Utils.save_mask_batch(pred, out_dir, names)
@@ -175,30 +167,12 @@ def predict_batch(model, u8, x, names, out_dir, dataset="Drishti-GS", threshold=
         cols = morphometry_columns(pred, sectors)
         for i in range(len(names)):
             rows[i].update({k: float(cols[k][i]) for k in MORPHOMETRY_COLUMNS})
-    if mc_passes or tta_uncertainty:
-        unc = fused if tta_uncertainty else ops.mc_uncertainty(mc_logits(x, mc_passes), outputs=("std",), u8_scale=UNCERTAINTY_U8_SCALE)
+    if unc is not None:
         Utils.save_uncertainty_batch(unc["std_u8"], out_dir, names)
         cols = uncertainty_columns(unc["std"], pred)
         for i in range(len(names)):
             rows[i].update({k: float(cols[k][i]) for k in UNCERTAINTY_COLUMNS})
     return rows, pred
-
-
-def check_tta(tta, tta_uncertainty, mc_passes):
-    """the argument errors of ``tta`` / ``tta_uncertainty``, as ``evaluate`` raises them"""
-    if tta_uncertainty and int(mc_passes):
-        raise ValueError("tta_uncertainty=True and mc_passes=%d: one uncertainty fills the columns, not both" % int(mc_passes))
-    if tta_uncertainty and tta is None:
-        raise ValueError("tta_uncertainty=True needs tta, a view list (got tta=None)")
-
-
-def resolve_mc_logits(model, mc_passes, mc_logits):
-    """the stochastic passes of ``mc_passes``: the callable given, else ``model.mc_inference_logits``"""
-    if int(mc_passes) and mc_logits is None:
-        mc_logits = getattr(model, "mc_inference_logits", None)
-        if mc_logits is None:
-            raise ValueError("mc_passes needs a model with mc_inference_logits (DeepLab) or an mc_logits callable")
-    return mc_logits
 
 
 def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_size=8, morphometry=False, sectors=72, mc_passes=0,
@@ -219,20 +193,13 @@ def predict(model, images, out_dir, dataset="Drishti-GS", threshold=0.75, batch_
     mc_passes = int(mc_passes)
     mc_logits = resolve_mc_logits(model, mc_passes, mc_logits)
     dev = torch.device("cuda")
-    was_training = getattr(model, "training", False)
-    if hasattr(model, "eval"):
-        model.eval()
     rows = []
-    try:
-        with torch.no_grad():
-            for names, u8 in batches(images, batch_size):
-                u8 = torch.from_numpy(u8).to(dev)
-                x = (u8.permute(0, 3, 1, 2).float() / 127.5 - 1.0).contiguous()          # Normalize_tf's image, ToTensor's layout
-                rows += predict_batch(model, u8, x, names, out_dir, dataset, threshold, morphometry, sectors, mc_passes, mc_logits,
-                                      tta, tta_uncertainty)[0]
-    finally:
-        if was_training and hasattr(model, "train"):
-            model.train()
+    with inference.eval_mode(model):
+        for names, u8 in batches(images, batch_size):
+            u8 = torch.from_numpy(u8).to(dev)
+            x = (u8.permute(0, 3, 1, 2).float() / 127.5 - 1.0).contiguous()              # Normalize_tf's image, ToTensor's layout
+            rows += predict_batch(model, u8, x, names, out_dir, dataset, threshold, morphometry, sectors, mc_passes, mc_logits,
+                                  tta, tta_uncertainty)[0]
     return rows
 
 

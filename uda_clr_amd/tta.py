@@ -15,6 +15,8 @@ import math
 import torch
 
 from . import ops
+from .inference import first_output
+from .kernels import check_side
 
 CODES = {"id": 0, "hflip": 1, "vflip": 2, "rot180": 3, "transpose": 4, "rot90": 5, "rot270": 6, "antitranspose": 7}
 NAMES = tuple(sorted(CODES, key=CODES.get))
@@ -27,11 +29,6 @@ def scaled_size(n, s):
     return 16 * max(1, int(math.floor(n * s / 16.0 + 0.5)))
 
 
-def _check_side(what, n):
-    if n % 16 or not 16 <= n <= 1024:
-        raise ValueError("tta: %s %d is not a multiple of 16 in 16..1024" % (what, n))
-
-
 def _check_views(views):
     """[(g, h, w)] as ints, every one valid, no two equal, 2..32 of them"""
     out = []
@@ -42,8 +39,7 @@ def _check_views(views):
             raise ValueError("tta: a view is (g, h, w), got %r" % (v,)) from None
         if not 0 <= g <= 7:
             raise ValueError("tta: view code %d outside 0..7" % g)
-        _check_side("view height", h)
-        _check_side("view width", w)
+        check_side("tta: view size", h, w)
         if (g, h, w) in out:
             raise ValueError("tta: view %s at %d x %d is given twice" % (NAMES[g], h, w))
         out.append((g, h, w))
@@ -57,8 +53,8 @@ def parse_views(spec, H, W):
     rot270 antitranspose, and the shorthands flips (= id,hflip,vflip,rot180) and d4 (= all eight); each optionally followed by @s, a
     scale: h = 16 * max(1, floor(H * s / 16 + 0.5)), w likewise.  A view given twice (two scales may round to one size), fewer than 2
     or more than 32 views, an unknown token or a size outside 16..1024 is a ValueError."""
-    _check_side("image height", int(H))
-    _check_side("image width", int(W))
+    check_side("tta: image height", int(H))
+    check_side("tta: image width", int(W))
     if not isinstance(spec, str) or not spec.strip():
         raise ValueError("tta: a view list is a string such as 'flips,id@0.75', got %r" % (spec,))
     views = []
@@ -107,9 +103,7 @@ def tta_logits(model, image, views, max_batch=64):
         for i in range(0, len(members), per):
             part = members[i:i + per]
             inputs = [ops.tta_view(image, views[v]) for v in part]
-            out = model(inputs[0] if len(part) == 1 else torch.cat(inputs))
-            out = out[0] if isinstance(out, (tuple, list)) else out
-            out = out.float().contiguous()
+            out = first_output(model(inputs[0] if len(part) == 1 else torch.cat(inputs))).float().contiguous()
             if out.shape[0] != B * len(part) or tuple(out.shape[2:]) != tuple(inputs[0].shape[2:]):
                 raise ValueError("tta: the model gave logits %s for inputs %s" % (tuple(out.shape), (B * len(part),) + tuple(inputs[0].shape[1:])))
             for k, v in enumerate(part):

@@ -20,7 +20,8 @@ import os
 import numpy as np
 import torch
 
-from . import ops, predict
+from . import inference, ops, predict
+from .kernels import check_side
 from .utils import Utils
 
 # morphometry columns of ``predict`` that are lengths in ROI pixels: multiplied by roi_size / size to read in photograph pixels
@@ -35,9 +36,7 @@ def locate(canvas_f32, factor, sizes, locator, threshold=0.75, dataset="Drishti-
     ``canvas_f32`` [B,3,S,S] and ``factor`` [B] as ``ops.photo_reduce`` gives them, ``sizes`` host [B,2] = (H, W).
     -> (centres int64 [B,2] = (cy, cx), located int64 [B]) on the host; an empty disc plane gives located 0 and the photograph's
     centre (H // 2, W // 2)."""
-    out = locator(canvas_f32)
-    logits = out[0] if isinstance(out, (tuple, list)) else out
-    pred = Utils.postprocessing_batch(torch.sigmoid(logits.float()), threshold, dataset)
+    pred = Utils.postprocessing_batch(inference.probabilities(locator, canvas_f32)[0], threshold, dataset)
     mom = ops.disc_morphometry(pred, 8)["moments"][:, 1, :3]
     f = np.asarray(factor.cpu() if torch.is_tensor(factor) else factor).astype(np.int64).reshape(-1)
     sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
@@ -80,8 +79,7 @@ def predict_photos(model, photos, out_dir, roi_size=800, size=512, locator=None,
     centre) and disc_cx, disc_cy: the centroid of the final disc mask in photograph pixels, x0 + (mean column + 0.5) * R / size (nan
     without a disc); the morphometry columns that are lengths in pixels (PIXEL_COLUMNS) are multiplied by R / size."""
     R, S = int(roi_size), int(size)
-    if S % 16 or not 16 <= S <= 1024:
-        raise ValueError("size must be a multiple of 16 in 16..1024, got %d" % S)
+    check_side("size", S)
     if R < 8 or 2 * R > 5 * S:
         raise ValueError("roi_size must lie in 8..2.5 * size = %d, got %d" % (5 * S // 2, R))
     if centres is not None:
@@ -91,47 +89,40 @@ def predict_photos(model, photos, out_dir, roi_size=800, size=512, locator=None,
     if not torch.cuda.is_available():
         raise RuntimeError("uda_clr_amd computes only on the MI355X HIP kernels (there is no CPU fallback)")
     mc_passes = int(mc_passes)
-    predict.check_tta(tta, tta_uncertainty, mc_passes)
-    mc_logits = predict.resolve_mc_logits(model, mc_passes, mc_logits)
+    inference.check_uncertainty_args(tta, tta_uncertainty, mc_passes)
+    mc_logits = inference.resolve_mc_logits(model, mc_passes, mc_logits)
     locator = model if locator is None else locator
     dev = torch.device("cuda")
-    nets = [m for m in ((model,) if locator is model else (model, locator)) if getattr(m, "training", False) and hasattr(m, "eval")]
-    for m in nets:
-        m.eval()
     rows = []
-    try:
-        with torch.no_grad():
-            for i in range(0, len(photos), int(batch_size)):
-                part = photos[i:i + int(batch_size)]
-                names = [n for n, _ in part]
-                pool = ops.PhotoPool([a for _, a in part], dev)                          # the one upload
-                if centres is None:
-                    red = ops.photo_reduce(pool, size=S, outputs=("f32",))
-                    cen, located = locate(red["f32"], red["factor"], pool.sizes_host, locator, threshold, dataset)
-                else:
-                    cen = np.array([(centres[n][1], centres[n][0]) for n in names], np.int64)
-                    located = np.ones(len(names), np.int64)
-                bx = boxes(cen, pool.sizes_host, R)
-                roi = ops.roi_cut(pool, torch.from_numpy(bx), size=S, outputs=("u8", "f32"))
-                part_rows, pred = predict.predict_batch(model, roi["u8"], roi["f32"], names, out_dir, dataset, threshold, morphometry, sectors,
-                                                        mc_passes, mc_logits, tta, tta_uncertainty)
-                masks = ops.roi_paste(pool, pred, torch.from_numpy(bx))
-                host = torch.cat([m.reshape(-1) for m in masks]).cpu().numpy()         # the one copy of the photograph-sized masks
-                mom = ops.disc_morphometry(pred, 8)["moments"][:, 1, :3]
-                at = 0
-                for b, (name, row) in enumerate(zip(names, part_rows)):
-                    H, W = (int(v) for v in pool.sizes_host[b])
-                    Utils._save_png(host[at:at + H * W].reshape(H, W), os.path.join(out_dir, "photo_mask"), name)
-                    at += H * W
-                    n, sr, sc = (int(v) for v in mom[b])
-                    row.update({"roi_x0": int(bx[b, 0]), "roi_y0": int(bx[b, 1]), "roi_size": R, "located": int(located[b]),
-                                "disc_cx": bx[b, 0] + (sc / n + 0.5) * R / S if n else float("nan"),
-                                "disc_cy": bx[b, 1] + (sr / n + 0.5) * R / S if n else float("nan")})
-                    for k in PIXEL_COLUMNS:
-                        if k in row:
-                            row[k] = row[k] * R / S
-                rows += part_rows
-    finally:
-        for m in nets:
-            m.train()
+    with inference.eval_mode(model, locator):
+        for i in range(0, len(photos), int(batch_size)):
+            part = photos[i:i + int(batch_size)]
+            names = [n for n, _ in part]
+            pool = ops.PhotoPool([a for _, a in part], dev)                          # the one upload
+            if centres is None:
+                red = ops.photo_reduce(pool, size=S, outputs=("f32",))
+                cen, located = locate(red["f32"], red["factor"], pool.sizes_host, locator, threshold, dataset)
+            else:
+                cen = np.array([(centres[n][1], centres[n][0]) for n in names], np.int64)
+                located = np.ones(len(names), np.int64)
+            bx = boxes(cen, pool.sizes_host, R)
+            roi = ops.roi_cut(pool, torch.from_numpy(bx), size=S, outputs=("u8", "f32"))
+            part_rows, pred = predict.predict_batch(model, roi["u8"], roi["f32"], names, out_dir, dataset, threshold, morphometry, sectors,
+                                                    mc_passes, mc_logits, tta, tta_uncertainty)
+            masks = ops.roi_paste(pool, pred, torch.from_numpy(bx))
+            host = torch.cat([m.reshape(-1) for m in masks]).cpu().numpy()         # the one copy of the photograph-sized masks
+            mom = ops.disc_morphometry(pred, 8)["moments"][:, 1, :3]
+            at = 0
+            for b, (name, row) in enumerate(zip(names, part_rows)):
+                H, W = (int(v) for v in pool.sizes_host[b])
+                Utils._save_png(host[at:at + H * W].reshape(H, W), os.path.join(out_dir, "photo_mask"), name)
+                at += H * W
+                n, sr, sc = (int(v) for v in mom[b])
+                row.update({"roi_x0": int(bx[b, 0]), "roi_y0": int(bx[b, 1]), "roi_size": R, "located": int(located[b]),
+                            "disc_cx": bx[b, 0] + (sc / n + 0.5) * R / S if n else float("nan"),
+                            "disc_cy": bx[b, 1] + (sr / n + 0.5) * R / S if n else float("nan")})
+                for k in PIXEL_COLUMNS:
+                    if k in row:
+                        row[k] = row[k] * R / S
+            rows += part_rows
     return rows
