@@ -381,6 +381,22 @@ uint64_t uda_proto_workspace_bytes(int64_t P, int C);
 int uda_proto_reduce(const float* feat, int64_t ldf, int64_t P, int C, const float* wts, double* sums,
                      float* workspace, uint64_t workspace_bytes, void* stream);
 int uda_proto_finalize(const double* sums, int C, float* centroids /* [4][C] */, void* stream);
+/* Second moments of the four classes for the domain-gap report (uda_clr_amd/domain_gap.py): the centred, weighted
+ * scatter of the features that utils/Utils.py:108-131 averages into prototypes and Trainer_prototype_full.py:428-444 aligns,
+ *     scatter[k][i][j] += sum_p w_k[p] (f[p,i] - a_k[i]) (f[p,j] - a_k[j]),   k < 4,  i, j < C.
+ * feat: the [P, C] rows uda_proto_reduce takes - 16-byte aligned, ldf % 4 == 0, ldf >= C rounded up to 4; the lanes from C up to that
+ * multiple may hold anything (NaN included) and reach no result; nothing behind that lane of row P - 1 is read; offsets are 64-bit.
+ * wts [P][4]: what uda_proto_weights writes (soft weights allowed; w_{k+2} = 1 - w_k is NOT assumed).  centre [4][C], or null for
+ * zeros.  scatter: double [4][C][C], ADDED into.  Every C in 1..1024, any P >= 1; a bad argument returns the error before
+ * anything is written.
+ * Arithmetic: products and the sum over pixels on the exact-fp32 MFMA (bitwise an fmaf chain); one fp32 accumulator sums at most
+ * PS_SLAB pixels (csrc/scatter_plan.h), slab partials are combined in fp64 in a fixed order, no atomics: the same inputs give the
+ * same bits.  Only channel blocks i-block <= j-block are computed and the other triangle is a copy: [k][i][j] and [k][j][i] are
+ * bitwise equal (given that they were on entry).  The workspace holds a fixed number of fp64 partial sets and depends on C alone. */
+uint64_t uda_proto_scatter_workspace_bytes(int C);
+int uda_proto_scatter(const float* feat, int64_t ldf, int64_t P, int C, const float* wts /* [P][4] */,
+                      const float* centre /* [4][C], null = zeros */, double* scatter /* [4][C][C], ADDED into */,
+                      void* workspace, uint64_t workspace_bytes, void* stream);
 /* adjoint of centroid = sum/count: d_feat[P,C] (optional, optionally accumulated) and d_w[P,4] (optional) */
 int uda_proto_bwd(const float* feat, int64_t ldf, int64_t P, int C, const float* wts, const double* sums,
                   const float* dC, float* coef_ws /* float[4][C+1] */, float* d_feat, int64_t ldd,

@@ -122,6 +122,8 @@ SYMBOLS = {
     "uda_proto_workspace_bytes": (_U, [_L, _I]),
     "uda_proto_reduce": (_I, [_P, _L, _L, _I, _P, _P, _P, _U, _P]),
     "uda_proto_finalize": (_I, [_P, _I, _P, _P]),
+    "uda_proto_scatter_workspace_bytes": (_U, [_I]),
+    "uda_proto_scatter": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _U, _P]),
     "uda_proto_bwd": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _L, _I, _P, _P]),
     "uda_feat_dot4": (_I, [_P, _L, _L, _I, _P, _P, _P]),
     "uda_feat_rank4": (_I, [_P, _P, _L, _I, _P, _L, _I, _P]),
@@ -1159,6 +1161,19 @@ class HipKernels:
         cent = torch.empty(4, Cc, dtype=torch.float32, device=sums.device)
         self._ck(self.lib.uda_proto_finalize(sums.data_ptr(), Cc, cent.data_ptr(), self._stream()))
         return cent
+
+    def proto_scatter(self, feat, wts, scatter, centre=None):
+        """scatter (double [4, C, C]) += sum_p w_k[p] (f[p] - centre_k)(f[p] - centre_k)^T; centre float [4, C] or None (zeros)"""
+        self._dev(feat)
+        f, ldf = _mat(feat, "feat")
+        P, Cc = feat.shape
+        assert wts.shape == (P, 4) and wts.is_contiguous() and wts.dtype == torch.float32
+        assert scatter.dtype == torch.float64 and scatter.is_contiguous() and tuple(scatter.shape) == (4, Cc, Cc)
+        if centre is not None:
+            assert centre.dtype == torch.float32 and centre.is_contiguous() and tuple(centre.shape) == (4, Cc)
+        ws = self._ws(feat, self.lib.uda_proto_scatter_workspace_bytes(Cc))
+        self._ck(self.lib.uda_proto_scatter(f, ldf, P, Cc, wts.data_ptr(), _ptr(centre), scatter.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            self._stream()))
 
     def proto_bwd(self, feat, wts, sums, dC, d_feat=None, accumulate=False, want_dw=False):
         f, ldf = _mat(feat, "feat")

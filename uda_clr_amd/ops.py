@@ -199,6 +199,22 @@ def gen_prototype_retrify(oT_before, xt_feature, preds, features, T, stride):
     return out
 
 
+def class_scatter(feature, wts, centre=None, out=None):
+    """Centred, weighted second moments of the four classes (uda_proto_scatter): feature [B,C,h,w] (or its [P,C] rows,
+    as ``rows_view`` gives them), wts [P, 4] as uda_proto_weights writes them, centre [4,C] float or None (zeros) -> float64 [4,C,C] on the device,
+    S_k = sum_p w_k[p] (f_p - centre_k)(f_p - centre_k)^T.  Added into ``out`` when given.  No autograd."""
+    if not feature.is_cuda:
+        raise hip.UdaError("class_scatter needs device tensors (got %s); there is no CPU fallback" % feature.device)
+    rows = feature.detach() if feature.dim() == 2 else rows_view(feature.detach())
+    C = rows.shape[1]
+    if out is None:
+        out = torch.zeros(4, C, C, dtype=torch.float64, device=feature.device)
+    if centre is not None:
+        centre = centre.detach().reshape(4, C).contiguous().float()
+    kernels().proto_scatter(rows, wts.detach().contiguous().float(), out, centre)
+    return out
+
+
 class _DiscriminativeFn(torch.autograd.Function):
     """Prototype-guided discriminative loss on the source features (no shipped
     source - parity unpinned).  D(f,c) = mean_c (f-c)^2, so D(f,c_obj) - D(f,c_bck) is AFFINE in f:
