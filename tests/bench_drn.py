@@ -77,7 +77,7 @@ def workload(name, B, S, steps, warmup, dev):
             "batch": B, "size": S, "images_per_step": per_step, "steps": steps, "warmup": warmup,
             "img_per_s": round(per_step / dt, 2), "ms_per_step": round(1e3 * dt, 2),
             "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2), "loss": loss,
-            "narrow_routes": os.environ.get("UDA_CLR_DRN_NARROW", "table"), "device": torch.cuda.get_device_name(dev)}
+            "device": torch.cuda.get_device_name(dev)}
 
 
 # (layer, Cin, Cout, stride, input side at 512^2): the narrow 3x3 convs of the head and of layer3; "dgrad" runs Cout -> Cin at stride 1 on the

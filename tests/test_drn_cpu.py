@@ -119,15 +119,23 @@ def test_eval_forward_matches_oracle(size):
         assert model_cases.rel(a, b) < 2e-4, (n, model_cases.rel(a, b))
 
 
-@pytest.mark.parametrize("narrow", ["", "0", "1"], ids=["routed", "implicit-gemm", "narrow"])
-def test_train_forward_backward_matches_oracle(narrow, monkeypatch):
+def narrow_table(route):
+    """drn._DRN_NARROW as the engine routes it ("routed"), with every narrow conv the implicit-GEMM route can serve on that route
+    ("implicit-gemm": the stride-1 ones; a stride-2 conv below the wide tiles has the narrow kernels only) and with every listed
+    shape on the narrow kernels ("narrow")"""
+    from uda_clr_amd.networks.backbone.drn import _DRN_NARROW
+    return {k: {"routed": v, "implicit-gemm": v and k[3] == 2, "narrow": True}[route] for k, v in _DRN_NARROW.items()}
+
+
+@pytest.mark.parametrize("route", ["routed", "implicit-gemm", "narrow"])
+def test_train_forward_backward_matches_oracle(route, monkeypatch):
     """Training forward + backward at 64^2 (injected dropout masks) against the fp64 oracle, with the bounds of the other
     backbones' CPU cases: outputs within 3x the fp32 oracle's own fp64 distance, gradients by model_cases.grads_ok with no
     parameter left out (every DRN BatchNorm is followed by a ReLU or by the residual add + ReLU: no gradient is analytically
-    zero).  Runs on the routes the engine picks, with every head conv on the implicit-GEMM route (stride 2 = stride 1 +
-    subsampling / zero stuffing) and with every head conv on the narrow kernels."""
+    zero).  Runs on the routes the engine picks, with every stride-1 head conv on the implicit-GEMM route and with every head
+    conv on the narrow kernels (``narrow_table``)."""
     from uda_clr_amd.networks.backbone import drn
-    monkeypatch.setattr(drn, "_DRN_NARROW_ENV", narrow)
+    monkeypatch.setattr(drn, "_DRN_NARROW", narrow_table(route))
     fwd, grads, stats, fwd64 = model_cases.train_parity(torch.device("cpu"), backbone="drn", output_stride=8, engine=_engine(),
                                                         oracle_forward=drn_ref.deeplab_forward)
     backbone_cases.train_checks(fwd64, grads, stats, stats_bound=1e-3, gmean_bound=1.5, n_grads=204)

@@ -7,7 +7,7 @@ import torch
 import backbone_cases
 import drn_ref
 import model_cases
-from test_drn_cpu import golden_errors
+from test_drn_cpu import golden_errors, narrow_table
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -19,11 +19,11 @@ def test_eval_forward_matches_oracle(size):
     assert max(errs.values()) < 1e-3, errs
 
 
-@pytest.mark.parametrize("narrow", ["", "0", "1"], ids=["routed", "implicit-gemm", "narrow"])
-def test_train_forward_backward_matches_oracle(narrow, monkeypatch):
-    """on the routes the engine picks, with every head conv on the implicit-GEMM route and with every one on the narrow kernels"""
+@pytest.mark.parametrize("route", ["routed", "implicit-gemm", "narrow"])
+def test_train_forward_backward_matches_oracle(route, monkeypatch):
+    """on the routes the engine picks, with every stride-1 head conv on the implicit-GEMM route and with every one on the narrow kernels"""
     from uda_clr_amd.networks.backbone import drn
-    monkeypatch.setattr(drn, "_DRN_NARROW_ENV", narrow)
+    monkeypatch.setattr(drn, "_DRN_NARROW", narrow_table(route))
     fwd, grads, stats, fwd64 = model_cases.train_parity(DEV, backbone="drn", output_stride=8, oracle_forward=drn_ref.deeplab_forward)
     backbone_cases.train_checks(fwd64, grads, stats, n_grads=204)
 

@@ -20,7 +20,9 @@ from typing import Optional
 
 import torch
 
-ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
+from .abi import CONSTANTS
+
+ACT_NONE, ACT_RELU, ACT_RELU6 = (CONSTANTS["UDA_ACT_" + a] for a in ("NONE", "RELU", "RELU6"))
 
 
 def round4(c: int) -> int:

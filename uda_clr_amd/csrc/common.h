@@ -44,9 +44,9 @@ static inline int uda_wgp_reduce(float* ws, int nwg, int nel, hipStream_t st) {
 int uda_wgp_finish(float* ws, int nwg, int nel, float* dw, const char* who, hipStream_t st);
 
 // ------------------------------------------------------------------------------------ device
-#define ACT_NONE 0
-#define ACT_RELU 1
-#define ACT_RELU6 2
+#define ACT_NONE UDA_ACT_NONE
+#define ACT_RELU UDA_ACT_RELU
+#define ACT_RELU6 UDA_ACT_RELU6
 
 // none / ReLU / ReLU6 as one clamp (v_med3_f32) between bounds that depend only on the launch's activation code
 __device__ __forceinline__ float uda_act(float v, int act) {

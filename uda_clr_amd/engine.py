@@ -32,6 +32,7 @@ import torch
 
 POISON_BUFFERS = False      # tests/test_generator_gpu.py sets it: every fp32 work matrix starts as NaN / Inf / huge values
 
+from .abi import CONSTANTS
 from .acts import ACT_RELU, Act, BNRec, nchw_view, round4
 from .domain_split import DomainSplit
 from .networks.backbone import BACKBONES
@@ -55,7 +56,7 @@ def check_input_size(H, W):
         raise ValueError("input height/width must be multiples of 16, got %dx%d" % (H, W))
 
 
-STAT_SLOTS = 16     # UDA_STAT_SLOTS: replicas of every per-channel statistics accumulator
+STAT_SLOTS = CONSTANTS["UDA_STAT_SLOTS"]     # replicas of every per-channel statistics accumulator
 
 
 class _Arena:

@@ -14,157 +14,15 @@ from typing import Optional
 
 import torch
 
+from .abi import CONSTANTS, STRUCTS, SYMBOLS
 from .acts import conv_weight_shape, Act, round4
 
-STAT_SLOTS = 16      # UDA_STAT_SLOTS in include/uda_clr_hip.h
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libuda_clr_hip.so")
 _lib = None
 
-
-class UdaSrc(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("N", C.c_int32), ("H", C.c_int32),
-                ("W", C.c_int32), ("C", C.c_int32), ("scale", C.c_void_p), ("shift", C.c_void_p),
-                ("act", C.c_int32), ("_pad", C.c_int32), ("mask", C.c_void_p), ("ldm", C.c_int64),
-                ("mask_scale", C.c_float), ("_pad2", C.c_float)]
-
-
-class UdaConvArgs(C.Structure):
-    _fields_ = [("src", UdaSrc), ("w", C.c_void_p), ("Cout", C.c_int32), ("ksize", C.c_int32),
-                ("dil", C.c_int32), ("origin", C.c_int32), ("bias", C.c_void_p), ("addend", C.c_void_p),
-                ("ld_add", C.c_int64), ("y", C.c_void_p), ("ldy", C.c_int64), ("stats", C.c_void_p),
-                ("mfma", C.c_int32), ("stride", C.c_int32), ("x3_src", C.c_void_p), ("x3_w", C.c_void_p),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
-
-
-class UdaWgradArgs(C.Structure):
-    _fields_ = [("src", UdaSrc), ("dy", C.c_void_p), ("lddy", C.c_int64), ("Cout", C.c_int32),
-                ("ksize", C.c_int32), ("dil", C.c_int32), ("origin", C.c_int32), ("dw", C.c_void_p),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64), ("mfma", C.c_int32), ("stride", C.c_int32),
-                ("x3_src", C.c_void_p), ("x3_dy", C.c_void_p)]
-
-
-# every symbol declared in include/uda_clr_hip.h: name -> (restype, argtypes)
-_P, _I, _L, _F, _D, _U = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_uint64
-SYMBOLS = {
-    "uda_last_error": (C.c_char_p, []),
-    "uda_version": (_I, []),
-    "uda_relayout_ohwi": (_I, [_P, _I, _I, _I, _P, _P]),
-    "uda_relayout_dgrad": (_I, [_P, _I, _I, _I, _P, _P]),
-    "uda_relayout_dw": (_I, [_P, _I, _P, _P]),
-    "uda_conv_fwd": (_I, [C.POINTER(UdaConvArgs), _P]),
-    "uda_conv_uses_x3": (_I, [C.POINTER(UdaConvArgs)]),
-    "uda_conv_fwd_workspace_bytes": (_U, [C.POINTER(UdaConvArgs)]),
-    "uda_conv_route": (_I, [C.POINTER(UdaConvArgs), C.c_char_p, _I]),
-    "uda_conv_wgrad_route": (_I, [C.POINTER(UdaWgradArgs), C.c_char_p, _I]),
-    "uda_conv_route_list": (C.c_char_p, []),
-    "uda_x3_packed_bytes": (_U, [_L, _I]),
-    "uda_x3_pack": (_I, [C.POINTER(UdaSrc), _P, _P]),
-    "uda_conv_wgrad_workspace_bytes": (_U, [_L, _I, _I, _I]),
-    "uda_conv_wgrad": (_I, [C.POINTER(UdaWgradArgs), _P]),
-    "uda_conv_wgrad_uses_x3": (_I, [C.POINTER(UdaWgradArgs)]),
-    "uda_dwconv_workspace_bytes": (_U, [_L, _I]),
-    "uda_dwconv_fwd": (_I, [C.POINTER(UdaSrc), _P, _I, _I, _I, _P, _L, _P, _I, _P]),
-    "uda_dwconv_dgrad": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _I, _P]),
-    "uda_dwconv_wgrad": (_I, [C.POINTER(UdaSrc), _P, _L, _I, _I, _I, _P, _P, _U, _I, _P]),
-    "uda_dwconv_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
-    "uda_dwconv_route_list": (C.c_char_p, []),
-    "uda_stem_workspace_bytes": (_U, [_L]),
-    "uda_stem_fwd": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
-    "uda_stem_wgrad": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _U, _P]),
-    "uda_stem_route": (_I, [_I, _I, _I, _I, _L, _I, C.c_char_p, _I]),
-    "uda_stem7_workspace_bytes": (_U, [_L]),
-    "uda_stem7_fwd": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
-    "uda_stem7_wgrad": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _U, _P]),
-    "uda_stem7s1_workspace_bytes": (_U, [_L]),
-    "uda_stem7s1_fwd": (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _P]),
-    "uda_stem7s1_wgrad": (_I, [_P, _I, _I, _I, _P, _L, _P, _P, _U, _P]),
-    "uda_conv3n_fwd": (_I, [C.POINTER(UdaSrc), _P, _I, _I, _P, _L, _P, _P]),
-    "uda_conv3n_workspace_bytes": (_U, [_I, _I]),
-    "uda_conv3n_wgrad": (_I, [C.POINTER(UdaSrc), _P, _L, _I, _I, _P, _P, _U, _P]),
-    "uda_maxpool_fwd": (_I, [C.POINTER(UdaSrc), _P, _L, _P, _L, _P]),
-    "uda_maxpool_bwd": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P]),
-    "uda_rows_stride": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
-    "uda_bn_add_relu": (_I, [C.POINTER(UdaSrc), C.POINTER(UdaSrc), _P, _L, _P]),
-    "uda_relu_gate": (_I, [_P, _L, _P, _L, _L, _I, _P, _L, _P]),
-    "uda_relayout_s2d": (_I, [_P, _I, _I, _I, _P, _P]),
-    "uda_s2d_fwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _I, _F, _P, _L, _I, _I, _P]),
-    "uda_s2d_bwd": (_I, [_P, _P, _L, _I, _I, _F, _I, _I, _I, _I, _I, _I, _P, _L, _I, _P]),
-    "uda_s2d_bwd_gate": (_I, [_P, _L, _I, _I, _P, _L, _F, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
-    "uda_x3_pack_s2d_fwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P]),
-    "uda_x3_pack_s2d_bwd": (_I, [_P, _L, _I, _I, _P, _L, _F, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "uda_bn_finalize": (_I, [_P, _I, _D, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
-    "uda_bn_running_replay": (_I, [_P, _P, _I, _D, _I, _F, _F, _P, _P, _P]),
-    "uda_bn_eval_coeffs": (_I, [_P, _P, _P, _P, _I, _F, _P, _P, _P]),
-    "uda_tn_gain": (_I, [_P, _P, _I, _D, _D, _F, _P, _P, _P, _P, _P, _P]),
-    "uda_tn_eval_coeffs": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P]),
-    "uda_bn_apply": (_I, [C.POINTER(UdaSrc), _P, _L, _P, _L, _P]),
-    "uda_colstats": (_I, [_P, _L, _L, _I, _I, _P, _P]),
-    "uda_colstats_window": (_I, [_P, _L, _L, _I, _I, _P, _I, _P]),
-    "uda_upsample_fwd_stats": (_I, [_P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _P, _I, _P]),
-    "uda_mc_seg_head": (_I, [_P, _L, _I, _I, _I, _I, _P, _L, _I, _L, _P, _L, _I, _I, _P, _P, _I, _P, _L, _F, _P, _L, _P, _P, _L, _P]),
-    "uda_bnbwd_reduce": (_I, [_P, _L, C.POINTER(UdaSrc), _P, _P, _P, _P]),
-    "uda_bnbwd_finalize": (_I, [_P, _I, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "uda_bnbwd_apply": (_I, [_P, _L, C.POINTER(UdaSrc), _P, _P, _P, _P, _P, _L, _P, _L, _P]),
-    "uda_bnbwd_reduce_lowrank": (_I, [_P, _L, _I, _P, C.POINTER(UdaSrc), _P, _P, _P, _P]),
-    "uda_bnbwd_apply_lowrank": (_I, [_P, _L, _I, _P, C.POINTER(UdaSrc), _P, _P, _P, _P, _P, _L, _P, _L, _P]),
-    "uda_upsample_fwd": (_I, [_P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _P]),
-    "uda_upsample_bwd": (_I, [_P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _P]),
-    "uda_head_upsample_fwd": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _I, _P]),
-    "uda_head_upsample_bwd": (_I, [_P, _I, _I, _I, _I, _P, _L, _I, _I, _I, _P]),
-    "uda_gap_fwd": (_I, [_P, _L, _I, _I, _I, _F, _P, _L, _P]),
-    "uda_broadcast_rows": (_I, [_P, _L, _I, _I, _I, _F, _P, _L, _P, _L, _P]),
-    "uda_dropout_mask": (_I, [_P, _L, _L, _I, _F, _U, _U, _P]),
-    "uda_seg_loss_fwd": (_I, [_P, _P, _L, _P, _P, _L, _P, _P, _P]),
-    "uda_seg_loss_bwd": (_I, [_P, _P, _L, _P, _P, _L, _P, _P, _P, _P]),
-    "uda_seg_counts": (_I, [_P, _P, _I, _I, _L, _F, _P, _P]),
-    "uda_mc_stats": (_I, [_P, _I, _L, _P, _P, _P]),
-    "uda_proto_weights": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
-    "uda_proto_workspace_bytes": (_U, [_L, _I]),
-    "uda_proto_reduce": (_I, [_P, _L, _L, _I, _P, _P, _P, _U, _P]),
-    "uda_proto_finalize": (_I, [_P, _I, _P, _P]),
-    "uda_proto_scatter_workspace_bytes": (_U, [_I]),
-    "uda_proto_scatter": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _U, _P]),
-    "uda_proto_bwd": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _L, _I, _P, _P]),
-    "uda_feat_dot4": (_I, [_P, _L, _L, _I, _P, _P, _P]),
-    "uda_feat_rank4": (_I, [_P, _P, _L, _I, _P, _L, _I, _P]),
-    "uda_adam_step": (_I, [_P, _P, _P, _P, _L, _D, _D, _D, _D, _L, _P]),
-    "uda_proto_align_fwd": (_I, [_P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P]),
-    "uda_proto_align_bwd": (_I, [_P, _P, _P, _F, _F, _I, _P, _P, _P]),
-    "uda_adv_loss_fwd": (_I, [_P, _I, _P, _I, _F, _F, _P, _P]),
-    "uda_adv_loss_bwd": (_I, [_P, _I, _P, _I, _F, _F, _P, _P, _P, _P]),
-    "uda_adv_s2d_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P]),
-    "uda_adv_s2d_bwd": (_I, [_P, _L, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "uda_upconv_fwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _I, _P, _P]),
-    "uda_upconv_bwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P]),
-    "uda_upconv_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _L, _I, _L, _L, _I, C.c_char_p, _I]),
-    "uda_upconv_route_list": (C.c_char_p, []),
-    "uda_postprocess_workspace_bytes": (_U, [_I, _I, _I]),
-    "uda_postprocess": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _U, _P]),
-    "uda_display_masks_workspace_bytes": (_U, [_I, _I, _I]),
-    "uda_display_masks": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _P, _U, _P]),
-    "uda_overlay_u8": (_I, [_P, _P, _I, _I, _I, _P, _P]),
-    "uda_image_u8": (_I, [_P, _I, _I, _I, _P, _P]),
-    "uda_surface_distance_workspace_bytes": (_U, [_I, _I, _I]),
-    "uda_surface_distance": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _U, _P]),
-    "uda_surface_profile_workspace_bytes": (_U, [_I, _I, _I]),
-    "uda_surface_profile": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _U, _P]),
-    "uda_disc_morphometry_workspace_bytes": (_U, [_I, _I, _I, _I]),
-    "uda_disc_morphometry": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _U, _P]),
-    "uda_mc_uncertainty": (_I, [_P, _I, _L, _P, _P, _P, _P, _P, _F, _P]),
-    "uda_selective_tables": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _I, _P, _P, _P, _P]),
-    "uda_tta_view": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "uda_tta_fuse": (_I, [C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P]),
-    "uda_normalize_tf_workspace_bytes": (_U, [_I, _I, _I]),
-    "uda_normalize_tf": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _U, _P]),
-    "uda_field_smooth": (_I, [_P, _I, _I, _I, _P, _I, _D, _P, _P, _P]),
-    "uda_elastic_warp": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "uda_photometric_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
-    "uda_geometry_u8_workspace_bytes": (_U, [_I, _I]),
-    "uda_geometry_u8": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _U, _P]),
-    "uda_photo_reduce_u8": (_I, [_P, _L, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
-    "uda_roi_cut_u8": (_I, [_P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
-    "uda_roi_paste_u8": (_I, [_P, _P, _P, _P, _I, _I, _P, _L, _P]),
-}
+# constants, argument blocks and every symbol (name -> (restype, argtypes)) as include/uda_clr_hip.h declares them
+STAT_SLOTS = CONSTANTS["UDA_STAT_SLOTS"]
+UdaSrc, UdaConvArgs, UdaWgradArgs = STRUCTS["uda_src_t"], STRUCTS["uda_conv_args_t"], STRUCTS["uda_wgrad_args_t"]
 
 
 def load_library(path: Optional[str] = None):
@@ -192,8 +50,8 @@ class UdaError(RuntimeError):
     pass
 
 
-_DW_FAMILY = {"": 0, "flat": 1, "tiled": 2, "cb": 3}      # UDA_DW_AUTO, _FLAT, _TILED, _CB
-_DW_OP = {"fwd": 0, "dgrad": 1, "wgrad": 2}                # UDA_DW_FWD, _DGRAD, _WGRAD
+_DW_FAMILY = {"": CONSTANTS["UDA_DW_AUTO"], **{f: CONSTANTS["UDA_DW_" + f.upper()] for f in ("flat", "tiled", "cb")}}
+_DW_OP = {op: CONSTANTS["UDA_DW_" + op.upper()] for op in ("fwd", "dgrad", "wgrad")}
 _UP_OP = {"fwd": 0, "bwd": 1}                              # uda_upconv_route's op
 
 
@@ -262,7 +120,7 @@ def unpack_host(layout, host):
 class HipKernels:
     name = "hip"
 
-    MFMA_F32, MFMA_BF16X3 = 0, 1
+    MFMA_F32, MFMA_BF16X3 = CONSTANTS["UDA_MFMA_F32"], CONSTANTS["UDA_MFMA_BF16X3"]
 
     def __init__(self, mfma=None):
         self.lib = load_library()

@@ -29,25 +29,13 @@ def bottleneck_bn_channels(blocks):
     return sum(2 * planes + 4 * planes * (2 if has_ds else 1) for pre, inp, planes, stride, dil, has_ds in blocks)
 
 
-def wide_s2(cin, cout):
-    """the implicit-GEMM kernels walk a strided output grid on their wide tiles only (uda_conv_fwd: Cout > 96, K > 192)"""
-    return cout > 96 and 9 * cin > 192
-
-
-def conv3x3(E, ctx, src, key, dil, stride, out, st, training, narrow=None):
-    """3x3 conv (pad = dil) of ``src`` at stride 1 | 2 into ``out`` with the statistics epilogue."""
-    K, N, H, W = E.K, src.N, src.H, src.W
-    cin, cout = src.C, out.shape[1]
-    if narrow is not None and narrow("fwd", cin, cout, stride, dil):
-        K.conv3n_fwd(src, E._w(ctx, key, "hwio"), stride, out, stats=st)
-    elif stride == 1 or wide_s2(cin, cout):
-        K.conv(src, E._w(ctx, key, "ohwi"), 3, dil, out, stats=st, **({"stride": stride} if stride != 1 else {}))
-    else:                                   # stride 1 + subsampling: four times the work
-        yfull = E._buf(src.x, N * H * W, cout)
-        K.conv(src, E._w(ctx, key, "ohwi"), 3, dil, yfull)
-        K.rows_stride(yfull, N, H, W, stride, out)
-        if training:
-            K.colstats(out, st, **({"N": N} if E.tn else {}))
+def conv3x3(E, ctx, src, key, dil, stride, out, st, narrow=None):
+    """3x3 conv (pad = dil) of ``src`` at stride 1 | 2 into ``out`` with the statistics epilogue: on the narrow direct kernel where
+    the backbone's table says so, else on the launch the library plans (it refuses a stride-2 conv below its wide tiles)."""
+    if narrow is not None and narrow("fwd", src.C, out.shape[1], stride, dil):
+        E.K.conv3n_fwd(src, E._w(ctx, key, "hwio"), stride, out, stats=st)
+    else:
+        E.K.conv(src, E._w(ctx, key, "ohwi"), 3, dil, out, stats=st, stride=stride)
 
 
 def conv3x3_backward(E, ctx, G, key, src, dy, dil, stride, out, narrow=None):
@@ -55,20 +43,16 @@ def conv3x3_backward(E, ctx, G, key, src, dy, dil, stride, out, narrow=None):
     gradient of a stride-2 conv is a stride-1 conv of the zero-stuffed gradient."""
     K, N, H, W = E.K, src.N, src.H, src.W
     cin, cout = src.C, dy.shape[1]
-    narrow_w = narrow is not None and narrow("wgrad", cin, cout, stride, dil)
-    native = stride == 1 or wide_s2(cin, cout)
-    if narrow_w:
+    if narrow is not None and narrow("wgrad", cin, cout, stride, dil):
         dw = torch.empty_like(ctx.params[key])
         K.conv3n_wgrad(src, dy, stride, dw)
         G[key] = dw
-    elif native:
+    else:
         E._wgrad(ctx, G, key, src, dy, 3, dil, stride)
     if stride != 1:
         full = E._buf(src.x, src.P, cout)
         K.rows_stride(dy, N, H, W, stride, full, scatter=True)
         dy = full
-    if not narrow_w and not native:
-        E._wgrad(ctx, G, key, src, dy, 3, dil)
     if narrow is not None and narrow("dgrad", cin, cout, stride, dil):
         K.conv3n_fwd(Act(dy, N, H, W), E._w(ctx, key, "hwio_dgrad"), 1, out)
     else:
@@ -93,7 +77,7 @@ def bottlenecks_forward(E, ctx, x, a, training, blocks, low_after, narrow=None):
         a1 = E._bn_act(ctx, pre + ".bn1", y1, N, H, W, st, P, training, ACT_RELU)
         y2 = E._buf(x, Po, planes)
         st = E._stats(ctx, planes, training)
-        conv3x3(E, ctx, a1, pre + ".conv2.weight", dil, stride, y2, st, training, narrow)
+        conv3x3(E, ctx, a1, pre + ".conv2.weight", dil, stride, y2, st, narrow)
         a2 = E._bn_act(ctx, pre + ".bn2", y2, N, Ho, Wo, st, Po, training, ACT_RELU)
         y3 = E._buf(x, Po, 4 * planes)
         st = E._stats(ctx, 4 * planes, training)

@@ -15,15 +15,10 @@ from ...acts import ACT_RELU, Act
 from .._tree import Holder, child, conv, normal_bn_init
 from ._bottleneck import bottleneck_bn_channels, bottleneck_tree, bottlenecks_backward, bottlenecks_forward, conv3x3, conv3x3_backward
 
-# Which narrow 3x3 convolutions of DRN (16 / 32 / 64 channels: layer1, layer2 and layer3's conv2, drn.py:131-136) run on the
-# direct kernels (uda_conv3n_*) instead of the implicit-GEMM route: (pass, Cin, Cout, stride of the LAYER) -> bool, as measured in
-# profiles/drn_head_kernels.md at B = 8 and 16.  "dgrad" runs as the stride-1 conv Cout -> Cin of the (zero-stuffed) gradient.
-# New / old time: head and layer3.0.conv2 0.20 - 0.57 (its input gradient 0.85 - 0.88); the stride-1 64 -> 64 convs of
-# layer3.1 / layer3.2 at 1/4 resolution: weight gradient 0.70 - 0.72, forward 1.70 / 1.00 and input gradient 1.58 / 0.95 at
-# B = 8 / 16 (512 tiles for 256 CUs), so those two stay where they were.  Shapes not listed stay on the implicit-GEMM route.
-# A/B switch UDA_CLR_DRN_NARROW: 1 = all listed shapes, 0 = none (stride 2 then runs at stride 1 + subsampling / zero
-# stuffing, four times the work).
-_DRN_NARROW_ENV = os.environ.get("UDA_CLR_DRN_NARROW", "")
+# Which passes of DRN's narrow 3x3 convolutions (16 / 32 / 64 channels: layer1, layer2 and layer3's conv2, drn.py:131-136) run on
+# the direct kernels (uda_conv3n_*) instead of the implicit-GEMM route: (pass, Cin, Cout, stride of the LAYER) -> bool, as measured
+# in profiles/drn_head_kernels.md.  "dgrad" runs as the stride-1 conv Cout -> Cin of the (zero-stuffed) gradient.  The two entries
+# read different weight layouts, so the engine asks here before it asks for the layout.
 _DRN_NARROW = {("fwd", 16, 16, 1): True, ("fwd", 16, 32, 2): True, ("fwd", 64, 64, 2): True, ("fwd", 64, 64, 1): False,
                ("wgrad", 16, 16, 1): True, ("wgrad", 16, 32, 2): True, ("wgrad", 64, 64, 2): True, ("wgrad", 64, 64, 1): True,
                ("dgrad", 16, 16, 1): True, ("dgrad", 16, 32, 2): True, ("dgrad", 64, 64, 2): True, ("dgrad", 64, 64, 1): False}
@@ -31,9 +26,7 @@ _DRN_NARROW = {("fwd", 16, 16, 1): True, ("fwd", 16, 32, 2): True, ("fwd", 64, 6
 
 def _narrow(what, cin, cout, stride, dil=1):
     """True when this pass of a 3x3 convolution layer (cin -> cout at ``stride``) runs on the narrow direct kernels."""
-    if dil != 1 or (what, cin, cout, stride) not in _DRN_NARROW:
-        return False
-    return _DRN_NARROW[(what, cin, cout, stride)] if _DRN_NARROW_ENV == "" else _DRN_NARROW_ENV != "0"
+    return dil == 1 and _DRN_NARROW.get((what, cin, cout, stride), False)
 
 
 D54_LAYERS = (1, 1, 3, 4, 6, 3, 1, 1)
@@ -132,7 +125,7 @@ class DRNExec:
             if k == 7:
                 K.stem7s1_fwd(x, E._w(ctx, key, "hwio"), y, st)
             else:
-                conv3x3(E, ctx, a, key, d, s, y, st, training, _narrow)
+                conv3x3(E, ctx, a, key, d, s, y, st, _narrow)
             src, H, W = a, Ho, Wo
             a = E._bn_act(ctx, "backbone." + bk, y, N, H, W, st, N * H * W, training, ACT_RELU)
             head.append(dict(key=key, src=src, a=a, stride=s, dil=d))
@@ -142,7 +135,7 @@ class DRNExec:
             key = "backbone." + ck + ".weight"
             y = E._buf(x, a.P, co)
             st = E._stats(ctx, co, training)
-            conv3x3(E, ctx, a, key, d, 1, y, st, training, _narrow)
+            conv3x3(E, ctx, a, key, d, 1, y, st, _narrow)
             src = a
             a = E._bn_act(ctx, "backbone." + bk, y, N, a.H, a.W, st, a.P, training, ACT_RELU)
             tail.append(dict(key=key, src=src, a=a, stride=1, dil=d))
