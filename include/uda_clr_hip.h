@@ -623,6 +623,31 @@ int uda_geometry_u8(const uint8_t* image_pool, const uint8_t* label_pool, const 
                     const int64_t* src_index, const int* records, int B, int S, uint8_t* image_out, uint8_t* label_out,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Fourier Domain Adaptation of the source batch (Yang & Soatto, CVPR 2020; uda_clr_amd/ops.py fda_transfer): a source
+ * image takes the amplitude spectrum of a target image on the (2 band + 1)^2 lowest frequencies Omega = [-band, band]^2 and keeps its
+ * own phase.  The reference has no such stage (train_process/Trainer_prototype_full.py aligns features and categories, not images):
+ * every definition here is this project's.  Per channel, with F[u,v] = sum_y sum_x s[y,x] e^{-2 pi i (u y / H + v x / W)},
+ *     out = src + (1 / HW) sum_{(u,v) in Omega} (|F_t[u,v]| P[u,v] - F_s[u,v]) e^{+2 pi i (u y / H + v x / W)},
+ *     P = F_s / |F_s|, and P = (1, 0) where |F_s[u,v]| <= 1e-6 H W (the zero-magnitude rule: numpy.angle(0) = 0),
+ * which is what fft2 / fftshift / swap the window [H/2 - band, H/2 + band] x [W/2 - band, W/2 + band] of the amplitude / ifftshift /
+ * ifft2 / real part gives.  All arithmetic from the bytes to the rounding is float64; twiddles are read from tables indexed by the
+ * integers (v x) mod W and (u y) mod H; every sum has one order fixed by the shapes, no atomics: equal inputs give equal bytes.
+ *   0 <= band <= UDA_FDA_MAX_BAND, 2 band + 2 <= min(H, W) (Omega stays clear of the Nyquist frequencies), 2 <= H, W <= 2048,
+ *   1 <= B, Bt <= 8192.  A null pointer, a value out of range, sizes that differ or a workspace that is too small return the error
+ *   before any launch and write nothing.  workspace: 16-byte aligned, uda_fda_workspace_bytes(B, Bt, H, W, band) bytes (Bt = 0: what
+ *   uda_fda_spectrum needs for B images); 0 for arguments out of range.
+ * uda_fda_spectrum: image_hwc uint8 [N,H,W,3] -> spectrum float64 [N,3,2 band + 1,band + 1,2] = (re, im) of F[n,c,u,v] at u = -band..band
+ *   (index u + band), v = 0..band; the other half of Omega is F[-u,-v] = conj(F[u,v]).  16-byte aligned.
+ * uda_fda_transfer: src_hwc uint8 [B,H,W,3], tgt_hwc uint8 [Bt,Ht,Wt,3] with (Ht, Wt) == (H, W); pair int32 [B] (DEVICE): source b takes
+ *   the amplitudes of target pair[b] - a value outside [0, Bt) is clamped into it, not checked; apply uint8 [B] (DEVICE) or null = all:
+ *   a sample with apply[b] == 0 is copied byte for byte.  -> out uint8 [B,H,W,3] = clip(rint(value), 0, 255), rint to even on ties. */
+#define UDA_FDA_MAX_BAND 64
+size_t uda_fda_workspace_bytes(int B, int Bt, int H, int W, int band);
+int uda_fda_spectrum(const uint8_t* image_hwc, int N, int H, int W, int band, double* spectrum, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int uda_fda_transfer(const uint8_t* src_hwc, int B, int H, int W, const uint8_t* tgt_hwc, int Bt, int Ht, int Wt, const int* pair,
+                     const uint8_t* apply, int band, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- whole-photograph prediction (uda_clr_amd/wholephoto.py): from a fundus photograph of any size to the S x S ROI the
  * generator takes, and back.  The reference reads ROIs that were cut beforehand (dataloaders/fundus_dataloader.py:41 `ROIs/image`) and
  * ships no such stage: every definition here is this project's, except the ROI resample, which is Pillow's.

@@ -22,6 +22,7 @@ _lib = None
 
 # constants, argument blocks and every symbol (name -> (restype, argtypes)) as include/uda_clr_hip.h declares them
 STAT_SLOTS = CONSTANTS["UDA_STAT_SLOTS"]
+FDA_MAX_BAND = CONSTANTS["UDA_FDA_MAX_BAND"]
 UdaSrc, UdaConvArgs, UdaWgradArgs = STRUCTS["uda_src_t"], STRUCTS["uda_conv_args_t"], STRUCTS["uda_wgrad_args_t"]
 
 
@@ -1188,6 +1189,54 @@ class HipKernels:
                                           src_index.data_ptr(), records.data_ptr(), B, S, io.data_ptr(), lo.data_ptr(),
                                           ws.data_ptr(), ws.numel(), self._stream()))
         return io, lo
+
+    # ------------------------------------------------------------------ Fourier style transfer (csrc/fda.hip)
+    def _ck_fda(self, who, band, *batches):
+        """contiguous uint8 [N,H,W,3] device batches of one size and a band the library takes -> (H, W, band)"""
+        for t in batches:
+            self._dev(t)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
+                raise ValueError("%s: contiguous uint8 [N, H, W, 3] batches (got %s %s)" % (who, t.dtype, tuple(t.shape)))
+        H, W = batches[0].shape[1:3]
+        if any(tuple(t.shape[1:3]) != (H, W) for t in batches):
+            raise ValueError("%s: source and target sizes differ: %s" % (who, [tuple(t.shape) for t in batches]))
+        band = int(band)
+        if not 0 <= band <= FDA_MAX_BAND or 2 * band + 2 > min(H, W):
+            raise ValueError("%s: band %d outside 0..%d or 2 band + 2 > min(H, W) of batches %s"
+                             % (who, band, FDA_MAX_BAND, [tuple(t.shape) for t in batches]))
+        return H, W, band
+
+    def fda_spectrum(self, image_u8, band, out=None):
+        """uint8 [N,H,W,3] -> float64 [N,3,2 band + 1,band + 1,2]: (re, im) of the DFT coefficients F[n,c,u,v], u = -band..band, v = 0..band
+        (include/uda_clr_hip.h, uda_fda_spectrum)."""
+        H, W, band = self._ck_fda("fda_spectrum", band, image_u8)
+        N = image_u8.shape[0]
+        shape = (N, 3, 2 * band + 1, band + 1, 2)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=image_u8.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("fda_spectrum: out must be contiguous float64 %s on the device (got %s %s)" % (shape, out.dtype, tuple(out.shape)))
+        ws = self._ws(image_u8, self.lib.uda_fda_workspace_bytes(N, 0, H, W, band))
+        self._ck(self.lib.uda_fda_spectrum(image_u8.data_ptr(), N, H, W, band, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
+
+    def fda_transfer(self, src_u8, tgt_u8, pair, band, apply=None, out=None):
+        """source uint8 [B,H,W,3] with the low-frequency amplitudes (band) of target uint8 [Bt,H,W,3] image pair[b] (int32 [B], device),
+        where apply[b] (uint8 [B], device; None = all) is set -> uint8 [B,H,W,3] (include/uda_clr_hip.h, uda_fda_transfer)."""
+        H, W, band = self._ck_fda("fda_transfer", band, src_u8, tgt_u8)
+        B, Bt = src_u8.shape[0], tgt_u8.shape[0]
+        if not pair.is_cuda or pair.dtype != torch.int32 or not pair.is_contiguous() or tuple(pair.shape) != (B,):
+            raise ValueError("fda_transfer: pair must be contiguous int32 [%d] on the device (got %s %s)" % (B, pair.dtype, tuple(pair.shape)))
+        if apply is not None and (not apply.is_cuda or apply.dtype != torch.uint8 or not apply.is_contiguous() or tuple(apply.shape) != (B,)):
+            raise ValueError("fda_transfer: apply must be contiguous uint8 [%d] on the device (got %s %s)" % (B, apply.dtype, tuple(apply.shape)))
+        if out is None:
+            out = torch.empty_like(src_u8)
+        elif out.dtype != torch.uint8 or out.shape != src_u8.shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("fda_transfer: out must be contiguous uint8 %s on the device (got %s %s)" % (tuple(src_u8.shape), out.dtype, tuple(out.shape)))
+        ws = self._ws(src_u8, self.lib.uda_fda_workspace_bytes(B, Bt, H, W, band))
+        self._ck(self.lib.uda_fda_transfer(src_u8.data_ptr(), B, H, W, tgt_u8.data_ptr(), Bt, H, W, pair.data_ptr(), _ptr(apply), band,
+                                           out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
 
     # ------------------------------------------------------------------ whole photographs (csrc/wholephoto.hip)
     @staticmethod

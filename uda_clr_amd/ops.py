@@ -293,6 +293,52 @@ def photometric_u8(image_u8, sp_pos, sp_count, sp_value, lut, erase_box):
                                     lut.contiguous(), erase_box.contiguous())
 
 
+def fda_band(beta, H, W):
+    """the band of Fourier Domain Adaptation at window ratio ``beta``: b = floor(beta * min(H, W)) (Yang & Soatto's ``np.floor(np.amin((h, w)) * L)``)"""
+    import math
+    return int(math.floor(float(beta) * min(int(H), int(W))))
+
+
+def fda_spectrum(image_u8, band):
+    """uint8 [N,H,W,3] on the device -> complex128 [N,3,2b+1,b+1]: F[n,c,u,v] = sum_y sum_x s[y,x] e^{-2 pi i (u y / H + v x / W)} for u = -b..b
+    (index u + b) and v = 0..b, the half of the window [-b, b]^2 that ``fda_transfer`` computes (the rest is its conjugate mirror).
+    float64 throughout; against numpy.fft.fft2 within 1e-12 * sum|s| (tests/test_fda_gpu.py)."""
+    return torch.view_as_complex(kernels().fda_spectrum(image_u8.contiguous(), band))
+
+
+def fda_transfer(src_u8, tgt_u8, beta=0.01, band=None, pair=None, apply=None):
+    """Fourier Domain Adaptation (Yang & Soatto, CVPR 2020) of a uint8 source batch [B,H,W,3] towards a uint8 target batch [Bt,H,W,3], on
+    the device: source image i takes the amplitude spectrum of target image pair[i] on the (2b+1)^2 lowest frequencies and keeps its own
+    phase.  Per channel, with F = fft2,
+
+        out = clip(rint(src + (1 / HW) sum_{(u,v) in [-b,b]^2} (|F_t[u,v]| P[u,v] - F_s[u,v]) e^{+2 pi i (u y / H + v x / W)}), 0, 255)
+
+    P = F_s / |F_s|, and P = (1, 0) where |F_s[u,v]| <= 1e-6 H W (the zero-magnitude rule: what numpy.angle(0) = 0 gives the literal
+    fft2 / fftshift / swap window / ifftshift / ifft2 statement, defined for a constant channel too).  float64 from the bytes to the
+    rounding; rint rounds ties to even, as numpy's.  ``band`` defaults to floor(beta * min(H, W)), ``pair`` to arange(B) % Bt; ``apply``
+    ([B], nonzero = transfer; None = all) leaves the other samples byte for byte.  Host-side ``pair`` values are checked here; values
+    already on the device are clamped into [0, Bt) by the kernel.  Labels are not involved.  Equal inputs give equal bytes.
+    The formula is pinned against the literal statement (tests/fda_ref.py) by tests/test_fda_cpu.py (restatement, identity, band-0 mean)
+    and byte for byte by tests/test_fda_gpu.py (rounding, zero-magnitude rule, clipping, pairing, apply)."""
+    if src_u8.dim() != 4 or tgt_u8.dim() != 4:
+        raise ValueError("fda_transfer: uint8 [B, H, W, 3] batches (got %s and %s)" % (tuple(src_u8.shape), tuple(tgt_u8.shape)))
+    B, H, W = src_u8.shape[:3]
+    Bt = tgt_u8.shape[0]
+    dev = src_u8.device
+    if band is None:
+        band = fda_band(beta, H, W)
+    if pair is None:
+        pair = torch.arange(B, dtype=torch.int32) % max(Bt, 1)
+    pair = torch.as_tensor(pair)
+    if not pair.is_cuda:
+        if pair.numel() != B or (B and (int(pair.min()) < 0 or int(pair.max()) >= Bt)):
+            raise ValueError("fda_transfer: pair must hold %d target indices in [0, %d) (got %s)" % (B, Bt, pair.tolist()))
+    pair = pair.to(dev).to(torch.int32).reshape(-1).contiguous()
+    if apply is not None:
+        apply = (torch.as_tensor(apply) != 0).to(torch.uint8).to(dev).reshape(-1).contiguous()
+    return kernels().fda_transfer(src_u8.contiguous(), tgt_u8.to(dev).contiguous(), pair, band, apply)
+
+
 class SourcePool(object):
     """A decoded dataset resident on the device for ``geometry_u8``: every image in one flat uint8 buffer, every mask in
     another, an int64 table of first pixels and an int32 (H0, W0) table, so sources of different sizes share a batch.

@@ -9,6 +9,7 @@ the loss as one fused kernel pair.  Data parallel when launched one process per 
 re-sharded by rank, generator gradients are averaged with one flat RCCL all-reduce, rank 0 logs,
 validates and checkpoints.
 """
+import os
 import os.path as osp
 import timeit
 
@@ -27,6 +28,10 @@ class Trainer(TrainerBase):
     def __init__(self, cuda, model_gen, optimizer_gen, val_loader, domain_loaderS,
                  domain_loaderT, out, max_epoch, stop_epoch=None,
                  lr_gen=1e-3, lr_decrease_rate=0.1, interval_validate=None, batch_size=8, warmup_epoch=10):
+        self._read_fda()
+        if self.fda_beta:
+            raise ValueError("UDA_CLR_FDA=%s: the source-only trainer has no target batch in its step to take a style from; "
+                             "unset it or use Trainer_prototype_full" % os.environ.get("UDA_CLR_FDA"))
         self.cuda = cuda
         self.warmup_epoch = warmup_epoch
         self.model_gen = model_gen

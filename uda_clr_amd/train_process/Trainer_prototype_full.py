@@ -86,6 +86,7 @@ class Trainer(TrainerBase):
         self.domain_loaderS = shard_loader(domain_loaderS, self.rank, self.world)
         self.domain_loaderT = shard_loader(domain_loaderT, self.rank, self.world)
         self.ops = HipOps()
+        self._read_fda()             # UDA_CLR_FDA: self.fda_beta, self.fda_p (train_step's _decode_pair)
         self._reducers = None
         if self.world > 1:
             self._reducers = [FlatGradAllReduce(list(m.parameters())) for m in (model_gen, model_dis, model_uncertainty_dis)]
@@ -223,7 +224,7 @@ class Trainer(TrainerBase):
         self._set_requires_grad((gen,), True)
         gen_params = [q for q in gen.parameters() if q.requires_grad]
         dis_params = [q for m in (dis, dis2) for q in m.parameters()]
-        sampleS, sampleT = self._decode(sampleS, getattr(self, 'domain_loaderS', None)), self._decode(sampleT, getattr(self, 'domain_loaderT', None))
+        sampleS, sampleT = self._decode_pair(sampleS, sampleT, getattr(self, 'domain_loaderS', None), getattr(self, 'domain_loaderT', None))
         imageS, target_map = self._to(sampleS['image']), self._to(sampleS['map'])
         target_boundary = self._to(sampleS['boundary'])
         imageT = self._to(sampleT['image'])

@@ -77,6 +77,7 @@ class HipOps:
         self.elastic_deform = ops.elastic_deform
         self.photometric_u8 = ops.photometric_u8
         self.geometry_u8 = ops.geometry_u8
+        self.fda_transfer = ops.fda_transfer
         self.SourcePool = ops.SourcePool
         self.consistency_loss = ops.consistency_loss
         self.proto_align = ops.proto_align
@@ -265,20 +266,20 @@ class TrainerBase(object):
             pools[id(ds)] = (ds, self.ops.SourcePool(ds.image_pool, ds.label_pool, self._device()))      # keeps ds alive: ids are not reused
         return pools[id(ds)][1]
 
-    def _decode(self, sample, dataset=None):
-        """A batch whose Normalize_tf + ToTensor tail was deferred (dataloaders.custom_transforms.DEVICE_TAIL: uint8 image and
-        grey mask) is decoded here, on the device, for the whole batch; any other sample passes through.  At level 3 the batch
-        holds source indices and geometry records instead of pixels; ``dataset`` (the loader it came from, or its dataset) names
-        the pool they index.  Order: geometry, elastic, photometric, normalize_tf."""
+    def _decode_head(self, sample, dataset=None):
+        """The uint8 batch a sample stands for, on the device: (image uint8 [B,S,S,3], label uint8 [B,S,S]) - after ``geometry_u8`` at
+        level 3, as handed over at levels 1 and 2 - or None for a sample that is decoded already (level 0)."""
         if 'src_index' in sample:
             if dataset is None:
                 raise ValueError("a batch of source indices (UDA_CLR_DEVICE_INPUT=3) cannot be decoded without its dataset: "
                                  "call _decode(sample, dataset=loader)")
-            iu, lu = self.ops.geometry_u8(self._source_pool(dataset), sample['src_index'], sample['geom'])
-        elif 'image_u8' in sample:
-            iu, lu = self._to(sample['image_u8']), self._to(sample['label_u8'])
-        else:
-            return sample
+            return self.ops.geometry_u8(self._source_pool(dataset), sample['src_index'], sample['geom'])
+        if 'image_u8' in sample:
+            return self._to(sample['image_u8']), self._to(sample['label_u8'])
+        return None
+
+    def _decode_tail(self, sample, iu, lu):
+        """elastic, photometric and normalize_tf of the uint8 batch (iu, lu) with the sample's records -> the decoded sample"""
         if 'aug_lut' in sample:          # UDA_CLR_DEVICE_INPUT=2: the recorded elastic / photometric outcomes, in the chain's order
             # (a chain without those transforms - the validation chain - still carries identity records from level 2 on and pays these
             # launches on them: same bytes out, left as it is)
@@ -292,6 +293,45 @@ class TrainerBase(object):
         out = dict(sample)
         out.update(image=image, map=mp, boundary=bd)
         return out
+
+    def _decode(self, sample, dataset=None):
+        """A batch whose Normalize_tf + ToTensor tail was deferred (dataloaders.custom_transforms.DEVICE_TAIL: uint8 image and
+        grey mask) is decoded here, on the device, for the whole batch; any other sample passes through.  At level 3 the batch
+        holds source indices and geometry records instead of pixels; ``dataset`` (the loader it came from, or its dataset) names
+        the pool they index.  Order: geometry, elastic, photometric, normalize_tf."""
+        head = self._decode_head(sample, dataset)
+        return sample if head is None else self._decode_tail(sample, *head)
+
+    def _read_fda(self):
+        """UDA_CLR_FDA=<beta>[,<p>]: Fourier style transfer of the source batch towards the target batch (ops.fda_transfer) at window
+        ratio beta, per sample with probability p (default 1).  Unset or beta 0: off.  Read once, at construction."""
+        text = os.environ.get("UDA_CLR_FDA", "").strip()
+        self.fda_beta, self.fda_p = 0.0, 1.0
+        if text:
+            try:
+                parts = [float(a) for a in text.split(",")]
+            except ValueError:
+                parts = []
+            if len(parts) not in (1, 2) or not 0.0 <= parts[0] < 0.5 or not 0.0 <= (parts + [1.0])[1] <= 1.0:
+                raise ValueError("UDA_CLR_FDA must be <beta>[,<p>] with 0 <= beta < 0.5 and 0 <= p <= 1, got %r" % text)
+            self.fda_beta, self.fda_p = parts[0], (parts + [1.0])[1]
+
+    def _decode_pair(self, sampleS, sampleT, datasetS=None, datasetT=None):
+        """The source and the target batch of one step.  With FDA off (``fda_beta`` 0) the two ``_decode`` calls.  With it on, the
+        source's uint8 batch takes the low-frequency amplitudes of the target's (ops.fda_transfer, sample i from target i % Bt, each
+        with probability ``fda_p``, drawn on the host) between the heads and the tails: the style is the target crop's before its own
+        noise and eraser, and the source's elastic and photometric draws act on the styled image.  Labels are not touched."""
+        if not getattr(self, 'fda_beta', 0.0):
+            return self._decode(sampleS, datasetS), self._decode(sampleT, datasetT)
+        headS, headT = self._decode_head(sampleS, datasetS), self._decode_head(sampleT, datasetT)
+        if headS is None or headT is None:
+            raise ValueError("UDA_CLR_FDA styles uint8 batches on the device: it needs UDA_CLR_DEVICE_INPUT >= 1 for both loaders "
+                             "(the %s batch arrived decoded)" % ("source" if headS is None else "target"))
+        B = headS[0].shape[0]
+        p = getattr(self, 'fda_p', 1.0)
+        apply = None if p >= 1.0 else (torch.rand(B) < p).to(torch.uint8)
+        styled = self.ops.fda_transfer(headS[0], headT[0], beta=self.fda_beta, apply=apply)
+        return self._decode_tail(sampleS, styled, headS[1]), self._decode_tail(sampleT, *headT)
 
     def _fetch(self, scalars):
         """The step's single host sync: the loss scalars plus the generator's device-side non-finite flag (a NaN / Inf that
