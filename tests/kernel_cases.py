@@ -2099,5 +2099,459 @@ CASES += LOSS_PROTO_EDGE_CASES
 LOSS_PROTO_CHANGED = ("seg counts 3x96", "proto retrify C=305 h=32")
 
 
+# ------------------------------------------------------------------------------------- bf16x3: the split, and one product per output
+# The dense cases above compare whole outputs with max|a - b| / max|b| at 2e-5 / 3e-5; a bf16x3 kernel that loses a third-order
+# piece product stays four times below that (tests/test_precision_cases_cpu.py plants such kernels and records the figures).
+# This section takes the accumulation out of the measurement:
+#   * pack cases: uda_x3_pack (raw, BN + activation, + keep-mask; activation rows and weight rows) against the statement
+#     SpecKernels.x3_pack, bit for bit, on a table of bit patterns;
+#   * probes: every output of a dense call is ONE product x * w, all other addends exact zeros, compared per element with the
+#     float64 product.  Bounds, in units of U24 = 2^-24 |x w| (derived, not fitted):
+#       fp32 routes    the accumulator holds round(x w) plus exact zeros: <= 1; the probes allow 2;
+#       bf16x3 routes  six exact piece products added into an fp32 accumulator (a3b1, a2b2, a1b3, a2b1, a1b2, a1b1): at most five
+#                      inexact additions of <= (1 + 2^-7) each, plus the three dropped products: bf16 keeps 8 significant bits, so
+#                      with pieces rounded to nearest |a2| <= 2^-8 |a|, |a3| <= 2^-16 |a| and a2b3 + a3b2 + a3b3 <= 2 (+ 2^-8):
+#                      <= 7.1; the probes allow 8.  A lost a1b3 / a2b2 product measures 117 / 225, a two-piece split 373.
+U24 = 2.0 ** -24
+X3_PACK_GRID_CAP = 65536 * 256          # uda_x3_pack: at most 65536 workgroups of 256 octets per step of its grid-stride loop
+
+
+def _i32(bits):
+    b = torch.as_tensor(bits, dtype=torch.int64)
+    return ((b & 0x7FFFFFFF) - (b & 0x80000000)).to(torch.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def x3_value_table():
+    """fp32 values by bit pattern, all inside the split's domain (|x| <= 0x7F7F7FFF): every exponent from the smallest normal to
+    2^126 with full random mantissas and both signs (four values each), +-0, subnormals (the build keeps them), round-up carries,
+    ties to even in the first and in the second piece, values whose first / second residual is negative, and the largest
+    magnitudes whose bf16 rounding is finite.  An odd number of entries, so rows of 16-multiples do not repeat lane by lane."""
+    g = gen(31)
+    e = torch.arange(1, 254, dtype=torch.int64)
+    rows = [(s << 31) | (e << 23) | torch.randint(0, 1 << 23, (253,), generator=g) for s in (0, 1, 0, 1)]
+    sub = torch.randint(1, 1 << 23, (64,), generator=g) | (torch.randint(0, 2, (64,), generator=g) << 31)
+    special = [0x00000000, 0x80000000,
+               0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF, 0x00400000, 0x00008000, 0x00018000, 0x0000FFFF, 0x00010000, 0x80010001,
+               0x3F7FFFFF, 0x3FFFFFFF, 0xBF7FFFFF, 0x3F7FFF80, 0x407FFFFF, 0x7EFFFFFF, 0x00FFFFFF,          # carries
+               0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x3F800080, 0x3F800180, 0x3F808080,          # ties
+               0x3F807FFF, 0xBF807FFF, 0x3F80FFFF, 0x3F8000FF, 0x3F80807F, 0x40490FDB,                      # negative residuals
+               0x7F7F7FFF, 0xFF7F7FFF, 0x7F7F0000, 0x7F123456, 0x7F7E7FFF, 0xFF7F7F80]                      # the top of the domain
+    t = _i32(torch.cat(rows + [sub, torch.tensor(special, dtype=torch.int64)])).view(torch.float32)
+    if t.numel() % 2 == 0:
+        t = torch.cat([t, _i32([0x3EAAAAAB]).view(torch.float32)])
+    assert bool(torch.isfinite(t).all()) and bool(torch.isfinite(t.to(torch.bfloat16).float()).all())
+    return t[torch.randperm(t.numel(), generator=g)]
+
+
+def _x3_out(rows, K, dev):
+    """a guarded buffer of uda_x3_packed_bytes(rows, K) bytes whose window is the body: the 64 trailing bytes are nobody's to write"""
+    body = rows * ((K + 15) // 16) * 96
+    return out_dev((1, body + 64), torch.uint8, dev, cols=body)[0], body
+
+
+def _x3_pack(K, a, dev, out):
+    return K.x3_pack(K._src(a) if hasattr(K, "_src") else a, a.P, a.C, dev, out=out)
+
+
+def case_x3_pack_raw(P, C, seed=0, on_device=False):
+    """XF 0, [P, C] activation rows with poisoned padding lanes: packed bytes == statement, bit for bit.  on_device: the operand is
+    built and the statement evaluated with torch on the test's device (the grid-stride shape: half a gigabyte of operand)."""
+    def run(dev):
+        K = hip()
+        tab = x3_value_table()
+        n = tab.numel()
+        if on_device:
+            blk = tab[(torch.arange(509 * C) + seed) % n].reshape(509, C).to(dev)
+            x = _poison(torch.empty(P, round4(C) + 4, device=dev))[:, :C]
+            x.copy_(blk.repeat(-(-P // 509), 1)[:P])
+            a = Act(x, 1, 1, P)
+            ah = Act(ro_dev(x, dev), 1, 1, P)
+        else:
+            x = padded(P, C, gen(seed))
+            x.copy_(tab[(torch.arange(P * C) + seed) % n].reshape(P, C))
+            a = Act(x, 1, 1, P)
+            ah = act_to(a, dev)
+        want = SPEC.x3_pack(a, P, C)
+        out, body = _x3_out(P, C, dev)
+        _x3_pack(K, ah, dev, out)
+        bad = out[:body] != want[:body].to(out.device)
+        DETAIL.clear()
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0]) // 2
+            DETAIL.update(first_bad=dict(row=i // (48 * ((C + 15) // 16)), block=i // 48 % ((C + 15) // 16), piece=i // 16 % 3, lane=i % 16))
+        return float(bad.sum()), 0.0
+    return run
+
+
+def case_x3_pack_rows(O, I, k, seed=0):
+    """weight rows: the relayouted [O, I, k, k] weight through x3_pack_rows"""
+    def run(dev):
+        K = hip()
+        tab = x3_value_table()
+        w = tab[(torch.arange(O * I * k * k) * 7 + seed) % tab.numel()].reshape(O, I, k, k).contiguous()
+        wl = ro_dev(K.relayout_ohwi(w.to(dev)), dev)
+        want = SPEC.x3_pack_rows(SPEC.relayout_ohwi(w))
+        out, body = _x3_out(wl.shape[0], wl.numel() // wl.shape[0], dev)
+        K.x3_pack_rows(wl, out=out)
+        return float((out[:body].cpu() != want[:body]).sum()), 0.0
+    return run
+
+
+def _quantised(x, bits):
+    """x rounded to ``bits`` significant bits"""
+    m, e = torch.frexp(x)
+    return torch.ldexp(torch.round(m * 2.0 ** bits) / 2.0 ** bits, e)
+
+
+def case_x3_pack_xf(P, C, act, mask, seed=0):
+    """XF 1 / XF 2: the three pieces sum (float64) to ONE fp32 value v; v lies within one fp32 ulp of x * scale + shift evaluated
+    in float64 and clamped (times mask_scale 2 where kept, exactly 0 where dropped); pieces == the statement's split of v, bit for
+    bit; the lanes [C, 16 nb) are zero pieces.  x carries 12 and scale 11 significant bits, so x * scale is exact in fp32 and an
+    fma and a mul + add round the same sum once (no cancellation against a rounded product); shift and hence v have full
+    mantissas.  Pre-activations within 1e-3 of a kink are moved away (asserted)."""
+    def run(dev):
+        g = gen(seed)
+        K = hip()
+        x = padded(P, C, g)
+        x.copy_(_quantised(2.0 * torch.randn(P, C, generator=g), 12))
+        scale, shift = _quantised(0.5 + torch.rand(C, generator=g), 11), 0.3 * torch.randn(C, generator=g)
+        pre = lambda: x.double() * scale.double() + shift.double()
+        for _ in range(4):
+            near = (pre().abs() < 1e-3) | ((pre() - 6).abs() < 1e-3)
+            x[near] = _quantised(x[near] + 0.25, 12)
+        assert not bool(((pre().abs() < 1e-3) | ((pre() - 6).abs() < 1e-3)).any()), "pre-activation on a kink in the test input"
+        m = None
+        if mask:
+            mb = torch.zeros(P, round4(C), dtype=torch.uint8)
+            mb[:, :C] = (torch.rand(P, C, generator=g) > 0.3).to(torch.uint8)
+            m = mb[:, :C]
+        a = Act(x, 1, 1, P, scale, shift, act, m, 2.0 if mask else 1.0)
+        out, body = _x3_out(P, C, dev)
+        _x3_pack(K, act_to(a, dev), dev, out)
+        nb = (C + 15) // 16
+        pc = out[:body].cpu().view(torch.bfloat16).reshape(P, nb, 3, 16).permute(2, 0, 1, 3).reshape(3, P, nb * 16)
+        bad = int((pc[:, :, C:].contiguous().view(torch.int16) != 0).sum())                          # lanes behind C: zero pieces
+        v = pc[:, :, :C].double().sum(0)
+        v32 = v.float()
+        bad += int((v32.double() != v).sum()) + int((~torch.isfinite(v)).sum())            # one fp32 value
+        ref = torch.clamp(pre(), 0.0, 6.0 if act == ACT_RELU6 else float("inf"))
+        if mask:
+            ref = ref * (m.double() * 2.0)
+            bad += int((v[m == 0] != 0).sum())
+        r32 = ref.float().abs()
+        ulp = (torch.nextafter(r32, torch.full_like(r32, float("inf"))) - r32).double()
+        bad += int((((v - ref).abs() > ulp) | ((ref == 0) & (v != 0))).sum())
+        want = torch.stack(SPEC.x3_split(v32))
+        bad += int((want.view(torch.int16) != pc[:, :, :C].contiguous().view(torch.int16)).sum())
+        return float(bad), 0.0
+    return run
+
+
+X3_PACK_BIG_P = X3_PACK_GRID_CAP // (2 * 128) + 3          # C = 2048: 256 octets per row; three rows are left for the second step
+assert X3_PACK_BIG_P * 128 * 2 > X3_PACK_GRID_CAP
+X3_PACK_CASES = [("x3 pack raw P=%d C=%d" % (P, C), case_x3_pack_raw(P, C, seed=P + C)) for C in (16, 40, 52, 304, 2048) for P in (1, 255, 257)]
+X3_PACK_CASES += [
+    ("x3 pack raw P=%d C=2048 (grid-stride loop takes a second step)" % X3_PACK_BIG_P, case_x3_pack_raw(X3_PACK_BIG_P, 2048, seed=5, on_device=True)),
+    ("x3 pack weight rows 3x3 72->40", case_x3_pack_rows(40, 72, 3)),
+    ("x3 pack weight rows 2x2 48->33", case_x3_pack_rows(33, 48, 2)),
+    ("x3 pack relu P=257 C=40", case_x3_pack_xf(257, 40, ACT_RELU, False, seed=1)),
+    ("x3 pack relu6 P=255 C=304", case_x3_pack_xf(255, 304, ACT_RELU6, False, seed=2)),
+    ("x3 pack relu mask P=257 C=52", case_x3_pack_xf(257, 52, ACT_RELU, True, seed=3)),
+    ("x3 pack relu6 mask P=255 C=2048", case_x3_pack_xf(255, 2048, ACT_RELU6, True, seed=4)),
+]
+CASES += X3_PACK_CASES
+
+
+def _full_mantissa(shape, g, e_lo, e_hi, signed=True):
+    """fp32 values +-2^e (1 + m 2^-23): e uniform in [e_lo, e_hi), all 23 mantissa bits random"""
+    e = torch.randint(e_lo, e_hi, shape, generator=g)
+    m = torch.randint(0, 1 << 23, shape, generator=g)
+    v = torch.ldexp(1.0 + m.double() / (1 << 23), e)
+    if signed:
+        v = v * (2.0 * torch.randint(0, 2, shape, generator=g) - 1.0)
+    return v.float()
+
+
+def _tap_offset(t, k, dil, origin):
+    """(dh, dw) of tap t, as SpecKernels._pad_taps lays the taps out"""
+    kh, kw = divmod(t, k)
+    if k == 3:
+        return (kh - 1) * dil, (kw - 1) * dil
+    if k == 2:
+        return kh - origin, kw - origin
+    return 0, 0
+
+
+def _probe_operand(N, H, W, C, g, mask):
+    """raw full-mantissa rows in [2^-3, 2^3), both signs; mask: a keep-mask with mask_scale 2 (an exact multiply)"""
+    x = padded(N * H * W, C, g)
+    x.copy_(_full_mantissa((N * H * W, C), g, -3, 3))
+    m = None
+    if mask:
+        mb = torch.zeros(N * H * W, round4(C), dtype=torch.uint8)
+        mb[:, :C] = (torch.rand(N * H * W, C, generator=g) > 0.3).to(torch.uint8)
+        m = mb[:, :C]
+    a = Act(x, N, H, W, None, None, ACT_NONE, m, 2.0 if mask else 1.0)
+    u = x.double() if m is None else x.double() * (m.double() * 2.0)
+    return a, u.reshape(N, H, W, C)
+
+
+def probe_positions(Cin, T, Cout, rounds=None):
+    """[rounds][Cout] flat K positions t * Cin + c of the one nonzero weight of each output channel.  rounds = None: position
+    (o + r * Cout) mod Ktot in round r of ceil(Ktot / Cout) - every position is hit.  rounds = n: n // T rounds per tap, each a run
+    of min(Cout, Cin) consecutive channels, the runs spread from channel 0 to the last channel."""
+    Ktot = Cin * T
+    o = torch.arange(Cout)
+    if rounds is None:
+        pos = torch.stack([(o + r * Cout) % Ktot for r in range(-(-Ktot // Cout))])
+    else:
+        rpt, n = rounds // T, min(Cout, Cin)
+        assert rpt >= 2
+        pos = torch.stack([t * Cin + (j * (Cin - n) + (rpt - 1) // 2) // (rpt - 1) + o % n for t in range(T) for j in range(rpt)])
+    hit = torch.unique(pos)
+    c = hit % Cin
+    assert set((hit // Cin).tolist()) == set(range(T)), "a tap is never probed"
+    assert set((c % 16).tolist()) == set(k % 16 for k in range(Cin)), "a lane k mod 16 is never probed"
+    assert 0 in (c // 16).tolist() and (Cin - 1) // 16 in (c // 16).tolist(), "the first / last 16-block of a row is never probed"
+    return pos, Ktot - hit.numel()
+
+
+_PROBE_INPUTS = {}
+
+
+def _probe_inputs(key, build):
+    """the CPU side of a probe (operands and float64 expectations of every round), built once and kept while the same probe runs
+    again (the other matrix mode, the stand-ins of tests/test_precision_cases_cpu.py); the next probe replaces it"""
+    if key not in _PROBE_INPUTS:
+        _PROBE_INPUTS.clear()
+        _PROBE_INPUTS[key] = build()
+    return _PROBE_INPUTS[key]
+
+
+def _is_x3(route):
+    return route.startswith(("x3", "wgrad-x3"))
+
+
+def _worst(got, want):
+    """(worst |got - want| / |want| over want != 0, its flat index); inf where got is not finite or not exactly 0 at want == 0"""
+    zero = want == 0
+    if not bool(torch.isfinite(got).all()) or bool((got[zero] != 0).any()):
+        bad = (~torch.isfinite(got)) | (zero & (got != 0))
+        return float("inf"), int(bad.reshape(-1).nonzero()[0])
+    e = torch.where(zero, torch.zeros_like(want), (got - want).abs() / want.abs().clamp_min(1e-300))
+    i = int(e.argmax())
+    return float(e.reshape(-1)[i]), i
+
+
+def case_conv_probe(N, H, W, Cin, Cout, k, dil, mask=False, addend=False, stats=False, origin=0, stride=1, rounds=None, dgrad=False,
+                    seed=40, *, route):
+    """Every output of the conv is one product: in round r output channel o has one nonzero weight, at flat K position
+    probe_positions()[r][o] (tap t, channel c), full-mantissa in [0.5, 2); the operand is raw and full-mantissa.  Expected, in
+    float64: x[stride * p + offset(t), c] * w, and exactly 0.0 where the tap leaves the image.  Fresh tensors in every round (the
+    packed forms ride on the tensor objects).  addend: an addend of exact zeros (in place, as the accumulating input gradient runs);
+    stats: a statistics accumulator, which the planner takes as "no K-split" - its sums are held to the dense cases' 2e-5;
+    dgrad: the weight goes through relayout_dgrad (rows = this conv's outputs, taps flipped).
+    -> (worst |y - x w| / |x w|, 2 U24 on an fp32 route, 8 U24 on a bf16x3 route)."""
+    T = k * k
+    pos, left_out = probe_positions(Cin, T, Cout, rounds)
+
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    P = N * Ho * Wo
+
+    def build():
+        g = gen(seed)
+        data = []
+        for r in range(pos.shape[0]):
+            a, u4 = _probe_operand(N, H, W, Cin, g, mask)
+            wv = _full_mantissa((Cout,), g, -1, 1)
+            t_o, c_o = pos[r] // Cin, pos[r] % Cin
+            w4 = torch.zeros(Cout, Cin, k, k)
+            w4[torch.arange(Cout), c_o, t_o // k, t_o % k] = wv
+            want = torch.zeros(P, Cout, dtype=torch.float64)
+            for t in set(t_o.tolist()):
+                dh, dw = _tap_offset(t, k, dil, origin)
+                pad = max(abs(dh), abs(dw))
+                up = torch.nn.functional.pad(u4, (0, 0, pad, pad, pad, pad))
+                tv = up[:, pad + dh:pad + dh + (Ho - 1) * stride + 1:stride, pad + dw:pad + dw + (Wo - 1) * stride + 1:stride]
+                cols = (t_o == t).nonzero().reshape(-1)
+                want[:, cols] = tv.reshape(P, Cin)[:, c_o[cols]] * wv[cols].double()
+            data.append((a, w4, want))
+        return data
+
+    def run(dev):
+        K = hip()
+        declared = _declared(route, getattr(K, "mfma", 0))
+        kw = {"stride": stride} if stride != 1 else {}
+        worst, where = 0.0, None
+        for r, (a, w4, want) in enumerate(_probe_inputs(run, build)):
+            a = Act(a.x, a.N, a.H, a.W, None, None, ACT_NONE, a.mask, a.mask_scale)        # a fresh descriptor: no packed form rides on it
+            t_o, c_o = pos[r] // Cin, pos[r] % Cin
+            g = gen(seed + 1 + r)
+            if dgrad:
+                wl = K.relayout_dgrad(w4.permute(1, 0, 2, 3).flip(2, 3).contiguous().to(dev))
+            else:
+                wl = K.relayout_ohwi(w4.to(dev))
+            wl = ro_dev(wl, dev)
+            out = to_dev(padded(P, Cout, g), dev)
+            ad = None
+            if addend:
+                out.zero_()
+                ad = out
+            st = out_dev((16, 2, Cout), torch.float64, dev, fill=0) if stats else None
+            args = (act_to(a, dev), wl, k, dil, out, None, ad, st)
+            if hasattr(K, "conv_route"):
+                _check_route(K.conv_route(*args, origin=origin, **kw), route, K.mfma)
+            DETAIL.clear()
+            DETAIL["route"] = declared
+            K.conv(*args, origin=origin, **kw)
+            e, i = _worst(out.double().cpu(), want)
+            if stats and e < float("inf"):
+                s = st.sum(0).cpu()
+                if max(rel(s[0], want.sum(0)), rel(s[1], (want ** 2).sum(0))) > 2e-5:
+                    e = float("inf")
+            if where is None or e > worst:
+                p, o = divmod(i, Cout)
+                worst, where = e, dict(round=r, row=p, column=o, k=int(pos[r][o]), tap=int(t_o[o]), channel=int(c_o[o]),
+                                       expected=float(want[p, o]), got=float(out[p, o]))
+        DETAIL.update(worst=where, units="%.2f" % (worst / U24), rounds=int(pos.shape[0]), k_positions_left_out=left_out)
+        return worst, (8 if _is_x3(declared) else 2) * U24
+    run.plan_query, run.route = _query("conv", N, H, W, Cin, Cout, k, dil, mask=mask, addend=addend, stats=stats, origin=origin, stride=stride), route
+    run.k_positions_left_out = left_out
+    return run
+
+
+def case_dgrad_probe(N, H, W, Cin, Cout, k, dil, rounds=None, seed=41, *, route):
+    """the accumulating input gradient of a conv Cin -> Cout: a conv of dy [P, Cout] towards Cin columns, added in place onto zeros"""
+    return case_conv_probe(N, H, W, Cout, Cin, k, dil, addend=True, rounds=rounds, dgrad=True, seed=seed, route=route)
+
+
+def wgrad_probe_pixels(N, Ho, Wo, route):
+    """The pixels of dy's grid that a weight-gradient probe puts its nonzeros on: the first and the last 16 pixels of every
+    pixel-range split of the planned route (S splits of ceil(chunks / S) chunks; a chunk is 16 pixels on the bf16x3 kernel, 32 on
+    the wide fp32 one, 64 on the narrow one) - that is all 16 residues of the pixel index mod 16 - and the corners and edge
+    midpoints of the first and the last image (first / last row and column)."""
+    P = N * Ho * Wo
+    chunk = 16 if route.startswith("wgrad-x3") else (32 if route.startswith("wgrad-ws") else 64)
+    S = int(route.split("S=")[1].split()[0])
+    nchunks = -(-P // chunk)
+    cps = -(-nchunks // S)
+    assert -(-nchunks // cps) == S
+    px = []
+    for s in range(S):
+        p0, p1 = s * cps * chunk, min((s + 1) * cps * chunk, P)
+        px += list(range(p0, min(p0 + 16, p1))) + list(range(max(p1 - 16, p0), p1))
+    for n in (0, N - 1):
+        for h, w in ((0, 0), (0, Wo - 1), (Ho - 1, 0), (Ho - 1, Wo - 1), (0, Wo // 2), (Ho - 1, Wo // 2), (Ho // 2, 0), (Ho // 2, Wo - 1)):
+            px.append((n * Ho + h) * Wo + w)
+    px = list(dict.fromkeys(px))
+    assert set(p % 16 for p in px) == set(range(min(16, P)))
+    return torch.tensor(px)
+
+
+def case_wgrad_probe(N, H, W, Cin, Cout, k, dil, mask=False, origin=0, stride=1, seed=42, *, route):
+    """Every weight gradient is one product: dy has one nonzero per column o, at pixel pi(o, r) = wgrad_probe_pixels()[(r * Cout + o)
+    mod n], in as many rounds as it takes to use every listed pixel.  Expected, in float64: dw[o, c, t] = dy[pi, o] *
+    x[stride * pi + offset(t), c], exactly 0.0 where the offset leaves the image.  -> (worst relative error, 2 / 8 U24)."""
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    Po = N * Ho * Wo
+    o = torch.arange(Cout)
+
+    def build(declared):
+        g = gen(seed)
+        px = wgrad_probe_pixels(N, Ho, Wo, declared)
+        data = []
+        for r in range(-(-px.numel() // Cout)):
+            a, u4 = _probe_operand(N, H, W, Cin, g, mask)
+            pi = px[(r * Cout + o) % px.numel()]
+            val = _full_mantissa((Cout,), g, -3, 3)
+            dy = padded(Po, Cout, g)
+            dy.zero_()
+            dy[pi, o] = val
+            n_, oh, ow = pi // (Ho * Wo), pi // Wo % Ho, pi % Wo
+            want = torch.zeros(Cout, Cin, k, k, dtype=torch.float64)
+            for t in range(k * k):
+                dh, dw_ = _tap_offset(t, k, dil, origin)
+                ih, iw = oh * stride + dh, ow * stride + dw_
+                ok = (ih >= 0) & (ih < H) & (iw >= 0) & (iw < W)
+                rows = u4[n_, ih.clamp(0, H - 1), iw.clamp(0, W - 1)] * ok.double().unsqueeze(1)
+                want[:, :, t // k, t % k] = rows * val.double().unsqueeze(1)
+            data.append((a, dy, pi, want))
+        return px, data
+
+    def run(dev):
+        K = hip()
+        declared = _declared(route, getattr(K, "mfma", 0))
+        kw = {"stride": stride} if stride != 1 else {}
+        px, data = _probe_inputs((run, declared), lambda: build(declared))
+        worst, where = 0.0, None
+        R = len(data)
+        for r, (a, dy, pi, want) in enumerate(data):
+            a = Act(a.x, a.N, a.H, a.W, None, None, ACT_NONE, a.mask, a.mask_scale)
+            out = out_dev((Cout, Cin, k, k), torch.float32, dev)
+            args = (act_to(a, dev), ro_dev(dy, dev), k, dil, out)
+            if hasattr(K, "wgrad_route"):
+                _check_route(K.wgrad_route(*args, origin=origin, **kw), route, K.mfma)
+            DETAIL.clear()
+            DETAIL["route"] = declared
+            K.conv_wgrad(*args, origin=origin, **kw)
+            e, i = _worst(out.double().cpu(), want)
+            if where is None or e > worst:
+                oc, rest = divmod(i, Cin * k * k)
+                c, t = divmod(rest, k * k)
+                worst, where = e, dict(round=r, column=oc, channel=c, tap=t, pixel=int(pi[oc]), expected=float(want.reshape(-1)[i]),
+                                       got=float(out.reshape(-1)[i]))
+        DETAIL.update(worst=where, units="%.2f" % (worst / U24), rounds=R, pixels=int(px.numel()))
+        return worst, (8 if _is_x3(declared) else 2) * U24
+    run.plan_query, run.route = _query("wgrad", N, H, W, Cin, Cout, k, dil, mask=mask, origin=origin, stride=stride), route
+    return run
+
+
+# Routes and shapes (the smallest shape the planner sends each way; without statistics a short conv splits its only round of tiles
+# over K, so the plain x3 128x128 routes are probed with a statistics accumulator).  K positions left out: only where said.
+# The plan sends no 3x3 conv to the fp32 wide tiles in bf16x3 mode ("ws ... k3" runs in the other mode of the x3 shapes).
+# Measured on an MI355X, worst per-product error in units of U24 (every probe within its derived bound, none needed explaining):
+#   f32 mode, and every fp32 family in either mode (ws, low, narrow, few, stream, heads, cout1, wgrad-ws): 0.98 - 1.00
+#   bf16x3 mode: x3 128x128 k3 2.45 (stride 2: 2.57, ragged 16-block: 2.45), x3 128x128 k1 2.56, x3 128x256 k1 2.59, x3 256x128 k3 2.71,
+#     x3 256x256 k3 2.51, x3 256x64 k3 2.48; x3+tail 128x128 k3 2.38 (2x2 origin 1: 2.40, accumulating input gradient: 2.58),
+#     x3+tail 128x128 k1 2.38, x3+tail 256x128 k3 2.64, x3+tail 128x256 k3 2.46, x3+tail 256x256 k3 2.73;
+#     wgrad-x3 128x256 2.45 (2x2: 2.21, stride 2: 2.38), wgrad-x3 256x256 2.47, wgrad-x3 128x128 2.28
+#   pack cases: bit-exact, fp32 subnormals included (the device keeps them, as the statement does).
+PROBE_CASES = [
+    ("conv probe 3x3 304->256 2x16x16 stats mask", case_conv_probe(2, 16, 16, 304, 256, 3, 1, mask=True, stats=True, route=("ws 64x128 k3 xf2", "x3 128x128 k3"))),
+    ("conv probe 1x1 2048->512 P=2312 stats", case_conv_probe(2, 34, 34, 2048, 512, 1, 1, stats=True, route=("ws 64x128 k1 xf0", "x3 128x128 k1"))),
+    ("conv probe 1x1 256->2304 P=2880", case_conv_probe(2, 40, 36, 256, 2304, 1, 1, route=("ws 128x256 k1 xf0", "x3 128x256 k1"))),
+    ("conv probe 3x3 64->128 P=38025", case_conv_probe(1, 195, 195, 64, 128, 3, 1, route=("ws 128x128 k3 xf0", "x3 256x128 k3"))),
+    ("conv probe 2x2 o0 64->160 P=49729", case_conv_probe(1, 223, 223, 64, 160, 2, 1, route=("ws 128x192 k3 xf0", "x3 256x256 k3"))),
+    ("conv probe 3x3 256->48 P=2442 (18 of 48 rounds: channels 0..47 and 208..255 of every tap)",
+     case_conv_probe(2, 33, 37, 256, 48, 3, 1, rounds=18, route=("low 64x64 pipe", "x3 256x64 k3"))),
+    ("conv probe 3x3 256->256 P=1152 mask (tail split)", case_conv_probe(2, 24, 24, 256, 256, 3, 1, mask=True, route=("ws 64x128 k3 xf2", "x3+tail 128x128 k3 full 0 tail 18x8"))),
+    ("conv probe 1x1 1536->300 P=1147 (tail split)", case_conv_probe(1, 37, 31, 1536, 300, 1, 1, route=("ws 64x128 k1 xf0", "x3+tail 128x128 k1 full 0 tail 27x8"))),
+    ("conv probe 2x2 o1 384->300 P=3811 zero addend (tail split)", case_conv_probe(1, 37, 103, 384, 300, 2, 1, addend=True, origin=1, route=("ws 64x128 k3 xf0", "x3+tail 256x128 k3 full 0 tail 45x5"))),
+    ("conv probe 3x3 176->512 P=2809 (tail split)", case_conv_probe(1, 53, 53, 176, 512, 3, 1, route=("ws 64x128 k3 xf0", "x3+tail 128x256 k3 full 0 tail 44x5"))),
+    ("conv probe 3x3 176->512 P=38809 (tail split after a full round)", case_conv_probe(1, 197, 197, 176, 512, 3, 1, route=("ws 128x128 k3 xf0", "x3+tail 256x256 k3 full 256 tail 48x5"))),
+    ("conv probe 3x3 s2 128->128 65x67", case_conv_probe(2, 65, 67, 128, 128, 3, 1, stride=2, route=("ws 64x128 k3 xf0", "x3 128x128 k3"))),
+    ("conv probe 2x2 o1 384->250 P=1147 (tail split)", case_conv_probe(1, 37, 31, 384, 250, 2, 1, origin=1, route=("ws 64x128 k3 xf0", "x3+tail 128x128 k3 full 0 tail 18x8"))),
+    ("conv probe 3x3 40->256 2x16x16 (ragged 16-block: Cin % 16 = 8)", case_conv_probe(2, 16, 16, 40, 256, 3, 1, route=("ws 64x128 k3 xf0", "x3 128x128 k3"))),
+    ("dgrad probe 3x3 304<-256 P=1152 accumulate (tail split)", case_dgrad_probe(2, 24, 24, 304, 256, 3, 1, route=("ws 64x128 k3 xf0", "x3+tail 128x128 k3 full 0 tail 27x8"))),
+    # the other forward families, fp32 in both modes
+    ("conv probe 1x1 96->24 (low)", case_conv_probe(2, 17, 13, 96, 24, 1, 1, route="low 64x64 xf0")),
+    ("conv probe 1x1 32->192 (narrow)", case_conv_probe(2, 12, 12, 32, 192, 1, 1, route="narrow 128x96 xf0")),
+    ("conv probe 1x1 196->160 P=12285 (few)", case_conv_probe(3, 65, 63, 196, 160, 1, 1, route="few 64x192 pipe xf0")),
+    ("conv probe 1x1 16->96 P=33800 (stream)", case_conv_probe(2, 130, 130, 16, 96, 1, 1, route="stream 8x3")),
+    ("conv probe 1x1 100->2 (heads)", case_conv_probe(2, 17, 13, 100, 2, 1, 1, route="heads 128x2")),
+    ("conv probe 2x2 o0 256->1 (cout1; 64 of 1024 positions: 16 channels 17 apart of every tap)", case_conv_probe(2, 9, 7, 256, 1, 2, 1, rounds=64, route="cout1 4x1")),
+    ("conv probe 1x1 320->256 P=4 (ws 1x1)", case_conv_probe(4, 1, 1, 320, 256, 1, 1, route="ws 64x128 k1 xf0")),
+    # weight gradients
+    ("wgrad probe 3x3 256->256 P=4608 mask", case_wgrad_probe(2, 48, 48, 256, 256, 3, 1, mask=True, route=("wgrad-ws 128x128 xf2 S=24 red8", "wgrad-x3 128x256 S=24 red8"))),
+    ("wgrad probe 3x3 64->192 P=8192", case_wgrad_probe(2, 64, 64, 64, 192, 3, 1, route=("wgrad-ws 128x128 xf0 S=64 red8", "wgrad-x3 256x256 S=64 red8"))),
+    ("wgrad probe 1x1 128->1024 P=4096", case_wgrad_probe(1, 64, 64, 128, 1024, 1, 1, route=("wgrad-ws 128x128 xf0 S=32 red8", "wgrad-x3 128x128 S=32 red8"))),
+    ("wgrad probe 2x2 o1 64->128 P=4608", case_wgrad_probe(2, 48, 48, 64, 128, 2, 1, origin=1, route=("wgrad-ws 128x128 xf0 S=36 red8", "wgrad-x3 128x256 S=36 red8"))),
+    ("wgrad probe 3x3 s2 64->128 41 images of 20x20", case_wgrad_probe(41, 20, 20, 64, 128, 3, 1, stride=2, route=("wgrad-ws 128x128 xf0 S=26 red8", "wgrad-x3 128x256 S=26 red8"))),
+    ("wgrad probe 1x1 960->320 P=128 (wgrad-ws)", case_wgrad_probe(2, 8, 8, 960, 320, 1, 1, route="wgrad-ws 128x128 xf0 S=1 red8")),
+]
+CASES += PROBE_CASES
+
+
 # every case begins with a cleared footprint registry and runs with guarded workspaces (footprint_violations() after it)
 CASES = [(name, footprinted(fn)) for name, fn in CASES]

@@ -139,6 +139,41 @@ class SpecKernels:
         res = torch.nn.grad.conv2d_weight(u, dw.shape, g, stride, 0, dil if ksize == 3 else 1)
         dw.copy_(res)
 
+    # ------------------------------------------------------------------ bf16x3 operands
+    def x3_split(self, x):
+        """The three bf16 pieces of fp32 ``x``: a1 = bf16(x), a2 = bf16(x - a1), a3 = bf16(x - a1 - a2), every conversion round to
+        nearest even (torch's ``.to(torch.bfloat16)``, the kernel's v_cvt_pk_bf16_f32), both residuals exact in fp32.
+        Domain: |x| <= 0x7F7F7FFF, the largest fp32 whose bf16 rounding is finite.  a1 + a2 + a3 == x exactly wherever the last
+        bit of x is worth at least 2^-133, bf16's smallest subnormal (all |x| >= 2^-110; smaller values only when their low bits
+        are zero); below, the third piece is rounded to that grid and |x - (a1 + a2 + a3)| <= 2^-134."""
+        assert x.dtype == torch.float32
+        a1 = x.to(torch.bfloat16)
+        r = x - a1.float()
+        a2 = r.to(torch.bfloat16)
+        a3 = (r - a2.float()).to(torch.bfloat16)
+        return a1, a2, a3
+
+    def x3_pack(self, src, rows, K, device=None, out=None):
+        """The packed operand of the bf16x3 kernels, as bytes: [rows][ceil(K / 16)][3][16] bf16 of the TRANSFORMED value
+        act(x * scale + shift) * mask * mask_scale of ``src`` (an Act; HipKernels takes its uda_src_t): element (row, k, piece q) at
+        ((row * nb + k // 16) * 3 + q) * 16 + k % 16, k >= K inside the last block packs as zero pieces.  uda_x3_packed_bytes
+        counts 64 bytes more that nobody writes: ``out`` (uint8, at least the body) keeps whatever it held there."""
+        u = transform(src)
+        assert tuple(u.shape) == (rows, K)
+        nb = (K + 15) // 16
+        full = u.new_zeros(rows, nb * 16)
+        full[:, :K] = u
+        body = torch.stack([p.reshape(rows, nb, 16) for p in self.x3_split(full)], 2).contiguous().view(torch.uint8).reshape(-1)
+        if out is None:
+            out = torch.zeros(body.numel() + 64, dtype=torch.uint8, device=body.device)
+        out[:body.numel()].copy_(body)
+        return out
+
+    def x3_pack_rows(self, w, out=None):
+        """a relayouted weight [rows, taps, K'] as packed rows of rows x (taps * K') values"""
+        m = w.reshape(w.shape[0], -1)
+        return self.x3_pack(Act(m, 1, 1, m.shape[0]), m.shape[0], m.shape[1], out=out)
+
     # ------------------------------------------------------------------ depthwise 3x3
     def _dw_input(self, src, dil, border_mode):
         u = _nchw(transform(src), src.N, src.H, src.W)

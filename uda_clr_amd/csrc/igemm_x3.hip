@@ -4,7 +4,10 @@
 // EXACTLY into three bf16 pieces, a = a1 + a2 + a3 (a1 = bf16(a), a2 = bf16(a - a1), a3 = a - a1 - a2: 3 x 8 significand bits,
 // the residuals are exact in fp32), and every product of two pieces is exact in the fp32 accumulator of the bf16 MFMA.  Of the
 // nine piece products of a * b the six with i + j <= 4 are kept:
-//     a*b ~= a1b1 + (a1b2 + a2b1) + (a1b3 + a2b2 + a3b1),      dropped terms <= 2^-24 |a b| (+ 2^-32): one fp32 rounding's worth,
+//     a*b ~= a1b1 + (a1b2 + a2b1) + (a1b3 + a2b2 + a3b1).
+// The dropped terms: bf16 keeps 8 significant bits, so with the pieces rounded to nearest |a2| <= 2^-8 |a| and |a3| <= 2^-16 |a|;
+// a2b3 and a3b2 are <= 2^-24 |a b| each, a3b3 <= 2^-32 |a b|: at most 2^-23 |a b| together (two fp32 roundings' worth, reached only
+// where both operands sit just above a power of two; a fraction of one on average),
 // so a dot product carries the same ~sqrt(K) * 2^-24 error as the fp32 fma chain it replaces (tests/bench_x3.py and
 // tests/noise_report.py measure both against float64).  Six v_mfma_f32_32x32x16_bf16 (32 cycles each) do the work of eight
 // v_mfma_f32_32x32x2_f32 (64 cycles each): 2.67x the matrix-pipe rate for the same fp32-level result.  Inputs, outputs,
@@ -33,7 +36,10 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 //     element (row, k, piece q) at ((row * nb + k / 16) * 3 + q) * 16 + k % 16,   nb = K blocks per row.
 // Activations: k = channel (nb = ceil(C / 16)).  Weights: k = position in the tap-chunked K order of the fp32 layout.
 
-// (v0, v1) -> the three bf16 pieces of each, packed (v0 in the low half)
+// (v0, v1) -> the three bf16 pieces of each, packed (v0 in the low half).
+// Domain: |v| <= 0x7F7F7FFF, the largest fp32 whose bf16 rounding is finite; above it the first piece is infinite and the split means
+// nothing.  The pieces sum to v exactly wherever v is a multiple of 2^-133, bf16's smallest subnormal (every |v| >= 2^-110); below
+// that the third piece is rounded to that grid (error <= 2^-134).  tests/kernel_spec.py x3_split states the same, bit for bit.
 __device__ __forceinline__ void x3_split2(float v0, float v1, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
     bf16x2 a = {(__bf16)v0, (__bf16)v1};                       // v_cvt_pk_bf16_f32 (round to nearest even)
     p1 = __builtin_bit_cast(uint32_t, a);

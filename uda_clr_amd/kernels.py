@@ -348,8 +348,12 @@ class HipKernels:
         """the bf16x3 GEMM launch alone (bench.py times this)"""
         self._ck(self.lib.uda_conv_fwd(C.byref(a), self._stream()))
 
-    def x3_pack(self, usrc: UdaSrc, rows, K, device):
-        out = torch.empty(int(self.lib.uda_x3_packed_bytes(rows, K)), dtype=torch.uint8, device=device)
+    def x3_pack(self, usrc: UdaSrc, rows, K, device, out=None):
+        """``out``: a caller's uint8 buffer of uda_x3_packed_bytes(rows, K) bytes (the kernel tests hand in a guarded one)"""
+        nbytes = int(self.lib.uda_x3_packed_bytes(rows, K))
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes and out.data_ptr() % 16 == 0
         self._ck(self.lib.uda_x3_pack(C.byref(usrc), out.data_ptr(), self._stream()))
         return out
 
@@ -376,14 +380,14 @@ class HipKernels:
         src._x3 = xs
         return xs
 
-    def x3_pack_rows(self, w):
+    def x3_pack_rows(self, w, out=None):
         """a relayouted weight [rows, taps, K'] (contiguous rows) as packed rows"""
         rows, klen = w.shape[0], w.numel() // w.shape[0]
         s = UdaSrc()
         s.x, s.ldx, s.N, s.H, s.W, s.C = w.data_ptr(), klen, 1, 1, rows, klen
         s.scale = s.shift = s.mask = None
         s.act, s.ldm, s.mask_scale = 0, 0, 1.0
-        return self.x3_pack(s, rows, klen, w.device)
+        return self.x3_pack(s, rows, klen, w.device, out)
 
     def conv_wgrad(self, src: Act, dy, ksize, dil, dw, origin=0, stride=1):
         """stride 2 (wide tiles only): ``dy`` lives on the strided output grid of the forward conv"""
