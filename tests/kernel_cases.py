@@ -6,6 +6,8 @@ from __future__ import annotations
 
 import functools
 import math
+import os
+import re
 
 import torch
 
@@ -54,6 +56,68 @@ def padded(P, C, g, dev=None, scale=1.0, dtype=torch.float32):
     return buf[:, :C]
 
 
+# ------------------------------------------------------------------------------------- launches past their grid caps
+# Many launches take grid = min(ceil(work / items), CAP) workgroups and walk the remainder with a grid-stride (or persistent-tile)
+# loop.  A "capped" case is shaped so that work > CAP * items, the last pass is partly filled and the work is no multiple of 256: the
+# loop body runs a second time, on other indices than the first.  The caps are read from their plain-number #defines in csrc, the
+# conditions are held without a GPU by tests/test_capped_cases_cpu.py, and a wrong value is reported with the pass it belongs to.
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uda_clr_amd", "csrc")
+CAP_FILES = ("launch_caps.h", "dw_plan.h", "upconv_plan.h", "drn_head.hip")
+
+
+@functools.lru_cache(maxsize=None)
+def cap_value(name):
+    """a workgroup cap of the library, from its ``#define NAME number`` in csrc"""
+    for f in CAP_FILES:
+        with open(os.path.join(CSRC, f)) as fh:
+            m = re.search(r"^#define %s (\d+)\b" % re.escape(name), fh.read(), re.M)
+        if m:
+            return int(m.group(1))
+    raise KeyError("no #define %s <number> in %s" % (name, ", ".join(CAP_FILES)))
+
+
+class Capped:
+    """One launch of a capped case.  launch: the kernel; cap: the name of its #define; work: its work items; items: work items
+    per workgroup; index(row, column) -> the work item that writes that element of the compared output (a [P, C] matrix, or any
+    other tensor flattened to [numel, 1]); None for an output that is a sum over all work items.  whole: why the work is a multiple of
+    256 at every shape of this kind (else a capped case's work must not be one)."""
+    def __init__(self, launch, cap, work, items=256, index=None, whole=None):
+        self.launch, self.cap, self.work, self.items, self.index, self.whole = launch, cap, int(work), items, index, whole
+
+    def grid(self):
+        return min(-(-self.work // self.items), cap_value(self.cap))
+
+    def passes(self):
+        return -(-self.work // (self.grid() * self.items))
+
+
+def by_group(C):
+    """one thread per pixel row and group of 4 channels, channel groups fastest: e = row * (C / 4) + column / 4"""
+    return lambda r, c: r * (C // 4) + c // 4
+
+
+def by_element(C):
+    return lambda r, c: r * C + c
+
+
+def rel_at(got, want, tol, cap=None):
+    """rel(got, want); beyond tol on a capped launch: an AssertionError that names the first wrong output's work item and the pass
+    of the grid-stride loop it belongs to (item // (grid * items per workgroup))"""
+    err = rel(got, want)
+    if cap is None or cap.index is None or err <= tol:
+        return err
+    a, b = got.detach().double().cpu(), want.detach().double().cpu()
+    if a.dim() != 2:
+        a, b = a.reshape(-1, 1), b.reshape(-1, 1)
+    bad = ~((a - b).abs() <= tol * max(b.abs().max().item(), 1e-30))          # (a NaN is wrong)
+    r, c = (int(v) for v in bad.nonzero()[0])
+    e = cap.index(r, c)
+    raise AssertionError("%s: rel err %.3e > %.1e; the first wrong output (row %d, column %d) is work item %d of %d = pass %d of the "
+                         "grid-stride loop (grid %d = %s, %d items per workgroup, %d of %d outputs wrong)"
+                         % (cap.launch, err, tol, r, c, e, cap.work, e // (cap.grid() * cap.items), cap.grid(), cap.cap, cap.items,
+                            int(bad.sum()), bad.numel()))
+
+
 # ------------------------------------------------------------------------------------- write footprints
 # Every device buffer a case hands to a kernel is a registered frame: the tensor the kernel sees, inside an allocation that the
 # test owns on both sides of it.  After the case, footprint_violations() compares the bits of every frame with a snapshot and
@@ -74,7 +138,9 @@ def padded(P, C, g, dev=None, scale=1.0, dtype=torch.float32):
 #       family 8 x 32 (N3_TW) and the 7x7 stride-1 stem 16 x 64 (H7_TH x H7_TW), resample one pixel per wave: the last tile of the
 #       last image ends at linear row (tiles_y * TH - 1) * W + tiles_x * TW - 1 of that image.  The largest over-hang in the suite
 #       is the stem's 1 x 33 x 80 shape (test_drn_kernels_gpu.py): tile rows 32..47 and columns 64..127 reach row 47 * 80 + 127 =
-#       3887 of P = 2640 rows, 1247 behind; the depthwise shapes stay below 8 * 16 + 16, upconv's tile kernel below 15 * 16 + 16.
+#       3887 of P = 2640 rows, 1247 behind; the depthwise shapes stay below 336 (the 8 x 8 tiles of the 1 x 97 x 95 stride-2 case: 49 x 48
+#       outputs, tile rows 48..55 reach row 55 * 48 + 47 = 2687 of P = 2352, 335 behind; the 3 x 3-tile seam shapes 195 and 111),
+#       upconv's tile kernel below 15 * 16 + 16.
 #   1280 is the next multiple of 256 above all of them.
 GUARD_ROWS = 1280          # multiple of 4: row 0 of the window keeps the poison phase and the 16-byte alignment of the allocation
 GUARD_BYTES = 4096
@@ -400,9 +466,13 @@ def _entry(route):
     return " ".join(route.split()[:2])          # "<family> <tile>" of a dense route, "<op> <kernel>" of a depthwise / stem one
 
 
-def case_dw(N, H, W, C, stride, dil, border, seed=3, *, route):
+def case_dw(N, H, W, C, stride, dil, border, seed=3, capped=False, seams=False, *, route):
     """route: the "<op> <kernel>" HipKernels.dw_route must begin with for the forward, input-gradient and weight-gradient call
-    (asserted before each call, and without a GPU by test_dw_plan_cpu.py)"""
+    (asserted before each call, and without a GPU by test_dw_plan_cpu.py).  capped: the flat input gradient runs past its cap;
+    seams: the tiled forward / weight gradient have real neighbours on every side of a tile (test_capped_cases_cpu.py holds both)."""
+    cap = Capped("dwconv_dgrad_kernel", "DW_DGRAD_MAX_WG", N * H * W * (C // 4), 256, by_group(C),
+                 whole="C / 4 = 256 channel groups: one pixel per workgroup" if C == 1024 else None) if capped else None
+
     def run(dev):
         g = gen(seed)
         src = make_src(N, H, W, C, g, True, ACT_RELU6)
@@ -427,7 +497,7 @@ def case_dw(N, H, W, C, stride, dil, border, seed=3, *, route):
         SPEC.dwconv_dgrad(dy, w9, stride, dil, N, H, W, dx_r)
         dx_h = to_dev(padded(N * H * W, C, g), dev)
         K.dwconv_dgrad(ro_dev(dy, dev), w9h, stride, dil, N, H, W, dx_h)
-        errs.append(rel(dx_h, dx_r))
+        errs.append(rel_at(dx_h, dx_r, 3e-5, cap))
         dw_r = torch.empty(C, 1, 3, 3)
         SPEC.dwconv_wgrad(src, dy, stride, dil, border, dw_r)
         dw_h = out_dev((C, 1, 3, 3), torch.float32, dev)
@@ -435,6 +505,7 @@ def case_dw(N, H, W, C, stride, dil, border, seed=3, *, route):
         errs.append(rel(dw_h, dw_r))
         return max(errs), 3e-5
     run.dw_query, run.route = dict(N=N, H=H, W=W, C=C, stride=stride, dil=dil), route
+    run.capped, run.seams = [cap] if capped else [], seams
     return run
 
 
@@ -659,7 +730,7 @@ def case_mc_seg_head(N, h, w, H, W, Cf, Cl, reps, mask, seed=10):
     return run
 
 
-def case_upsample_stats(N, h, w, H, W, C, Cs, seed=8):
+def case_upsample_stats(N, h, w, H, W, C, Cs, seed=8, capped=False):
     """uda_upsample_fwd_stats: the upsampled tensor AND its per-channel (sum, sum of squares) in channels [0, C) of a wider
     accumulator; uda_colstats_window: the remaining channels of the wide buffer (a strided column window) into the same accumulator
     (round 3: the BatchNorm(305) statistics of decoder.py:23 without a pass over the whole 305-channel buffer)."""
@@ -678,11 +749,17 @@ def case_upsample_stats(N, h, w, H, W, C, Cs, seed=8):
         K.colstats_window(wide_h[:, C:], st_h, C)
         full = torch.zeros(16, 2, Cs, dtype=torch.float64)
         SPEC.colstats(wide_r, full)                       # the one-pass statement over the whole buffer
-        return max(rel(wide_h, wide_r), rel(st_h.sum(0), st_r.sum(0)), rel(st_h.sum(0), full.sum(0))), 2e-5
+        return max(rel_at(wide_h[:, :C], wide_r[:, :C], 2e-5, cap), rel(wide_h, wide_r), rel(st_h.sum(0), st_r.sum(0)),
+                   rel(st_h.sum(0), full.sum(0))), 2e-5
+    cap = Capped("upsample_fwd_kernel<true, true>", "UPSAMPLE_STATS_MAX_WG", N * H * W * (C // 4), 256, by_group(C)) if capped else None
+    run.capped = [cap] if capped else []
     return run
 
 
-def case_resample(N, h, w, H, W, C, seed=6):
+def case_resample(N, h, w, H, W, C, seed=6, capped=False):
+    caps = [Capped("upsample_fwd_kernel", "RESAMPLE_MAX_WG", N * H * W * (C // 4), 256, by_group(C)),
+            Capped("upsample_bwd_kernel", "RESAMPLE_MAX_WG", N * h * w * (C // 4), 256, by_group(C))] if capped else [None, None]
+
     def run(dev):
         g = gen(seed)
         K = hip()
@@ -692,17 +769,22 @@ def case_resample(N, h, w, H, W, C, seed=6):
         K.upsample_fwd(ro_dev(x, dev), N, h, w, o_h, H, W)
         ref_t = torch.nn.functional.interpolate(x.reshape(N, h, w, C).permute(0, 3, 1, 2), size=(H, W), mode="bilinear",
                                                 align_corners=True).permute(0, 2, 3, 1).reshape(N * H * W, C)
-        errs = [rel(o_h, o_r), rel(o_h, ref_t)]
+        errs = [rel_at(o_h, o_r, 2e-5, caps[0]), rel(o_h, ref_t)]
         d = padded(N * H * W, C, g)
         dx_r, dx_h = padded(N * h * w, C, g), to_dev(padded(N * h * w, C, g), dev)
         SPEC.upsample_bwd(d, N, H, W, dx_r, h, w)
         K.upsample_bwd(ro_dev(d, dev), N, H, W, dx_h, h, w)
-        errs.append(rel(dx_h, dx_r))
+        errs.append(rel_at(dx_h, dx_r, 2e-5, caps[1]))
         return max(errs), 2e-5
+    run.capped = caps if capped else []
     return run
 
 
-def case_head(N, h, w, H, W, C, seed=7):
+def case_head(N, h, w, H, W, C, seed=7, capped=False):
+    # one thread per pixel; the forward's output is NCHW: flat element ((n * C + c) * H + oh) * W + ow belongs to pixel (n, oh, ow)
+    caps = [Capped("head_upsample_fwd_kernel", "RESAMPLE_MAX_WG", N * H * W, 256, lambda r, c: r // (C * H * W) * H * W + r % (H * W)),
+            Capped("head_upsample_bwd_kernel", "RESAMPLE_MAX_WG", N * h * w, 256, lambda r, c: r)] if capped else [None, None]
+
     def run(dev):
         g = gen(seed)
         K = hip()
@@ -712,22 +794,25 @@ def case_head(N, h, w, H, W, C, seed=7):
         K.head_upsample_fwd(ro_dev(x, dev), N, h, w, o_h)
         ref_t = torch.nn.functional.interpolate(x.reshape(N, h, w, C).permute(0, 3, 1, 2), size=(H, W), mode="bilinear",
                                                 align_corners=True)
-        errs = [rel(o_h, o_r), rel(o_h, ref_t)]
+        errs = [rel_at(o_h, o_r, 2e-5, caps[0]), rel(o_h, ref_t)]
         d = torch.randn(N, C, H, W, generator=g)
         base = padded(N * h * w, C, g)
         dx_r = base.clone()
         SPEC.head_upsample_bwd(d, dx_r, N, h, w, True)
         dx_h = to_dev(base, dev)
         K.head_upsample_bwd(ro_dev(d, dev), dx_h, N, h, w, True)
-        errs.append(rel(dx_h, dx_r))
+        errs.append(rel_at(dx_h, dx_r, 2e-5, caps[1]))
         dx_h2 = to_dev(base, dev)
         K.head_upsample_bwd(ro_dev(d, dev), dx_h2, N, h, w, False)
-        errs.append(rel(dx_h2, dx_r - base))
+        errs.append(rel_at(dx_h2, dx_r - base, 2e-5, caps[1]))
         return max(errs), 2e-5
+    run.capped = caps if capped else []
     return run
 
 
-def case_gap(N, HW, C, seed=8):
+def case_gap(N, HW, C, seed=8, capped=False):
+    cap = Capped("broadcast_rows_kernel", "RESAMPLE_MAX_WG", N * HW * (C // 4), 256, by_group(C)) if capped else None
+
     def run(dev):
         g = gen(seed)
         K = hip()
@@ -740,12 +825,19 @@ def case_gap(N, HW, C, seed=8):
         b_r, b_h = padded(N * HW, C, g), to_dev(padded(N * HW, C, g), dev)
         SPEC.broadcast_rows(o_r, N, b_r, 0.25, ad)
         K.broadcast_rows(ro_dev(o_r, dev), N, b_h, 0.25, ro_dev(ad, dev))
-        errs.append(rel(b_h, b_r))
+        errs.append(rel_at(b_h, b_r, 2e-5, cap))
         return max(errs), 2e-5
+    run.capped = [cap] if capped else []
     return run
 
 
-def case_dropout(P, C, p, seed=9):
+def case_dropout(P, C, p, seed=9, capped=False):
+    """capped: P * ceil(C / 8) work items exceed the cap.  The kernel's counter is the ELEMENT index e = row * ceil(C / 8) + group
+    (uda_dropout_mask), whatever the grid: the rows a second pass serves must not repeat those of the first, must keep the rate, and
+    the rows [0, 4096) must equal the mask of the same (seed, offset) and C drawn on 4096 rows, which fit one pass."""
+    G8 = (C + 7) // 8
+    cap = Capped("dropout_mask_kernel", "RESAMPLE_MAX_WG", P * G8, 256, by_element(G8)) if capped else None
+
     def run(dev):
         K = hip()
         m = out_dev((P, round4(C)), torch.uint8, dev, fill=0)[:, :C]      # uda_dropout_mask writes round4(C) bytes per row (its documented shape)
@@ -763,7 +855,25 @@ def case_dropout(P, C, p, seed=9):
         sig = ((1 - p) * p / (P * C)) ** 0.5
         err = abs(keep - (1 - p)) / (5 * sig)
         assert (col - (1 - p)).abs().max().item() < 8 * ((1 - p) * p / P) ** 0.5
+        if capped:
+            assert cap.grid() * 256 % G8 == 0
+            step = cap.grid() * 256 // G8                    # rows one pass of the grid serves
+            n2 = P - step                                    # rows [step, P): the second pass
+            assert 0 < n2 < step
+            a, b = m[:n2].cpu(), m[step:].cpu()
+            same_rows = int((a == b).all(1).sum())
+            # a counter taken from the thread index repeats every row; independent rows agree per byte with probability q
+            q = (1 - p) ** 2 + p ** 2
+            agree = (a == b).float().mean().item()
+            assert same_rows == 0, "%d of %d second-pass rows copy the row one grid stride (%d rows) before them" % (same_rows, n2, step)
+            assert abs(agree - q) < 5 * (q * (1 - q) / (n2 * C)) ** 0.5, "rows p and p + %d agree in %.4f of their bytes, %.4f expected" % (step, agree, q)
+            keep2 = b.float().mean().item()
+            err = max(err, abs(keep2 - (1 - p)) / (5 * ((1 - p) * p / (n2 * C)) ** 0.5))      # the second pass alone, its own 5 sigma
+            ms = out_dev((4096, round4(C)), torch.uint8, dev, fill=0)[:, :C]
+            K.dropout_mask(ms, p, 1234, 7)
+            assert torch.equal(m[:4096], ms), "the mask of a shape past the cap differs from the one-pass mask of the same (seed, offset) on the rows both have"
         return err, 1.0
+    run.capped = [cap] if capped else []
     return run
 
 
@@ -1167,17 +1277,26 @@ CASES += [
 ]
 
 
-def case_s2d(N, H, W, C, nchw, vh=None, vw=None, seed=20):
+def case_s2d(N, H, W, C, nchw, vh=None, vw=None, seed=20, capped=False):
+    vh_, vw_ = vh or H, vw or W
+    Hz, Wz = (vh_ + 5) // 2, (vw_ + 5) // 2
+    v4 = not nchw and C % 4 == 0        # (padded() rows are 16-byte aligned with a row stride that is a multiple of 4)
+    caps = [None, None]
+    if capped and v4:                   # 4 channels per thread: z is [Pz, 4C] in groups of 4, the source side [P, C] in groups of 4
+        caps = [Capped("s2d_fwd4_kernel", "S2D_MAX_WG", N * Hz * Wz * C, 256, by_group(4 * C)),
+                Capped("s2d_bwd4_kernel", "S2D_MAX_WG", N * H * W * (C // 4), 256, by_group(C))]
+    elif capped:                        # one element per thread; an NCHW destination is compared flat, in the kernel's own order
+        caps = [Capped("s2d_fwd_kernel", "S2D_MAX_WG", N * Hz * Wz * 4 * C, 256, by_element(4 * C)),
+                Capped("s2d_bwd_kernel", "S2D_MAX_WG", N * H * W * C, 256, by_element(1 if nchw else C))]
+
     def run(dev):
         g = gen(seed)
         K = hip()
-        vh_, vw_ = vh or H, vw or W
-        Hz, Wz = (vh_ + 5) // 2, (vw_ + 5) // 2
         src = torch.randn(N, C, H, W, generator=g) if nchw else padded(N * H * W, C, g)
         z_r, z_h = padded(N * Hz * Wz, 4 * C, g), to_dev(padded(N * Hz * Wz, 4 * C, g), dev)
         SPEC.s2d_fwd(src, nchw, N, H, W, C, vh_, vw_, 0.2, z_r)
         K.s2d_fwd(ro_dev(src, dev), nchw, N, H, W, C, vh_, vw_, 0.2, z_h)
-        errs = [rel(z_h, z_r)]
+        errs = [rel_at(z_h, z_r, 0.0, caps[0])]
         dz = torch.randn(N * Hz * Wz, 4 * C, generator=g)
         zs = torch.randn(N * Hz * Wz, 4 * C, generator=g)
         for sign in (None, zs):
@@ -1187,8 +1306,9 @@ def case_s2d(N, H, W, C, nchw, vh=None, vw=None, seed=20):
                 d_r, d_h = padded(N * H * W, C, g), to_dev(padded(N * H * W, C, g), dev)
             SPEC.s2d_bwd(dz, sign, 0.2, N, H, W, C, vh_, vw_, d_r, nchw)
             K.s2d_bwd(ro_dev(dz, dev), ro_dev(sign, dev), 0.2, N, H, W, C, vh_, vw_, d_h, nchw)
-            errs.append(rel(d_h, d_r))
+            errs.append(rel_at(d_h, d_r, 0.0, caps[1]))
         return max(errs), 0.0
+    run.capped = caps if capped else []
     return run
 
 
@@ -1243,12 +1363,40 @@ CASES += [
 ]
 
 
-def case_relayout_s2d(O, C, seed=21):
+def _k_row(chan, taps):
+    """floats of one row of a relayouted weight (uda_k_row / uda_relayout_s2d): channels padded to 4, from 32 on tap-chunked in 32s"""
+    Kc = round4(chan)
+    return Kc if taps == 1 else (taps * Kc if Kc < 32 else -(-Kc // 32) * taps * 32)
+
+
+def case_relayout_s2d(O, C, seed=21, capped=False):
+    """capped: both operands run past the cap.  The dgrad operand's 4C rows of a multiple of 128 floats are always a multiple of 256
+    work items; the forward operand (O rows) is shaped not to be."""
+    caps = [Capped("relayout_s2d_kernel (forward operand)", "RELAYOUT_S2D_MAX_WG", O * _k_row(4 * C, 4), 256, by_element(1)),
+            Capped("relayout_s2d_kernel (dgrad operand)", "RELAYOUT_S2D_MAX_WG", 4 * C * _k_row(O, 4), 256, by_element(1),
+                   whole="4C rows of a multiple of 128 floats")] if capped else [None, None]
+
     def run(dev):
         w = torch.randn(O, C, 4, 4, generator=gen(seed))
         K = hip()
-        return max(rel(K.relayout_s2d(w.to(dev), False), SPEC.relayout_s2d(w, False)),
-                   rel(K.relayout_s2d(w.to(dev), True), SPEC.relayout_s2d(w, True))), 0.0
+        return max(rel_at(K.relayout_s2d(w.to(dev), False), SPEC.relayout_s2d(w, False), 0.0, caps[0]),
+                   rel_at(K.relayout_s2d(w.to(dev), True), SPEC.relayout_s2d(w, True), 0.0, caps[1])), 0.0
+    run.capped = caps if capped else []
+    return run
+
+
+def case_relayout(O, I, k, seed=23, capped=False):
+    """uda_relayout_ohwi / uda_relayout_dgrad on their own (the dense cases compare them at widths of one pass)"""
+    caps = [Capped("relayout_ohwi_kernel", "RELAYOUT_MAX_WG", O * _k_row(I, k * k), 256, by_element(1)),
+            Capped("relayout_dgrad_kernel", "RELAYOUT_MAX_WG", I * _k_row(O, k * k), 256, by_element(1))] if capped else [None, None]
+
+    def run(dev):
+        w = torch.randn(O, I, k, k, generator=gen(seed))
+        K = hip()
+        wh = ro_dev(w, dev)
+        return max(rel_at(K.relayout_ohwi(wh), SPEC.relayout_ohwi(w), 0.0, caps[0]),
+                   rel_at(K.relayout_dgrad(wh), SPEC.relayout_dgrad(w), 0.0, caps[1])), 0.0
+    run.capped = caps if capped else []
     return run
 
 
@@ -1452,10 +1600,26 @@ def upconv_routes(K, q):
     return _entry(fwd), _entry(K.upconv_route("bwd", q["N"], q["h"], q["w"], q["H"], q["W"], q["C"], q["dil"], q["ldg"]))
 
 
-def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47, *, route=None):
+def _strip_index(H, W, C):
+    """upconv_fwd_strip_kernel's work item of output (row, column): strips of 4 pixels, the four vertically adjacent strips of a
+    4-row band consecutive, channel groups fastest"""
+    def index(r, c):
+        n, oh, ow = r // (H * W), r // W % H, r % W
+        sp = ((n * (H // 4) + oh // 4) * (W // 4) + ow // 4) * 4 + oh % 4
+        return sp * (C // 4) + c // 4
+    return index
+
+
+def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47, fwd_only=False, capped=False, remap=False, *, route=None):
     """route: the "fwd <kernel>" / "bwd <kernel>" HipKernels.upconv_route must begin with for the two calls (asserted on the real
     tensors before them, and without a GPU by test_upconv_plan_cpu.py, which also wants one of every case in CASES; None - the
-    shape fuzzer - asserts nothing).  As with the dense cases, where a label's remark and the route differ the route is what runs."""
+    shape fuzzer - asserts nothing).  As with the dense cases, where a label's remark and the route differ the route is what runs.
+    fwd_only: the backward (planned and declared all the same) is not run - its CPU statement takes 12 s at the shapes that take
+    the strip kernels past their cap.  capped: the strip forward runs past its cap; remap: the forward's grid is one on which
+    uda_xcd_remap is not the identity (test_capped_cases_cpu.py holds both)."""
+    cap = Capped("upconv_fwd_strip_kernel", "UPCONV_STRIP_MAX_WG", N * H * (W // 4) * (C // 4), 256, _strip_index(H, W, C),
+                 whole="H % 4 == 0 on the strip kernels and C / 4 = 64 channel groups" if C == 256 else None) if capped else None
+
     def run(dev):
         g = gen(seed)
         K = hip()
@@ -1473,7 +1637,9 @@ def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47, *, route=Non
         got = upconv_routes(K, q)
         assert route is None or got == tuple(route), "planned routes %r, the case declares %r" % (got, route)
         K.upconv_fwd(gl_h, N, h, w, o_h, H, W, ad_h, dil, st_h)
-        errs = [rel(o_h, o_r), rel(st_h.sum(0), st_r.sum(0))]
+        errs = [rel_at(o_h, o_r, 2e-5, cap), rel(st_h.sum(0), st_r.sum(0))]
+        if fwd_only:
+            return max(errs), 2e-5
         dy = padded(N * H * W, C, g)
         dg_r = torch.empty(N * h * w, 9 * C)
         SPEC.upconv_bwd(dy, N, H, W, dg_r, h, w, dil)
@@ -1484,6 +1650,7 @@ def case_upconv(N, h, w, H, W, C, dil=1, addend_rows=None, seed=47, *, route=Non
     run.upconv_query = dict(N=N, h=h, w=w, H=H, W=W, C=C, dil=dil, ldg=9 * C, ld_add=None if addend_rows is None else round4(C) + 4,
                             addend_rows=addend_rows or 0)
     run.route = route
+    run.capped, run.remap = [cap] if capped else [], remap
     return run
 
 
@@ -1623,8 +1790,11 @@ def case_adv_loss(n1, n2, label, scale, seed=72):
     return run
 
 
-def case_adv_s2d(N, C, H, W, op, seed=73):
+def case_adv_s2d(N, C, H, W, op, seed=73, capped=False):
     """First discriminator layer fed by logits: z = s2d(sigmoid | uncertainty map) and its adjoint incl. the map's derivative."""
+    caps = [Capped("s2d_fwd_kernel (uda_adv_s2d_fwd)", "S2D_MAX_WG", N * ((H + 5) // 2) * ((W + 5) // 2) * 4 * C, 256, by_element(4 * C)),
+            Capped("s2d_bwd_kernel (uda_adv_s2d_bwd)", "S2D_MAX_WG", N * C * H * W, 256, by_element(1))] if capped else [None, None]
+
     def run(dev):
         g = gen(seed)
         K = hip()
@@ -1638,7 +1808,8 @@ def case_adv_s2d(N, C, H, W, op, seed=73):
         d_r, d_h = torch.empty_like(x), out_dev((N, C, H, W), torch.float32, dev)
         SPEC.adv_s2d_bwd(dz, x, op, d_r)
         K.adv_s2d_bwd(ro_dev(dz, dev), ro_dev(x, dev), op, d_h)
-        return max(rel(z_h, z_r), rel(d_h, d_r)), 5e-6
+        return max(rel_at(z_h, z_r, 5e-6, caps[0]), rel_at(d_h, d_r, 5e-6, caps[1])), 5e-6
+    run.capped = caps if capped else []
     return run
 
 
@@ -2551,6 +2722,66 @@ PROBE_CASES = [
     ("wgrad probe 1x1 960->320 P=128 (wgrad-ws)", case_wgrad_probe(2, 8, 8, 960, 320, 1, 1, route="wgrad-ws 128x128 xf0 S=1 red8")),
 ]
 CASES += PROBE_CASES
+
+
+# ---------------------------------------------------------------- past the grid caps: second passes, tile seams, XCD remap
+# The shapes above fit one pass of every capped grid-stride loop, one LDS tile across and grids on which uda_xcd_remap is the
+# identity or has r = 0.  These are the smallest shapes of their kind at which
+#   - a grid-stride loop runs a second, partly filled pass (``capped=True``: work > CAP * items, work % 256 != 0; the caps are read
+#     from csrc, tests/test_capped_cases_cpu.py holds the conditions and fails when a cap moves),
+#   - the LDS-tiled depthwise kernels have 3 x 3 tiles x 2 images, ragged both ways (``seams=True``): a halo with real neighbours
+#     on all sides, the quirk-Q1 border value owed at the IMAGE edge only, tilesX > 1 in the tile decode, more than 16 workgroups in
+#     x so that blockIdx.x % UDA_STAT_SLOTS wraps,
+#   - uda_xcd_remap runs with q >= 1 and r != 0 (``remap=True``: grid >= 8, grid % 8 != 0),
+#   - the weight gradient's plan has more than 256 slabs and ends in wgrad_reduce_kernel<64> (declared by the route).
+# Left out on purpose: upconv_fwd_kernel (pixel), upconv_bwd_kernel and upconv_bwd_wave_kernel (UPCONV_FLAT_MAX_WG = 65536) and
+# x3_pack_kernel and its siblings (65536): crossing any of them takes 16.7 M work items, operands of 0.5 - 2.4 GB; they stay with the
+# whole-network tests.  fda.hip, uncertainty.hip and morphometry.hip size their grids differently and have their own suites.
+# The persistent tile loops of drn_head.hip are in tests/test_drn_kernels_gpu.py.
+# The weight-gradient cases keep the fp32 statement: over their 90 000 - 262 144 pixels it is within 2.1e-6 of its own float64
+# evaluation (measured per case: 5.1e-7, 4.0e-7, 2.0e-6, 5.8e-7), a fifteenth of the constructor's 3e-5.
+# CPU statement times (16 threads): no case above 5 s; the largest is the strip4 forward at 5 x (43 -> 128) x 256 with 1.7 s.
+_TILED = ("fwd tiled-8x16", "dgrad flat", "wgrad tiled-8x16")
+_TILED_S2 = ("fwd tiled-8x8", "dgrad flat", "wgrad tiled-8x8")
+CAPPED_CASES = [
+    ("dw 1024 s2 d1 border1 97x95 (dgrad past its cap on the stride-2 branch; 6x7 tiles x 32 channel slices)",
+     case_dw(1, 97, 95, 1024, 2, 1, 1, capped=True, route=_TILED_S2)),
+    ("dw 1024 s1 d2 border0 96x96 (dgrad past its cap on the general branch)", case_dw(1, 96, 96, 1024, 1, 2, 0, capped=True, route=_TILED)),
+]
+for _b in (0, 1):
+    CAPPED_CASES += [
+        ("dw seams 96 s1 d1 border%d 2x19x37 (3x3 tiles)" % _b, case_dw(2, 19, 37, 96, 1, 1, _b, seams=True, route=_TILED)),
+        ("dw seams 40 s1 d2 border%d 2x19x37 (3x3 tiles)" % _b, case_dw(2, 19, 37, 40, 1, 2, _b, seams=True, route=_TILED)),
+        ("dw seams 96 s2 d1 border%d 2x37x43 (3x3 tiles)" % _b, case_dw(2, 37, 43, 96, 2, 1, _b, seams=True, route=_TILED_S2)),
+        ("dw seams 40 s2 d2 border%d 2x37x43 (3x3 tiles)" % _b, case_dw(2, 37, 43, 40, 2, 2, _b, seams=True, route=_TILED_S2)),
+    ]
+CAPPED_CASES += [
+    ("upconv fwd/bwd 5 x (43x43 -> 128x128) x 256, forward only (strip4 past its cap, addend shared per image)",
+     case_upconv(5, 43, 43, 128, 128, 256, addend_rows=16384, fwd_only=True, capped=True, route=("fwd strip4", "bwd wave"))),
+    ("upconv fwd/bwd 7 x (25x25 -> 100x100) x 256, forward only (strip3 past its cap, addend shared per image)",
+     case_upconv(7, 25, 25, 100, 100, 256, addend_rows=10000, fwd_only=True, capped=True, route=("fwd strip3", "bwd wave"))),
+    ("upconv fwd/bwd 1 x (13x4 -> 52x16) x 64 (strip3 on 13 workgroups: XCD remap)", case_upconv(1, 13, 4, 52, 16, 64, remap=True, route=("fwd strip3", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (26x8 -> 52x16) x 64 (strip4 on 13 workgroups: XCD remap)", case_upconv(1, 26, 8, 52, 16, 64, remap=True, route=("fwd strip4", "bwd thread"))),
+    ("upconv fwd/bwd 1 x (12x12 -> 48x48) x 32 (tile kernel on 9 workgroups: XCD remap)", case_upconv(1, 12, 12, 48, 48, 32, remap=True, route=("fwd tile", "bwd thread"))),
+    ("upconv fwd/bwd 3 x (12x12 -> 48x48) x 32, addend (tile kernel on 27 workgroups: XCD remap)",
+     case_upconv(3, 12, 12, 48, 48, 32, addend_rows=2304, remap=True, route=("fwd tile", "bwd thread"))),
+    ("wgrad1x1 24->48 P=90000 (282 slabs, red64, 64x64 tiles)", case_wgrad(1, 300, 300, 24, 48, 1, 1, route="wgrad 64x64 S=282 red64")),
+    ("wgrad1x1 16->96 P=90000 mask (282 slabs, red64, 128x32 tiles)", case_wgrad(1, 300, 300, 16, 96, 1, 1, mask=True, route="wgrad 128x32 S=282 red64")),
+    ("wgrad3x3 16->16 P=135000 (422 slabs, red64, 32x128 tiles)", case_wgrad(1, 375, 360, 16, 16, 3, 1, route="wgrad 32x128 S=422 red64")),
+    ("wgrad1x1 24->48 P=262144 (the slab cap: 1024 slabs, red64)", case_wgrad(4, 256, 256, 24, 48, 1, 1, route="wgrad 64x64 S=1024 red64")),
+    ("upsample 257x259->301x299 C=256 (forward and backward past their cap)", case_resample(1, 257, 259, 301, 299, 256, capped=True)),
+    ("upsample + stats 65x65->257x257 C=64 into 72 (past the statistics kernel's cap)", case_upsample_stats(1, 65, 65, 257, 257, 64, 72, capped=True)),
+    ("head 2049x2051->2051x2053 C=1 (forward and backward past their cap)", case_head(1, 2049, 2051, 2051, 2053, 1, capped=True)),
+    ("gap C=256 3 x 25001 (broadcast_rows past its cap)", case_gap(3, 25001, 256, capped=True)),
+    ("dropout p=.5 140001 x 256 (past its cap)", case_dropout(140001, 256, 0.5, capped=True)),
+    ("s2d rows C=64 513x513 (4 channels per thread, forward and backward past their cap)", case_s2d(1, 513, 513, 64, False, capped=True)),
+    ("s2d nchw C=1 2049x2051 (scalar path, forward and backward past their cap)", case_s2d(1, 2049, 2051, 1, True, capped=True)),
+    ("adv_s2d sigmoid C=1 2049x2051 (past the cap)", case_adv_s2d(1, 1, 2049, 2051, 1, capped=True)),
+    ("adv_s2d entropy C=2 1449x1451 (past the cap)", case_adv_s2d(1, 2, 1449, 1451, 2, capped=True)),
+    ("relayout s2d 497<-264 (both operands past the cap)", case_relayout_s2d(497, 264, capped=True)),
+    ("relayout ohwi / dgrad 455x260x3x3 (past the cap)", case_relayout(455, 260, 3, capped=True)),
+]
+CASES += CAPPED_CASES
 
 
 # every case begins with a cleared footprint registry and runs with guarded workspaces (footprint_violations() after it)

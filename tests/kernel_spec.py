@@ -514,12 +514,18 @@ class SpecKernels:
         H, W = out.shape[2], out.shape[3]
         mh, mw = _bilinear_matrix(h, H, x.device, x.dtype), _bilinear_matrix(w, W, x.device, x.dtype)
         t = x.reshape(N, h, w, -1)
+        if H * h * W * w > 1 << 28:         # (einsum forms the outer product of the two matrices first: rows, then columns, as upsample_fwd)
+            out.copy_(torch.einsum("Ww,nHwc->ncHW", mw, torch.einsum("Hh,nhwc->nHwc", mh, t)))
+            return
         out.copy_(torch.einsum("Hh,Ww,nhwc->ncHW", mh, mw, t))
 
     def head_upsample_bwd(self, dout, dx, N, h, w, accumulate=False):
         H, W = dout.shape[2], dout.shape[3]
         mh, mw = _bilinear_matrix(h, H, dout.device, dout.dtype), _bilinear_matrix(w, W, dout.device, dout.dtype)
-        t = torch.einsum("Hh,Ww,ncHW->nhwc", mh, mw, dout).reshape(N * h * w, -1)
+        if H * h * W * w > 1 << 28:         # as the forward: one side at a time
+            t = torch.einsum("Ww,nchW->nhwc", mw, torch.einsum("Hh,ncHW->nchW", mh, dout)).reshape(N * h * w, -1)
+        else:
+            t = torch.einsum("Hh,Ww,ncHW->nhwc", mh, mw, dout).reshape(N * h * w, -1)
         if accumulate:
             dx.add_(t)
         else:

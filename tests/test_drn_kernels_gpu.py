@@ -126,6 +126,54 @@ def test_conv3n_matches_fp64(N, H, W, Cin, Cout, stride, lazy):
     assert footprint_violations() == [], "a kernel wrote outside its outputs: (buffer, first position)"
 
 
+# ---- the weight gradients past their workgroup caps.  stem7s1_wgrad_kernel (8 x 64 tiles) and conv3n_wgrad_kernel (8 x 32 tiles at
+# stride 1 below 64 output channels, else 4 x 32) launch min(tiles, cap) workgroups that walk their tiles with a stride of the grid
+# and write ONE partial row of the workspace each; the shapes above have at most 4 tiles.  Here a workgroup takes a second tile and
+# the last round is partly filled (tests/test_capped_cases_cpu.py holds that against H7W_MAX_WG / N3_MAX_WG_* of drn_head.hip).
+# BOUND stays: a workgroup sums at most two tiles of 512 (stem, 8 x 32: 256; 4 x 32: 128) products in fp32, fewer than the 3,000
+# the bound was worked out for; the partial rows are added in fp64.  Weight gradients only: the forward kernels launch one
+# workgroup per tile.
+STEM_CAPPED = [(2, 264, 520)]                                   # 2 * 33 * 9 = 594 tiles on 512 workgroups
+CONV_CAPPED = [(3, 100, 100, 64, 64, 1, True),                  # 3 * 25 * 4 = 300 tiles of 4 x 32 on 256 workgroups
+               (4, 200, 360, 16, 16, 1, False),                 # 4 * 25 * 12 = 1200 tiles of 8 x 32 on 1024
+               (2, 263, 1001, 16, 32, 2, True)]                 # stride 2, 132 x 501 outputs: 2 * 33 * 16 = 1056 tiles of 4 x 32 on 1024
+
+
+@pytest.mark.parametrize("N,H,W", STEM_CAPPED, ids=["n%d_%dx%d" % s for s in STEM_CAPPED])
+def test_stem7s1_wgrad_past_its_workgroup_cap_matches_fp64(N, H, W):
+    g = gen(40 + H)
+    x = torch.randn(N, 3, H, W, generator=g)
+    dy = padded(N * H * W, 16, g)
+    dwr = torch.nn.grad.conv2d_weight(x.double(), (16, 3, 7, 7), _nchw(dy.double(), N, H, W), 1, 3)
+    dwh = out_dev((16, 3, 7, 7), torch.float32, DEV)
+    hip().stem7s1_wgrad(ro_dev(x, DEV), ro_dev(dy, DEV), dwh)
+    torch.cuda.synchronize()
+    err = _rel(dwh, dwr)
+    print({"dw": err})
+    assert err < BOUND
+    assert footprint_violations() == [], "a kernel wrote outside its outputs: (buffer, first position)"
+
+
+@pytest.mark.parametrize("N,H,W,Cin,Cout,stride,lazy", CONV_CAPPED,
+                         ids=["n%d_%dx%d_%dto%d_s%d_%s" % (s[:6] + ("bn" if s[6] else "raw",)) for s in CONV_CAPPED])
+def test_conv3n_wgrad_past_its_workgroup_cap_matches_fp64(N, H, W, Cin, Cout, stride, lazy):
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    g = gen(300 + Cin + 3 * Cout + stride + H)
+    src = make_src(N, H, W, Cin, g, lazy, ACT_RELU)
+    u = src.x.double()
+    if lazy:
+        u = torch.relu(u * src.scale.double() + src.shift.double())
+    dy = padded(N * Ho * Wo, Cout, g)
+    dwr = torch.nn.grad.conv2d_weight(_nchw(u, N, H, W), (Cout, Cin, 3, 3), _nchw(dy.double(), N, Ho, Wo), stride, 1)
+    dwh = out_dev((Cout, Cin, 3, 3), torch.float32, DEV)
+    hip().conv3n_wgrad(act_to(src, DEV), ro_dev(dy, DEV), stride, dwh)
+    torch.cuda.synchronize()
+    err = _rel(dwh, dwr)
+    print({"dw": err})
+    assert err < BOUND
+    assert footprint_violations() == [], "a kernel wrote outside its outputs: (buffer, first position)"
+
+
 def test_statistics_are_added_into():
     """the statistics epilogue ADDS into its fp64 accumulator (several launches of one BatchNorm share it)"""
     N, H, W = 1, 9, 40

@@ -425,7 +425,9 @@ __global__ __launch_bounds__(256) void conv3n_wgrad_kernel(Conv3nArgs a) {
     }
 }
 
-static inline int n3_max_wg(int Cin, int Cout) { return Cin * Cout <= 512 ? 1024 : 256; }
+#define N3_MAX_WG_SMALL 1024      // Cin * Cout <= 512: partial rows of 4608 floats at most
+#define N3_MAX_WG_LARGE 256
+static inline int n3_max_wg(int Cin, int Cout) { return Cin * Cout <= 512 ? N3_MAX_WG_SMALL : N3_MAX_WG_LARGE; }
 
 static int n3_check(const uda_src_t* s, int Cout, int stride, const char* who) {
     UDA_REQUIRE(s && s->x && uda_aligned16(s->x) && s->N > 0 && s->H > 0 && s->W > 0, "%s: bad src", who);

@@ -22,6 +22,7 @@ enum DwFamily {
 #define DWB_ITER_RED 32        // ... and weight gradient
 #define DW_CMAX 1024           // flat / tiled forward and weight gradient: LDS sized for it
 #define DWB_CMAX 2048
+#define DW_DGRAD_MAX_WG 8192   // flat input gradient: one thread per pixel and channel group, grid-stride beyond this many workgroups
 // the <stride, tile rows, tile columns> instantiations of the tiled kernels
 #define DW_TILED_VARIANTS(X) X(1, 8, 16) X(2, 8, 8)
 
@@ -97,8 +98,8 @@ static DwPlan dw_plan(int op, int N, int H, int W, int C, int stride, int dil, i
         p.gy = uda_cdiv(C / 4, 1 << p.lg);
     } else if (op == DW_DGRAD) {
         if (p.family == DWF_TILED) { p.error = "the input gradient has no tiled kernel"; return p; }
-        const int g = uda_cdiv(P * (C / 4), 256);        // one thread per pixel and channel group, grid-stride beyond 8192 workgroups
-        p.gx = g > 8192 ? 8192 : g;
+        const int g = uda_cdiv(P * (C / 4), 256);        // one thread per pixel and channel group, grid-stride beyond the cap
+        p.gx = g > DW_DGRAD_MAX_WG ? DW_DGRAD_MAX_WG : g;
         p.gy = 1;
     } else {
         if (p.family == DWF_TILED) {

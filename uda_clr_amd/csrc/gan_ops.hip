@@ -7,6 +7,7 @@
 // crop of its output grid to the valid Ho x Wo region) and route gradients back (fusing the LeakyReLU gate,
 // read from the sign of z).  HBM-bound streaming passes, ~3 % of a discriminator forward+backward.
 #include "common.h"
+#include "launch_caps.h"
 
 struct S2dArgs {
     const float* src;     // forward: [N, Hs, Ws, C] rows (ld) or NCHW [N, C, Hs, Ws];  backward: dz [N, Hz, Wz, 4C]
@@ -157,7 +158,7 @@ extern "C" int uda_s2d_fwd(const float* src, int64_t ld_src, int nchw_in, int N,
     p.pre_op = 0; p.pre_x = nullptr;
     const bool v4 = !nchw_in && C % 4 == 0 && ld_src % 4 == 0 && ld_z % 4 == 0 && uda_aligned16(src) && uda_aligned16(z);
     const int64_t total = (int64_t)N * Hz * Wz * (v4 ? C : 4 * C);
-    const int grid = (int)(uda_cdiv(total, 256) > 16384 ? 16384 : uda_cdiv(total, 256));
+    const int grid = (int)(uda_cdiv(total, 256) > S2D_MAX_WG ? S2D_MAX_WG : uda_cdiv(total, 256));
     if (v4) hipLaunchKernelGGL(s2d_fwd4_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(s2d_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     UDA_LAUNCH_CHECK("s2d_fwd");
@@ -175,7 +176,7 @@ extern "C" int uda_s2d_bwd(const float* dz, const float* z_sign, int64_t ld_z, i
     const bool v4 = !nchw_out && C % 4 == 0 && ld_z % 4 == 0 && ld_dst % 4 == 0 && uda_aligned16(dz) && uda_aligned16(dst) &&
                     (!z_sign || uda_aligned16(z_sign));
     const int64_t total = (int64_t)N * Hs * Ws * (v4 ? C / 4 : C);
-    const int grid = (int)(uda_cdiv(total, 256) > 16384 ? 16384 : uda_cdiv(total, 256));
+    const int grid = (int)(uda_cdiv(total, 256) > S2D_MAX_WG ? S2D_MAX_WG : uda_cdiv(total, 256));
     if (v4) hipLaunchKernelGGL(s2d_bwd4_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(s2d_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     UDA_LAUNCH_CHECK("s2d_bwd");
@@ -195,7 +196,7 @@ extern "C" int uda_s2d_bwd_gate(const float* dz, int64_t ld_z, int Hz, int Wz, c
     const bool v4 = C % 4 == 0 && ld_z % 4 == 0 && ld_dst % 4 == 0 && ld_gate % 4 == 0 && uda_aligned16(dz) && uda_aligned16(dst) &&
                     uda_aligned16(gate_rows);
     const int64_t total = (int64_t)N * Hs * Ws * (v4 ? C / 4 : C);
-    const int grid = (int)(uda_cdiv(total, 256) > 16384 ? 16384 : uda_cdiv(total, 256));
+    const int grid = (int)(uda_cdiv(total, 256) > S2D_MAX_WG ? S2D_MAX_WG : uda_cdiv(total, 256));
     if (v4) hipLaunchKernelGGL(s2d_bwd4_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(s2d_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     UDA_LAUNCH_CHECK("s2d_bwd_gate");
@@ -214,7 +215,7 @@ extern "C" int uda_adv_s2d_fwd(const float* logits_nchw, int N, int C, int H, in
     p.N = N; p.Hs = H; p.Ws = W; p.C = C; p.vh = H; p.vw = W; p.Hz = Hz; p.Wz = Wz; p.nchw = 1; p.slope = 1.f;
     p.pre_op = pre_op; p.pre_x = nullptr;
     const int64_t total = (int64_t)N * Hz * Wz * 4 * C;
-    const int grid = (int)(uda_cdiv(total, 256) > 16384 ? 16384 : uda_cdiv(total, 256));
+    const int grid = (int)(uda_cdiv(total, 256) > S2D_MAX_WG ? S2D_MAX_WG : uda_cdiv(total, 256));
     hipLaunchKernelGGL(s2d_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     UDA_LAUNCH_CHECK("adv_s2d_fwd");
     return 0;
@@ -229,7 +230,7 @@ extern "C" int uda_adv_s2d_bwd(const float* dz, int64_t ld_z, int Hz, int Wz, co
     p.N = N; p.Hs = H; p.Ws = W; p.C = C; p.vh = H; p.vw = W; p.Hz = Hz; p.Wz = Wz; p.nchw = 1; p.slope = 1.f;
     p.pre_op = pre_op; p.pre_x = logits_nchw;
     const int64_t total = (int64_t)N * H * W * C;
-    const int grid = (int)(uda_cdiv(total, 256) > 16384 ? 16384 : uda_cdiv(total, 256));
+    const int grid = (int)(uda_cdiv(total, 256) > S2D_MAX_WG ? S2D_MAX_WG : uda_cdiv(total, 256));
     hipLaunchKernelGGL(s2d_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     UDA_LAUNCH_CHECK("adv_s2d_bwd");
     return 0;
@@ -266,7 +267,7 @@ extern "C" int uda_relayout_s2d(const float* w, int O, int C, int dgrad, float* 
     const int Kc = ((chan + 3) / 4) * 4;
     const int Kr = Kc < 32 ? 4 * Kc : ((Kc + 31) / 32) * 4 * 32;
     const int64_t total = (int64_t)rows * Kr;
-    const int grid = (int)(uda_cdiv(total, 256) > 8192 ? 8192 : uda_cdiv(total, 256));
+    const int grid = (int)(uda_cdiv(total, 256) > RELAYOUT_S2D_MAX_WG ? RELAYOUT_S2D_MAX_WG : uda_cdiv(total, 256));
     hipLaunchKernelGGL(relayout_s2d_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, O, C, dgrad, Kr, Kc, total, out);
     UDA_LAUNCH_CHECK("relayout_s2d");
     return 0;

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include "common.h"
 #include "conv_plan.h"
+#include "launch_caps.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -1016,10 +1017,10 @@ extern "C" int uda_conv_wgrad(const uda_wgrad_args_t* a, void* stream) {
     const int T = a->ksize * a->ksize;
     const int64_t total = (int64_t)a->Cout * T * a->src.C;
     if (p.red_q == 64)
-        hipLaunchKernelGGL(wgrad_reduce_kernel<64>, dim3(uda_cdiv(total, 4) > 4096 ? 4096 : uda_cdiv(total, 4)), dim3(256), 0, st,
+        hipLaunchKernelGGL(wgrad_reduce_kernel<64>, dim3(uda_cdiv(total, 4) > WGRAD_REDUCE_MAX_WG ? WGRAD_REDUCE_MAX_WG : uda_cdiv(total, 4)), dim3(256), 0, st,
                            k.slab, p.S, a->Cout, a->src.C, T, k.Kc, a->dw);
     else
-        hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3(uda_cdiv(total, 32) > 4096 ? 4096 : uda_cdiv(total, 32)), dim3(256), 0, st,
+        hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3(uda_cdiv(total, 32) > WGRAD_REDUCE_MAX_WG ? WGRAD_REDUCE_MAX_WG : uda_cdiv(total, 32)), dim3(256), 0, st,
                            k.slab, p.S, a->Cout, a->src.C, T, k.Kc, a->dw);
     UDA_LAUNCH_CHECK("wgrad_reduce");
     return 0;
@@ -1134,7 +1135,7 @@ __global__ void relayout_dw_kernel(const float* __restrict__ w, int C, float* __
 
 static inline int grid_for(int64_t total) {
     int g = uda_cdiv(total, 256);
-    return g > 4096 ? 4096 : (g < 1 ? 1 : g);
+    return g > RELAYOUT_MAX_WG ? RELAYOUT_MAX_WG : (g < 1 ? 1 : g);
 }
 
 extern "C" int uda_relayout_ohwi(const float* w, int O, int I, int k, float* out, void* stream) {

@@ -7,6 +7,7 @@
 // arithmetic, which outputs touched it) - deterministic, no float atomics.
 #include "common.h"
 #include "bilinear.h"
+#include "launch_caps.h"
 
 // STATS: per-channel (sum, sum of squares) of the OUTPUT accumulated on the way (a thread's channel group is fixed over its
 // grid-stride iterations because 256 % (C / 4) == 0; the host checks it): per-thread fp32 partial sums, the 256 / G threads of a
@@ -165,7 +166,7 @@ extern "C" int uda_upsample_fwd(const float* x, int64_t ldx, int N, int h, int w
     UDA_REQUIRE(N > 0 && h > 0 && w > 0 && H > 0 && W > 0, "uda_upsample_fwd: bad geometry");
     const int64_t total = (int64_t)N * H * W * (C / 4);
     int grid = uda_cdiv(total, 256);
-    if (grid > 16384) grid = 16384;
+    if (grid > RESAMPLE_MAX_WG) grid = RESAMPLE_MAX_WG;
     hipLaunchKernelGGL(upsample_fwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, N, h, w, C, out, ldo, H, W,
                        bil_scale(h, H), bil_scale(w, W), (double*)nullptr, 0);
     UDA_LAUNCH_CHECK("upsample_fwd");
@@ -184,7 +185,7 @@ extern "C" int uda_upsample_fwd_stats(const float* x, int64_t ldx, int N, int h,
     UDA_REQUIRE(stats && stat_C >= C && 256 % (C / 4) == 0, "uda_upsample_fwd_stats: needs an accumulator and 256 %% (C / 4) == 0");
     const int64_t total = (int64_t)N * H * W * (C / 4);
     int grid = uda_cdiv(total, 256);
-    if (grid > 4096) grid = 4096;                 // (fewer, longer threads: one LDS reduction + 2C fp64 atomics per workgroup)
+    if (grid > UPSAMPLE_STATS_MAX_WG) grid = UPSAMPLE_STATS_MAX_WG;                 // (fewer, longer threads: one LDS reduction + 2C fp64 atomics per workgroup)
     if (out)
         hipLaunchKernelGGL((upsample_fwd_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, N, h, w, C, out, ldo,
                            H, W, bil_scale(h, H), bil_scale(w, W), stats, stat_C);
@@ -322,7 +323,7 @@ extern "C" int uda_upsample_bwd(const float* dout, int64_t ldo, int N, int H, in
     UDA_REQUIRE(N > 0 && h > 0 && w > 0 && H > 0 && W > 0, "uda_upsample_bwd: bad geometry");
     const int64_t total = (int64_t)N * h * w * (C / 4);
     int grid = uda_cdiv(total, 256);
-    if (grid > 16384) grid = 16384;
+    if (grid > RESAMPLE_MAX_WG) grid = RESAMPLE_MAX_WG;
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dout, ldo, N, H, W, C, dx, ldx, h, w,
                        bil_scale(h, H), bil_scale(w, W));
     UDA_LAUNCH_CHECK("upsample_bwd");
@@ -384,7 +385,7 @@ extern "C" int uda_head_upsample_fwd(const float* x, int64_t ldx, int N, int h, 
                                      void* stream) {
     UDA_REQUIRE(x && out && C >= 1 && C <= 4 && ldx >= C && N > 0 && h > 0 && w > 0 && H > 0 && W > 0, "uda_head_upsample_fwd: bad args");
     int grid = uda_cdiv((int64_t)N * H * W, 256);
-    if (grid > 16384) grid = 16384;
+    if (grid > RESAMPLE_MAX_WG) grid = RESAMPLE_MAX_WG;
     hipLaunchKernelGGL(head_upsample_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, N, h, w, C, out, H, W,
                        bil_scale(h, H), bil_scale(w, W));
     UDA_LAUNCH_CHECK("head_upsample_fwd");
@@ -395,7 +396,7 @@ extern "C" int uda_head_upsample_bwd(const float* dout, int N, int C, int H, int
                                      int accumulate, void* stream) {
     UDA_REQUIRE(dout && dx && C >= 1 && C <= 4 && ldx >= C && N > 0 && h > 0 && w > 0 && H > 0 && W > 0, "uda_head_upsample_bwd: bad args");
     int grid = uda_cdiv((int64_t)N * h * w, 256);
-    if (grid > 16384) grid = 16384;
+    if (grid > RESAMPLE_MAX_WG) grid = RESAMPLE_MAX_WG;
     hipLaunchKernelGGL(head_upsample_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dout, N, C, H, W, dx, ldx, h, w,
                        accumulate, bil_scale(h, H), bil_scale(w, W));
     UDA_LAUNCH_CHECK("head_upsample_bwd");
@@ -477,7 +478,7 @@ extern "C" int uda_broadcast_rows(const float* g, int64_t ldg, int N, int HW, in
     if (addend) UDA_REQUIRE(uda_aligned16(addend) && ld_add % 4 == 0, "uda_broadcast_rows: bad addend layout");
     const int64_t total = (int64_t)N * HW * (C / 4);
     int grid = uda_cdiv(total, 256);
-    if (grid > 16384) grid = 16384;
+    if (grid > RESAMPLE_MAX_WG) grid = RESAMPLE_MAX_WG;
     hipLaunchKernelGGL(broadcast_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, ldg, N, HW, C, scale, addend,
                        ld_add, out, ldo);
     UDA_LAUNCH_CHECK("broadcast_rows");
@@ -527,7 +528,7 @@ extern "C" int uda_dropout_mask(uint8_t* mask, int64_t ldm, int64_t P, int C, fl
     UDA_REQUIRE(p >= 0.f && p < 1.f, "uda_dropout_mask: p must be in [0, 1)");
     const uint32_t thresh16 = (uint32_t)((double)p * 65536.0 + 0.5);
     int grid = uda_cdiv(P * ((C + 7) / 8), 256);
-    if (grid > 16384) grid = 16384;
+    if (grid > RESAMPLE_MAX_WG) grid = RESAMPLE_MAX_WG;
     hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, mask, ldm, P, C, thresh16, seed, offset);
     UDA_LAUNCH_CHECK("dropout_mask");
     return 0;

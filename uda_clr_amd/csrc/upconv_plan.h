@@ -42,6 +42,8 @@ static inline int upconv_foot(int o_min, int o_max, float scale, int n_in, int n
 }
 
 // workgroups of 256 threads for `threads` of them, at most `cap` (all kernels but the tile kernel walk the rest with a grid stride)
+#define UPCONV_FLAT_MAX_WG 65536     // pixel forward, thread / wave backward: one item per thread (wave), grid-stride beyond
+#define UPCONV_STRIP_MAX_WG 4096     // strip forward: bounded, the statistics epilogue issues 2*C atomics per workgroup
 static inline unsigned upconv_grid(int64_t threads, int64_t cap) {
     const int64_t g = (threads + 255) / 256;
     return (unsigned)(g > cap ? cap : g);
@@ -68,10 +70,10 @@ static UpconvPlan upconv_plan(int op, int N, int h, int w, int H, int W, int C, 
         const int64_t npix = (int64_t)N * h * w;
         if (C == 256 && dil == 1 && p.sh > 0.f && p.sw > 0.f && 2.f / p.sh + 6.f <= 32.f && 2.f / p.sw + 6.f <= 32.f && npix < lim32) {
             p.kernel = UPK_WAVE;
-            p.grid = upconv_grid(npix * 64, 65536);
+            p.grid = upconv_grid(npix * 64, UPCONV_FLAT_MAX_WG);
         } else {
             p.kernel = UPK_THREAD;
-            p.grid = upconv_grid(npix * G, 65536);
+            p.grid = upconv_grid(npix * G, UPCONV_FLAT_MAX_WG);
         }
         return p;
     }
@@ -86,7 +88,7 @@ static UpconvPlan upconv_plan(int op, int N, int h, int w, int H, int W, int C, 
                        (!has_addend || addend_rows * ld_add < lim32 * 4);
     if (!strip) {
         p.kernel = UPK_PIXEL;
-        p.grid = upconv_grid((int64_t)N * H * W * G, 65536);
+        p.grid = upconv_grid((int64_t)N * H * W * G, UPCONV_FLAT_MAX_WG);
         return p;
     }
     p.fused_stats = want_stats;
@@ -105,6 +107,6 @@ static UpconvPlan upconv_plan(int op, int N, int h, int w, int H, int W, int C, 
         }
     }
     p.kernel = sw3 < 0.98f ? UPK_STRIP3 : UPK_STRIP4;
-    p.grid = upconv_grid(strips, 4096);          // bounded: the statistics epilogue issues 2*C atomics per workgroup
+    p.grid = upconv_grid(strips, UPCONV_STRIP_MAX_WG);
     return p;
 }
