@@ -311,6 +311,16 @@ int uda_bnbwd_reduce_lowrank(const float* d, int64_t ldd, int k, const float* w,
 int uda_bnbwd_apply_lowrank(const float* d, int64_t ldd, int k, const float* w, const uda_src_t* y, const float* mean,
                             const float* invstd, const float* c1, const float* c2, const float* addend, int64_t ld_add,
                             float* out, int64_t ldo, void* stream);
+/* The two apply passes with a packed destination: out_x3 (uda_x3_packed_bytes(P, C) bytes, 16-byte aligned) receives the result as
+ * the bf16x3 operand uda_x3_pack would make of out - the same bytes, the split is exact and both destinations are written from one
+ * value - in the same pass.  out == NULL: only the packed form is written (a gradient matrix that only bf16x3 convs read);
+ * out_x3 == NULL: uda_bnbwd_apply / uda_bnbwd_apply_lowrank. */
+int uda_bnbwd_apply_x3(const float* dU, int64_t ldu, const uda_src_t* y, const float* mean,
+                       const float* invstd, const float* c1, const float* c2, const float* addend,
+                       int64_t ld_add, float* out, int64_t ldo, void* out_x3, void* stream);
+int uda_bnbwd_apply_lowrank_x3(const float* d, int64_t ldd, int k, const float* w, const uda_src_t* y, const float* mean,
+                               const float* invstd, const float* c1, const float* c2, const float* addend, int64_t ld_add,
+                               float* out, int64_t ldo, void* out_x3, void* stream);
 
 /* ---- resampling / pooling (F.interpolate bilinear align_corners=True, adaptive_avg_pool2d) */
 int uda_upsample_fwd(const float* x, int64_t ldx, int N, int h, int w, int C, float* out,
@@ -428,6 +438,10 @@ int uda_upconv_fwd(const float* g, int64_t ldg, int N, int h, int w, int C, int 
                    int64_t addend_rows, float* y, int64_t ldy, int H, int W, double* stats, void* stream);
 int uda_upconv_bwd(const float* dy, int64_t ldy, int N, int H, int W, int C, int dil, float* dg, int64_t ldg, int h, int w,
                    void* stream);
+/* uda_upconv_bwd with a packed destination: dg_x3 (uda_x3_packed_bytes(N*h*w, 9*C) bytes) receives what uda_x3_pack would make of
+ * dg, in the same pass; dg == NULL: only the packed form is written (ldg is not read, the launch is planned for ldg = 9*C). */
+int uda_upconv_bwd_x3(const float* dy, int64_t ldy, int N, int H, int W, int C, int dil, float* dg, int64_t ldg, void* dg_x3,
+                      int h, int w, void* stream);
 /* The launch planned for uda_upconv_fwd (op 0) / uda_upconv_bwd (op 1) as text: "fwd tile", "fwd strip3", "fwd strip4",
  * "fwd pixel", "bwd wave" or "bwd thread", then the grid and for the tile kernel R, RC and lds; a forward route with want_stats
  * ends in "stats fused" or "stats colstats"; "none" for refused arguments.  has_addend ... want_stats are not read for op 1.

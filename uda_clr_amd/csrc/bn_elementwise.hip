@@ -10,6 +10,7 @@
 // Reductions are two-stage and deterministic: per-workgroup fp32 partials, then an fp64 sum.
 // Thread mapping: cg = tid % G float4 channel groups, pl = tid / G pixel lanes (coalesced rows).
 #include "common.h"
+#include "x3_split.h"
 
 #define RED_ITER 32
 #define RED_CBLK 1024
@@ -553,14 +554,23 @@ struct LowRank {            // dU[p, c] = sum_{o < k} d[p, o] * w[o, c] (see Red
     const float* w;
 };
 
+// X3: out (fp32 rows, or null) and out_x3 (the same matrix as a packed bf16x3 operand, x3_split.h): both are written from the one
+// value r, so the packed bytes are those of the packing pass over out.  A workgroup's strip of an iteration is PP consecutive rows,
+// 6144 contiguous packed bytes where the channel groups fill the workgroup (256 % G == 0) in whole blocks (C % 16 == 0, one
+// channel block): those are staged in LDS in output order and stored as fully coalesced 16-byte rows, as x3_pack_kernel does (the
+// 8-byte stores of x3_store4, 32-byte runs at a 96-byte stride, cost as much as the packing pass they replace); two staging
+// buffers, so one barrier per iteration.  Other shapes store directly.
+template <bool X3>
 __global__ __launch_bounds__(256) void bnbwd_apply_kernel(const float* __restrict__ dU, int64_t ldu, uda_src_t y,
                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
                                                           const float* __restrict__ c1, const float* __restrict__ c2,
                                                           const float* addend, int64_t ld_add, float* out, int64_t ldo,
-                                                          int64_t P, LowRank lr) {
+                                                          int64_t P, LowRank lr, uint32_t* out_x3) {
     const int C = y.C, cblk0 = blockIdx.y * RED_CBLK;
     const int Cb = min(RED_CBLK, C - cblk0), G = (Cb + 3) >> 2, PP = 256 / G;
     const int tid = threadIdx.x, cg = tid % G, pl = tid / G;
+    __shared__ uint2 stg[X3 ? 2 * 768 : 1];
+    const bool staged = X3 && 256 % G == 0 && C % 16 == 0 && gridDim.y == 1;        // uniform: then no thread leaves below
     if (pl >= PP) return;
     const int c0 = cblk0 + cg * 4;
     // dx = ad + sc*(g - c1 - xhat*c2),  xhat = (y - mu)*is   ==>   dx = ad + sc*g - (k0 + k1*y)
@@ -613,37 +623,91 @@ __global__ __launch_bounds__(256) void bnbwd_apply_kernel(const float* __restric
             if (y.mask) g *= (float)((mk >> (8 * j)) & 0xffu) * y.mask_scale;
             r[j] = ad[j] + (sc[j] * g - (k0[j] + k1[j] * yv[j]));
         }
-        if (ok) st4_guard(out + p * ldo + c0, r, C - c0);
+        if (ok && (!X3 || out)) st4_guard(out + p * ldo + c0, r, C - c0);
+        if (X3) {
+            const int nb = x3_blocks(C);
+            if (staged) {
+                uint2* buf = stg + (it & 1) * 768;
+                uint32_t lo[3], hi[3];
+                x3_split2(r[0], r[1], lo[0], lo[1], lo[2]);
+                x3_split2(r[2], r[3], hi[0], hi[1], hi[2]);
+                const int slot = (pl * nb + (cg >> 2)) * 12 + (cg & 3);          // uint2 slots: a block is [piece][4 granules]
+#pragma unroll
+                for (int q = 0; q < 3; ++q) buf[slot + q * 4] = make_uint2(lo[q], hi[q]);
+                __syncthreads();
+                const int64_t row0 = base + (int64_t)it * PP;
+                const int64_t left = (min((int64_t)PP, P - row0)) * nb * 6;      // 16-byte units of the rows that exist (<= 0: none)
+                uint4* dst = reinterpret_cast<uint4*>(out_x3) + row0 * nb * 6;
+                const uint4* src4 = reinterpret_cast<const uint4*>(buf);
+                if (tid < left) dst[tid] = src4[tid];
+                if (tid < 128 && tid + 256 < left) dst[tid + 256] = src4[tid + 256];
+            } else if (ok) {
+                x3_store4(out_x3, p, nb, c0, r, C - c0);
+                if (c0 + 4 >= C) x3_store_pad(out_x3, p, nb, c0 + 4);       // the thread of the last columns: the rest of a ragged block
+            }
+        }
     }
+}
+
+// the checks both packed-output entries share: an fp32 destination, a packed one, or both
+static int bnbwd_apply_dst_check(const char* who, const float* out, int64_t ldo, const void* out_x3) {
+    UDA_REQUIRE(out || out_x3, "%s: no destination (out, out_x3 or both)", who);
+    UDA_REQUIRE(!out || (uda_aligned16(out) && ldo % 4 == 0), "%s: bad out layout", who);
+    UDA_REQUIRE(!out_x3 || uda_aligned16(out_x3), "%s: out_x3 must be 16-byte aligned", who);
+    return 0;
+}
+
+extern "C" int uda_bnbwd_apply_x3(const float* dU, int64_t ldu, const uda_src_t* y, const float* mean, const float* invstd,
+                                  const float* c1, const float* c2, const float* addend, int64_t ld_add, float* out,
+                                  int64_t ldo, void* out_x3, void* stream) {
+    if (int e = src_check(y, "uda_bnbwd_apply")) return e;
+    UDA_REQUIRE(y->scale && mean && invstd && c1 && c2, "uda_bnbwd_apply: needs scale/shift/mean/invstd/c1/c2");
+    UDA_REQUIRE(dU && uda_aligned16(dU) && ldu % 4 == 0, "uda_bnbwd_apply: bad dU layout");
+    if (int e = bnbwd_apply_dst_check("uda_bnbwd_apply", out, ldo, out_x3)) return e;
+    if (addend) UDA_REQUIRE(uda_aligned16(addend) && ld_add % 4 == 0, "uda_bnbwd_apply: bad addend layout");
+    const int64_t P = (int64_t)y->N * y->H * y->W;
+    LowRank lr = {nullptr, 0, 0, nullptr};
+    if (out_x3)
+        hipLaunchKernelGGL(bnbwd_apply_kernel<true>, ew_grid2(P, y->C), dim3(256), 0, (hipStream_t)stream, dU, ldu, *y, mean, invstd,
+                           c1, c2, addend, ld_add, out, ldo, P, lr, reinterpret_cast<uint32_t*>(out_x3));
+    else
+        hipLaunchKernelGGL(bnbwd_apply_kernel<false>, ew_grid2(P, y->C), dim3(256), 0, (hipStream_t)stream, dU, ldu, *y, mean, invstd,
+                           c1, c2, addend, ld_add, out, ldo, P, lr, (uint32_t*)nullptr);
+    UDA_LAUNCH_CHECK("bnbwd_apply");
+    return 0;
 }
 
 extern "C" int uda_bnbwd_apply(const float* dU, int64_t ldu, const uda_src_t* y, const float* mean, const float* invstd,
                                const float* c1, const float* c2, const float* addend, int64_t ld_add, float* out,
                                int64_t ldo, void* stream) {
-    if (int e = src_check(y, "uda_bnbwd_apply")) return e;
-    UDA_REQUIRE(y->scale && mean && invstd && c1 && c2, "uda_bnbwd_apply: needs scale/shift/mean/invstd/c1/c2");
-    UDA_REQUIRE(dU && uda_aligned16(dU) && ldu % 4 == 0 && out && uda_aligned16(out) && ldo % 4 == 0, "uda_bnbwd_apply: bad dU/out layout");
-    if (addend) UDA_REQUIRE(uda_aligned16(addend) && ld_add % 4 == 0, "uda_bnbwd_apply: bad addend layout");
-    const int64_t P = (int64_t)y->N * y->H * y->W;
-    LowRank lr = {nullptr, 0, 0, nullptr};
-    hipLaunchKernelGGL(bnbwd_apply_kernel, ew_grid2(P, y->C), dim3(256), 0, (hipStream_t)stream, dU, ldu, *y, mean, invstd,
-                       c1, c2, addend, ld_add, out, ldo, P, lr);
-    UDA_LAUNCH_CHECK("bnbwd_apply");
-    return 0;
+    UDA_REQUIRE(out, "uda_bnbwd_apply: bad dU/out layout");
+    return uda_bnbwd_apply_x3(dU, ldu, y, mean, invstd, c1, c2, addend, ld_add, out, ldo, nullptr, stream);
 }
 
-/* uda_bnbwd_apply with the low-rank upstream gradient of uda_bnbwd_reduce_lowrank */
-extern "C" int uda_bnbwd_apply_lowrank(const float* d, int64_t ldd, int k, const float* w, const uda_src_t* y, const float* mean,
-                                       const float* invstd, const float* c1, const float* c2, const float* addend, int64_t ld_add,
-                                       float* out, int64_t ldo, void* stream) {
+/* uda_bnbwd_apply_x3 with the low-rank upstream gradient of uda_bnbwd_reduce_lowrank */
+extern "C" int uda_bnbwd_apply_lowrank_x3(const float* d, int64_t ldd, int k, const float* w, const uda_src_t* y, const float* mean,
+                                          const float* invstd, const float* c1, const float* c2, const float* addend, int64_t ld_add,
+                                          float* out, int64_t ldo, void* out_x3, void* stream) {
     if (int e = src_check(y, "uda_bnbwd_apply_lowrank")) return e;
     UDA_REQUIRE(y->scale && mean && invstd && c1 && c2, "uda_bnbwd_apply_lowrank: needs scale/shift/mean/invstd/c1/c2");
-    UDA_REQUIRE(d && w && (k == 1 || k == 2) && ldd >= k && out && uda_aligned16(out) && ldo % 4 == 0, "uda_bnbwd_apply_lowrank: bad args");
+    UDA_REQUIRE(d && w && (k == 1 || k == 2) && ldd >= k, "uda_bnbwd_apply_lowrank: bad args");
+    if (int e = bnbwd_apply_dst_check("uda_bnbwd_apply_lowrank", out, ldo, out_x3)) return e;
     if (addend) UDA_REQUIRE(uda_aligned16(addend) && ld_add % 4 == 0, "uda_bnbwd_apply_lowrank: bad addend layout");
     const int64_t P = (int64_t)y->N * y->H * y->W;
     LowRank lr = {d, ldd, k, w};
-    hipLaunchKernelGGL(bnbwd_apply_kernel, ew_grid2(P, y->C), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, (int64_t)0, *y,
-                       mean, invstd, c1, c2, addend, ld_add, out, ldo, P, lr);
+    if (out_x3)
+        hipLaunchKernelGGL(bnbwd_apply_kernel<true>, ew_grid2(P, y->C), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, (int64_t)0,
+                           *y, mean, invstd, c1, c2, addend, ld_add, out, ldo, P, lr, reinterpret_cast<uint32_t*>(out_x3));
+    else
+        hipLaunchKernelGGL(bnbwd_apply_kernel<false>, ew_grid2(P, y->C), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, (int64_t)0,
+                           *y, mean, invstd, c1, c2, addend, ld_add, out, ldo, P, lr, (uint32_t*)nullptr);
     UDA_LAUNCH_CHECK("bnbwd_apply_lowrank");
     return 0;
+}
+
+extern "C" int uda_bnbwd_apply_lowrank(const float* d, int64_t ldd, int k, const float* w, const uda_src_t* y, const float* mean,
+                                       const float* invstd, const float* c1, const float* c2, const float* addend, int64_t ld_add,
+                                       float* out, int64_t ldo, void* stream) {
+    UDA_REQUIRE(out, "uda_bnbwd_apply_lowrank: bad args");
+    return uda_bnbwd_apply_lowrank_x3(d, ldd, k, w, y, mean, invstd, c1, c2, addend, ld_add, out, ldo, nullptr, stream);
 }

@@ -24,32 +24,15 @@
 //     before they were needed and the kernel ran at the load latency (2.3 us per chunk against 1.5 us of MFMA work).
 #include "common.h"
 #include "conv_plan.h"
+#include "x3_split.h"         // the packed layout and x3_split2
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
                           // (linear, conflict-free ds_write_b128), and the fragment reads of 16 lanes (rows r, byte r*112 + q*32 + h*16)
                           // fall on 64 distinct banks
 
-// Packed operand ("x3 layout"): per row (pixel, or weight row) and per 16-wide K block the three bf16 pieces, 96 contiguous bytes:
-//     element (row, k, piece q) at ((row * nb + k / 16) * 3 + q) * 16 + k % 16,   nb = K blocks per row.
-// Activations: k = channel (nb = ceil(C / 16)).  Weights: k = position in the tap-chunked K order of the fp32 layout.
-
-// (v0, v1) -> the three bf16 pieces of each, packed (v0 in the low half).
-// Domain: |v| <= 0x7F7F7FFF, the largest fp32 whose bf16 rounding is finite; above it the first piece is infinite and the split means
-// nothing.  The pieces sum to v exactly wherever v is a multiple of 2^-133, bf16's smallest subnormal (every |v| >= 2^-110); below
-// that the third piece is rounded to that grid (error <= 2^-134).  tests/kernel_spec.py x3_split states the same, bit for bit.
-__device__ __forceinline__ void x3_split2(float v0, float v1, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-    bf16x2 a = {(__bf16)v0, (__bf16)v1};                       // v_cvt_pk_bf16_f32 (round to nearest even)
-    p1 = __builtin_bit_cast(uint32_t, a);
-    const float r0 = v0 - __builtin_bit_cast(float, p1 << 16), r1 = v1 - __builtin_bit_cast(float, p1 & 0xffff0000u);   // exact
-    bf16x2 b = {(__bf16)r0, (__bf16)r1};
-    p2 = __builtin_bit_cast(uint32_t, b);
-    const float s0 = r0 - __builtin_bit_cast(float, p2 << 16), s1 = r1 - __builtin_bit_cast(float, p2 & 0xffff0000u);   // exact
-    bf16x2 c = {(__bf16)s0, (__bf16)s1};                       // s has <= 8 significant bits left: exact
-    p3 = __builtin_bit_cast(uint32_t, c);
-}
+// The packed operand ("x3 layout") and the split x3_split2: x3_split.h.
 
 // one thread: 8 consecutive k of one row -> 3 x 16 B; a workgroup's 256 octets are consecutive in the output ([row][block] order,
 // 48 B each), so the 12 KB it produces are staged in LDS in output order and stored as three fully coalesced 4 KB rows.

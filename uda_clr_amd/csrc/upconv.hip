@@ -21,6 +21,7 @@
 #include "common.h"
 #include "bilinear.h"
 #include "upconv_plan.h"
+#include "x3_split.h"
 
 __global__ __launch_bounds__(256) void upconv_fwd_kernel(const float* __restrict__ g, int64_t ldg, int N, int h, int w, int C,
                                                          int dil, const float* __restrict__ addend, int64_t ld_add,
@@ -406,7 +407,7 @@ extern "C" int uda_upconv_fwd(const float* g, int64_t ldg, int N, int h, int w, 
 // 16 cached 16-byte reads per 16-byte output at x4 instead of 81 for a thread per (pixel, tap)
 __global__ __launch_bounds__(256) void upconv_bwd_kernel(const float* __restrict__ dy, int64_t ldy, int N, int H, int W, int C,
                                                          int dil, float* __restrict__ dg, int64_t ldg, int h, int w, float sh,
-                                                         float sw) {
+                                                         float sw, uint32_t* __restrict__ dg_x3) {
     const int G = C >> 2;
     const int64_t total = (int64_t)N * h * w * G;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -447,8 +448,19 @@ __global__ __launch_bounds__(256) void upconv_bwd_kernel(const float* __restrict
                     }
             }
         }
+        if (dg) {
 #pragma unroll
-        for (int t = 0; t < 9; ++t) uda_st4(dg + q * ldg + t * C + cg * 4, acc[t]);
+            for (int t = 0; t < 9; ++t) uda_st4(dg + q * ldg + t * C + cg * 4, acc[t]);
+        }
+        if (dg_x3) {        // the same values as a packed [N*h*w, 9*C] operand (x3_split.h)
+            const int nb = x3_blocks(9 * C);
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const float v[4] = {acc[t].x, acc[t].y, acc[t].z, acc[t].w};
+                x3_store4(dg_x3, q, nb, t * C + cg * 4, v, 4);
+            }
+            if (cg == G - 1) x3_store_pad(dg_x3, q, nb, 9 * C);
+        }
     }
 }
 
@@ -460,7 +472,8 @@ __global__ __launch_bounds__(256) void upconv_bwd_kernel(const float* __restrict
 //   * the column sums are formed first, tmp[tw] = sum_ow B(ow + tw - 1) dy[oh][ow] (12 multiply-adds per dy value), then
 //     dG[(th, tw)] += A(oh + th - 1) tmp[tw] once per row.
 __global__ __launch_bounds__(256) void upconv_bwd_wave_kernel(const float* __restrict__ dy, int64_t ldy, int N, int H, int W, int C,
-                                                              float* __restrict__ dg, int64_t ldg, int h, int w, float sh, float sw) {
+                                                              float* __restrict__ dg, int64_t ldg, int h, int w, float sh, float sw,
+                                                              uint32_t* __restrict__ dg_x3) {
     const int lane = threadIdx.x & 63;
     const int64_t npix = (int64_t)N * h * w;
     const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -515,26 +528,43 @@ __global__ __launch_bounds__(256) void upconv_bwd_wave_kernel(const float* __res
                 r2.x += k * t2.x; r2.y += k * t2.y; r2.z += k * t2.z; r2.w += k * t2.w;
             }
         }
+        if (dg) {
 #pragma unroll
-        for (int t = 0; t < 9; ++t) uda_st4(dg + q * ldg + t * C + lane * 4, acc[t]);
+            for (int t = 0; t < 9; ++t) uda_st4(dg + q * ldg + t * C + lane * 4, acc[t]);
+        }
+        if (dg_x3) {        // the same values as a packed [N*h*w, 9*C] operand (x3_split.h); 9 * 256 columns: no ragged block
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const float v[4] = {acc[t].x, acc[t].y, acc[t].z, acc[t].w};
+                x3_store4(dg_x3, q, 9 * C / 16, t * C + lane * 4, v, 4);
+            }
+        }
     }
+}
+
+// dg (fp32 rows [N*h*w, ldg]), dg_x3 (the same matrix as a packed bf16x3 operand of 9*C columns) or both
+extern "C" int uda_upconv_bwd_x3(const float* dy, int64_t ldy, int N, int H, int W, int C, int dil, float* dg, int64_t ldg, void* dg_x3,
+                                 int h, int w, void* stream) {
+    UDA_REQUIRE(dy && (dg || dg_x3) && uda_aligned16(dy) && uda_aligned16(dg) && uda_aligned16(dg_x3) && ldy % 4 == 0 && ldy >= C,
+                "uda_upconv_bwd: dy and dg / dg_x3 must be 16-byte aligned, dy [N*H*W, >= C] with a row stride that is a multiple of 4");
+    const UpconvPlan p = upconv_plan(UP_BWD, N, h, w, H, W, C, dil, dg ? ldg : 9 * (int64_t)C, false, 0, 0, false);
+    UDA_REQUIRE(!p.error, "uda_upconv_bwd: %s", p.error);
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* px = reinterpret_cast<uint32_t*>(dg_x3);
+    if (p.kernel == UPK_WAVE) {
+        hipLaunchKernelGGL(upconv_bwd_wave_kernel, dim3(p.grid), dim3(256), 0, st, dy, ldy, N, H, W, C, dg, ldg, h, w, p.sh, p.sw, px);
+        UDA_LAUNCH_CHECK("upconv_bwd_wave");
+    } else {
+        hipLaunchKernelGGL(upconv_bwd_kernel, dim3(p.grid), dim3(256), 0, st, dy, ldy, N, H, W, C, dil, dg, ldg, h, w, p.sh, p.sw, px);
+        UDA_LAUNCH_CHECK("upconv_bwd");
+    }
+    return 0;
 }
 
 extern "C" int uda_upconv_bwd(const float* dy, int64_t ldy, int N, int H, int W, int C, int dil, float* dg, int64_t ldg, int h,
                               int w, void* stream) {
-    UDA_REQUIRE(dy && dg && uda_aligned16(dy) && uda_aligned16(dg) && ldy % 4 == 0 && ldy >= C,
-                "uda_upconv_bwd: dy and dg must be 16-byte aligned, dy [N*H*W, >= C] with a row stride that is a multiple of 4");
-    const UpconvPlan p = upconv_plan(UP_BWD, N, h, w, H, W, C, dil, ldg, false, 0, 0, false);
-    UDA_REQUIRE(!p.error, "uda_upconv_bwd: %s", p.error);
-    hipStream_t st = (hipStream_t)stream;
-    if (p.kernel == UPK_WAVE) {
-        hipLaunchKernelGGL(upconv_bwd_wave_kernel, dim3(p.grid), dim3(256), 0, st, dy, ldy, N, H, W, C, dg, ldg, h, w, p.sh, p.sw);
-        UDA_LAUNCH_CHECK("upconv_bwd_wave");
-    } else {
-        hipLaunchKernelGGL(upconv_bwd_kernel, dim3(p.grid), dim3(256), 0, st, dy, ldy, N, H, W, C, dil, dg, ldg, h, w, p.sh, p.sw);
-        UDA_LAUNCH_CHECK("upconv_bwd");
-    }
-    return 0;
+    UDA_REQUIRE(dg, "uda_upconv_bwd: dy and dg must be 16-byte aligned, dy [N*H*W, >= C] with a row stride that is a multiple of 4");
+    return uda_upconv_bwd_x3(dy, ldy, N, H, W, C, dil, dg, ldg, nullptr, h, w, stream);
 }
 
 // ---- routes: the plan as a short stable text, for tests and tools

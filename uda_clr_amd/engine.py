@@ -111,6 +111,7 @@ class GeneratorEngine:
         # the trainers fetch the flag with their single host sync and raise like the reference's NaN checks
         # (Trainer_prototype_full.py:296-299).
         self.nonfinite = None
+        self._x3_producers = True       # gradient matrices of bf16x3 readers in packed form from their producers (backward); False: fp32 + packing passes
         if backbone not in BACKBONES:
             raise NotImplementedError("backbone %r" % (backbone,))
         self.bb = BACKBONES[backbone]["exec"](self, output_stride)      # the backbone's part of forward / backward
@@ -523,13 +524,16 @@ class GeneratorEngine:
         return out
 
     # ------------------------------------------------------------------ backward pieces
-    def _bn_backward(self, ctx, G, y: Act, dU, out=None, addend=None, keys=None, q1_total=None, lowrank=None):
+    def _bn_backward(self, ctx, G, y: Act, dU, out=None, addend=None, keys=None, q1_total=None, lowrank=None, out_x3=None):
         """dU: gradient w.r.t. the activated values of ``y``.  Writes the gradient w.r.t. the raw
         tensor y.x into ``out`` (default: in place over dU) and the BN parameter gradients into G.
         ``lowrank`` = (d [P, k], w [k, C]) instead of dU: the gradient is the outer product d @ w (the input gradient of a 1x1 conv
-        to one or two outputs) and is formed inside the two passes, never written (``out`` is then required)."""
+        to one or two outputs) and is formed inside the two passes, never written (``out`` is then required).
+        ``out_x3``: the packed bf16x3 form of ``out`` (``K.packed_out``), written by the same pass."""
         K = self.K
         lr = {} if lowrank is None else {"lowrank": lowrank}
+        if out_x3 is not None:
+            lr["out_x3"] = out_x3
         if y.bn is None:
             raise RuntimeError("this activation's BatchNorm kept no backward record (forward ran without gradient bookkeeping)")
         C = y.C
@@ -541,7 +545,7 @@ class GeneratorEngine:
         else:
             sums = ctx.arena.take(3, C)
             cg = self._empty(y.x, 4, C)
-        K.bnbwd_reduce(dU, y, sums, **lr)
+        K.bnbwd_reduce(dU, y, sums, **({} if lowrank is None else {"lowrank": lowrank}))
         K.bnbwd_finalize(sums, y, cg[0], cg[1], cg[2], cg[3], **({} if q1_total is None else {"q1_total": q1_total}))
         out = dU if out is None else out
         K.bnbwd_apply(dU, y, cg[0], cg[1], out, addend, **lr)
@@ -633,23 +637,40 @@ class GeneratorEngine:
         d_x2b = d_xf[:, 304:305]
         self._wgrad(ctx, G, "decoder.last_conv_boundary.8.weight", b2, d_x2b, 1, 1)
         self._bias_grad(G, "decoder.last_conv_boundary.8.bias", d_x2b)
-        dy2 = self._empty(x, P4, 256)
+        # Gradient matrices that bf16x3 convs read are written as packed operands by their producers (no packing pass; dy2 and
+        # dG, which nothing else reads, in packed form only) - when the library routes every such reader to the bf16x3 kernels
+        # in one launch
+        key0, CF = "decoder.last_conv_boundary.0.weight", self.C_FEAT
+        w0 = ctx.params[key0]
+        O0 = w0.shape[0]
+        x3p = self._x3_producers and not self.tn and hasattr(K, "packed_out") and hasattr(K, "conv_route_x3")
+        x3_dy2 = x3p and K.wgrad_route_x3(N, H4, W4, b1.C, 256, 3) and K.conv_route_x3(N, H4, W4, 256, b1.C, 3)
+        x3_dy1 = x3p and (K.wgrad_route_x3(N, H4, W4, 304 - CF, O0, 3) or K.conv_route_x3(N, H4, W4, O0, 304 - CF, 3))
+        x3_dG = x3p and K.wgrad_route_x3(N, H16, W16, CF, 9 * O0, 1) and K.conv_route_x3(N, H16, W16, 9 * O0, CF, 1)
         w_bnd = ctx.params["decoder.last_conv_boundary.8.weight"].reshape(1, 256).contiguous()
-        self._bn_backward(ctx, G, b2, None, out=dy2, lowrank=(d_x2b, w_bnd))       # 256 -> 1 head: rank one
+        if x3_dy2:
+            dy2, dy2_x3 = K.packed_out(P4, 256, x.device)
+        else:
+            dy2, dy2_x3 = self._empty(x, P4, 256), None
+        self._bn_backward(ctx, G, b2, None, out=dy2, lowrank=(d_x2b, w_bnd), out_x3=dy2_x3)       # 256 -> 1 head: rank one
         self._wgrad(ctx, G, "decoder.last_conv_boundary.4.weight", b1, dy2, 3, 1)
         dU1 = self._empty(x, P4, 256)
         self._dgrad(ctx, "decoder.last_conv_boundary.4.weight", dy2, N, H4, W4, 3, 1, dU1)
-        del dy2
-        dy1 = self._bn_backward(ctx, G, b1, dU1)
+        del dy2, dy2_x3
+        # dy1 keeps its fp32 rows (uda_upconv_bwd reads them): both forms in one pass
+        dy1 = self._bn_backward(ctx, G, b1, dU1, out_x3=K.packed_out(P4, 256, x.device, fp32=dU1)[1] if x3_dy1 else None)
         # conv0, split as in _conv0: low-level part on the high-resolution kernels, upsampled part through the adjoint
         # interpolation (dG) and low-resolution GEMMs
-        key0, CF = "decoder.last_conv_boundary.0.weight", self.C_FEAT
-        w0 = ctx.params[key0]
         dw_low = self._empty(x, w0.shape[0], w0.shape[1] - CF, 3, 3)
         K.conv_wgrad(Act(xf[:, CF:304], N, H4, W4), dy1, 3, 1, dw_low)
         K.conv(Act(dy1, N, H4, W4), self._w(ctx, key0, "low_dgrad"), 3, 1, d_xf[:, CF:304], addend=d_xf[:, CF:304])
-        dG = self._empty(x, P16, 9 * w0.shape[0])
-        K.upconv_bwd(dy1, N, H4, W4, dG, H16, W16)
+        if x3_dG:
+            dG, dG_x3 = K.packed_out(P16, 9 * O0, x.device)
+            K.upconv_bwd(dy1, N, H4, W4, dG, H16, W16, dg_x3=dG_x3)
+            del dG_x3
+        else:
+            dG = self._empty(x, P16, 9 * O0)
+            K.upconv_bwd(dy1, N, H4, W4, dG, H16, W16)
         dw_taps = self._empty(x, 9 * w0.shape[0], CF, 1, 1)
         K.conv_wgrad(Act(D["feature"], N, H16, W16), dG, 1, 1, dw_taps)
         dw0 = torch.empty_like(w0)

@@ -273,13 +273,29 @@ class HipKernels:
         r = slice(n0 * ppi, n1 * ppi)
         return Act(a.x[r], n1 - n0, a.H, a.W, a.scale, a.shift, a.act, None if a.mask is None else a.mask[r], a.mask_scale, a.bn, a.meta)
 
+    @staticmethod
+    def _x3_only(t):
+        """True for a matrix that exists only as its packed bf16x3 operand (``_packed_only``): its fp32 values are uninitialised"""
+        return getattr(t, "_x3_only", False)
+
+    def _refuse_x3_only(self, who, why, *operands):
+        """A packed-only operand can be read by the bf16x3 kernels alone, whole: anything else would read its uninitialised fp32
+        view (a slice of it, ``_act_rows``, also loses the attached packed form)."""
+        for t in operands:
+            if self._x3_only(t):
+                raise RuntimeError("%s: a packed-only [%d, %d] operand %s; its fp32 values were never written"
+                                   % (who, t.shape[0], t.shape[1], why))
+
     def conv(self, src: Act, w, ksize, dil, out, bias=None, addend=None, stats=None, origin=0, stride=1):
         """stride 2 (wide tiles only: the C side raises otherwise): ``out`` / ``addend`` / ``stats`` live on the strided grid"""
+        if self.mfma == self.MFMA_F32:
+            self._refuse_x3_only("conv", "reaches the fp32 matrix mode", src.x)
         groups = self._image_groups(src.N, src.P // src.N, max(src.x.stride(0), out.stride(0), 0 if addend is None else addend.stride(0),
                                                                0 if src.mask is None else src.mask.stride(0) // 4),
                                     src.C if self.mfma != self.MFMA_F32 else 0)
         Po = src.N * ((src.H - 1) // stride + 1) * ((src.W - 1) // stride + 1)
         if groups is not None:
+            self._refuse_x3_only("conv", "would be sliced into %d image groups" % len(groups), src.x)
             ppo = Po // src.N
             for n0, n1 in groups:
                 r = slice(n0 * ppo, n1 * ppo)
@@ -301,6 +317,7 @@ class HipKernels:
                 ws = self._ws(out, nws)
                 a.workspace, a.workspace_bytes = ws.data_ptr(), nws
             return self._conv_x3(a)
+        self._refuse_x3_only("conv", "reaches a route that reads fp32 rows", src.x)
         self._ck(self.lib.uda_conv_fwd(C.byref(a), self._stream()))
 
     def conv_args(self, usrc: UdaSrc, Cout, ksize, dil=1, origin=0, stride=1, w=None, bias=None, addend=None, ld_add=0, y=None, ldy=0,
@@ -371,6 +388,7 @@ class HipKernels:
             raise RuntimeError("bf16x3 packed operand of %d bytes attached to a [%d, %d] matrix (expected %d): stale attachment"
                                % (xs.numel(), src.P, src.C, int(self.lib.uda_x3_packed_bytes(src.P, src.C))))
         if xs is None:
+            self._refuse_x3_only("bf16x3 packing", "has lost its packed form and would be re-packed from its fp32 view", src.x)
             xs = self.x3_pack(usrc, src.P, src.C, device)
             if raw:
                 try:
@@ -391,10 +409,13 @@ class HipKernels:
 
     def conv_wgrad(self, src: Act, dy, ksize, dil, dw, origin=0, stride=1):
         """stride 2 (wide tiles only): ``dy`` lives on the strided output grid of the forward conv"""
+        if self.mfma == self.MFMA_F32:
+            self._refuse_x3_only("conv_wgrad", "reaches the fp32 matrix mode", src.x, dy)
         groups = self._image_groups(src.N, src.P // src.N, max(src.x.stride(0), dy.stride(0), 0 if src.mask is None else src.mask.stride(0) // 4))
         Ho, Wo = (src.H - 1) // stride + 1, (src.W - 1) // stride + 1
         Po = src.N * Ho * Wo
         if groups is not None:
+            self._refuse_x3_only("conv_wgrad", "would be sliced into %d image groups" % len(groups), src.x, dy)
             ppo = Po // src.N
             tmp = torch.empty_like(dw)
             for i, (n0, n1) in enumerate(groups):
@@ -412,6 +433,8 @@ class HipKernels:
             dsrc = Act(dy, src.N, Ho, Wo)
             xd = self._packed(dsrc, self._src(dsrc), dy.device)
             a.x3_src, a.x3_dy = xs.data_ptr(), xd.data_ptr()
+        else:
+            self._refuse_x3_only("conv_wgrad", "reaches a route that reads fp32 rows", src.x, dy)
         self._ck(self.lib.uda_conv_wgrad(C.byref(a), self._stream()))
 
     def wgrad_args(self, usrc: UdaSrc, Cout, ksize, dil=1, origin=0, stride=1, dy=None, lddy=0, dw=None) -> UdaWgradArgs:
@@ -651,11 +674,32 @@ class HipKernels:
     def _packed_only(self, rows, Cc, device):
         """A [rows, Cc] fp32 matrix that exists ONLY in packed bf16x3 form: the returned tensor is an (uninitialised, never
         read) fp32 view over the head of the packed buffer, which rides on it as ``_x3`` like any cached packed operand -
-        the x3 conv / weight-gradient kernels read nothing else.  Returns (matrix, packed bytes)."""
+        the x3 conv / weight-gradient kernels read nothing else.  It is marked (``_x3_only``): ``conv``, ``conv_wgrad`` and
+        ``_packed`` raise where it would be read as fp32 rows (``_refuse_x3_only``).  Returns (matrix, packed bytes)."""
         xs = torch.empty(int(self.lib.uda_x3_packed_bytes(rows, Cc)), dtype=torch.uint8, device=device)
         m = xs[:rows * Cc * 4].view(torch.float32).view(rows, Cc)
         m._x3 = xs
+        m._x3_only = True
         return m, xs
+
+    def packed_out(self, rows, Cc, device, fp32=None):
+        """The destination(s) of a producer that writes its [rows, Cc] result as a packed bf16x3 operand (``bnbwd_apply`` /
+        ``upconv_bwd`` with ``out_x3``): -> (matrix, packed bytes).  Without ``fp32`` the matrix is packed-only
+        (``_packed_only``); with it (a [rows, Cc] fp32 matrix the producer writes too) the packed form is attached to that."""
+        if fp32 is None:
+            return self._packed_only(rows, Cc, device)
+        assert tuple(fp32.shape) == (rows, Cc)
+        xs = torch.empty(int(self.lib.uda_x3_packed_bytes(rows, Cc)), dtype=torch.uint8, device=device)
+        fp32._x3 = xs
+        return fp32, xs
+
+    def _x3_dst(self, out, out_x3, rows, Cc):
+        """(fp32 address or None, row stride, packed address) of a producer's destinations; a packed-only ``out`` has no fp32 side"""
+        assert out_x3.dtype == torch.uint8 and out_x3.is_contiguous() and out_x3.data_ptr() % 16 == 0
+        assert out_x3.numel() == int(self.lib.uda_x3_packed_bytes(rows, Cc))
+        if out is None or self._x3_only(out):
+            return None, 0, out_x3.data_ptr()
+        return _mat(out, "out") + (out_x3.data_ptr(),)
 
     def s2d_pack_fwd(self, src, N, Hs, Ws, Cc, vh, vw, slope):
         """uda_s2d_fwd + uda_x3_pack in one pass: src rows [N*Hs*Ws, Cc] -> the packed z image (a packed-only matrix
@@ -816,11 +860,26 @@ class HipKernels:
                                              c1.data_ptr(), c2.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
                                              self._stream()))
 
-    def bnbwd_apply(self, dU, y: Act, c1, c2, out, addend=None, lowrank=None):
+    def bnbwd_apply(self, dU, y: Act, c1, c2, out, addend=None, lowrank=None, out_x3=None):
+        """``out_x3`` (uint8, uda_x3_packed_bytes(P, C) bytes): the result also - with a packed-only or absent ``out``: only - as
+        the packed bf16x3 operand ``x3_pack`` would make of ``out``, written in the same pass (``packed_out``)"""
         s = self._src(y)
+        ad, lda = (None, 0) if addend is None else _mat(addend, "addend")
+        if out_x3 is not None:
+            assert out is None or y.x.shape == out.shape
+            o, ldo, ox = self._x3_dst(out, out_x3, y.P, y.C)
+            if lowrank is not None:
+                dp, ldd, k, wp = self._lowrank(lowrank, y)
+                self._ck(self.lib.uda_bnbwd_apply_lowrank_x3(dp, ldd, k, wp, C.byref(s), y.bn.mean.data_ptr(), y.bn.invstd.data_ptr(),
+                                                             c1.data_ptr(), c2.data_ptr(), ad, lda, o, ldo, ox, self._stream()))
+                return
+            assert dU.shape == y.x.shape
+            d, ldu = _mat(dU, "dU")
+            self._ck(self.lib.uda_bnbwd_apply_x3(d, ldu, C.byref(s), y.bn.mean.data_ptr(), y.bn.invstd.data_ptr(),
+                                                 c1.data_ptr(), c2.data_ptr(), ad, lda, o, ldo, ox, self._stream()))
+            return
         assert y.x.shape == out.shape
         o, ldo = _mat(out, "out")
-        ad, lda = (None, 0) if addend is None else _mat(addend, "addend")
         if lowrank is not None:
             dp, ldd, k, wp = self._lowrank(lowrank, y)
             self._ck(self.lib.uda_bnbwd_apply_lowrank(dp, ldd, k, wp, C.byref(s), y.bn.mean.data_ptr(), y.bn.invstd.data_ptr(),
@@ -895,11 +954,17 @@ class HipKernels:
         self._ck_stats(stats, Cc)
         self._ck(self.lib.uda_upconv_fwd(gp, ldg, N, h, w, Cc, dil, ad, lda, rows, o, ldo, H, W, _ptr(stats), self._stream()))
 
-    def upconv_bwd(self, dy, N, H, W, dg, h, w, dil=1):
+    def upconv_bwd(self, dy, N, H, W, dg, h, w, dil=1, dg_x3=None):
+        """``dg_x3`` (uint8, uda_x3_packed_bytes(N*h*w, 9*C) bytes): dg also - with a packed-only or absent ``dg``: only - as the
+        packed bf16x3 operand ``x3_pack`` would make of it, written in the same pass (``packed_out``)"""
         self._dev(dy)
         Cc = dy.shape[1]
-        assert dy.shape[0] == N * H * W and dg.shape == (N * h * w, 9 * Cc)
+        assert dy.shape[0] == N * H * W and (dg is None or dg.shape == (N * h * w, 9 * Cc))
         d, ldy = _mat(dy, "dy")
+        if dg_x3 is not None:
+            gp, ldg, gx = self._x3_dst(dg, dg_x3, N * h * w, 9 * Cc)
+            self._ck(self.lib.uda_upconv_bwd_x3(d, ldy, N, H, W, Cc, dil, gp, ldg, gx, h, w, self._stream()))
+            return
         gp, ldg = _mat(dg, "dg")
         self._ck(self.lib.uda_upconv_bwd(d, ldy, N, H, W, Cc, dil, gp, ldg, h, w, self._stream()))
 
